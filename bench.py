@@ -52,7 +52,11 @@ def main():
                     help="BASELINE.json configs[N]: 1 = the headline (10 M reads, k=31, coverage 5, bothdirs False); 2 = k=63 poly-hash "
                          "keys, coverage 3, bothdirs True on 100 x 5 Mb contigs (100 M reads at full size: give --reads to scale down)")
     ap.add_argument("--total-reads", type=int, default=0, help="reads of the whole job, split evenly over the ranks (configs[3]: 1000000000 on 8 GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -171,7 +175,7 @@ def main():
                 levels += r["levels"]
                 lookups += r["lookups"]
             bfs_ms = res[0]["device_ms"]
-            info.update(bfs_ms=bfs_ms, reached=reached, levels=levels, lookups=lookups)
+            info.update(bfs_ms=bfs_ms, reached=reached, levels=levels, lookups=lookups, bfs_res=res)
         if in_place:
             sc.walk_done(dst=0)  # (the other ranks' tables were being read: nobody clears before rank 0 has let go)
 
@@ -204,6 +208,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     st = ctx.stats()
+    if args.dump_outputs and rank == 0:  # (after the timed steps and their stats: nothing of it is timed)
+        dump_outputs(args.dump_outputs, ctx if world == 1 else None, k, args.contigs * args.contig_len, info)
     # what every rank spent where, per step (ms, host clocks): the record of a multi-GPU run must say how many ranks there
     # were and what each of them did, so that a scaling number can be read without the source
     ranks_seen, rank_phases = world, None
@@ -393,6 +399,54 @@ def main():
         dist.destroy_process_group()
     if out is not None:
         print(json.dumps(out), flush=True)
+
+
+DUMP_SAMPLE, DUMP_SEED, DUMP_GENOME_SPAN, DUMP_BFS_MAX = 1 << 17, 7, 1 << 24, 1 << 18
+
+
+def dump_outputs(out_dir, ctx, k, genome_bases, info):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float64 .npy files (about 17 MB at the defaults,
+    at most about 45 MB).  64-bit words are stored as exact (high 32 bits, low 32 bits) pairs.
+
+    distinct_kmers.npy  [mc_finalize_counts' number of distinct k-mers]
+    bfs<i>_kmer.npy     (n, 4) the k-mers of pass i in insertion order: (hi >> 32, hi & 0xffffffff, lo >> 32, lo & 0xffffffff)
+    bfs<i>_dist/cov/last.npy, bfs<i>_levels.npy   the rest of pass i (0 = runBfs(-1), 1 = runBfs(+1); one pass with bothdirs);
+        a pass of more than DUMP_BFS_MAX vertices is cut to a seeded sample of them, in order (bfs<i>_index.npy: which ones)
+    count_sample_kmer.npy / count_sample_count.npy   one GPU only: the table's counts (mc_get) of a fixed, seeded sample of
+        k-mers -- DUMP_SAMPLE windows of the synthetic genome (counted about --coverage times over) and as many random k-mers
+        (nearly all absent: -1, as mc_get answers).  Every number is a function of the arguments alone, so two builds compare file for file."""
+    import numpy as np
+
+    def halves(a):
+        a = np.asarray(a, dtype=np.uint64)
+        return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    arrays = {"distinct_kmers": np.array([info["distinct"]], dtype=np.float64)}
+    for i, r in enumerate(info["bfs_res"]):
+        sel = slice(None)
+        if len(r["lo"]) > DUMP_BFS_MAX:
+            sel = np.sort(rng.choice(len(r["lo"]), DUMP_BFS_MAX, replace=False))
+            arrays["bfs%d_index" % i] = sel.astype(np.float64)
+        arrays["bfs%d_kmer" % i] = np.concatenate([halves(r["hi"][sel]), halves(r["lo"][sel])], axis=1)
+        for f in ("dist", "cov", "last"):
+            arrays["bfs%d_%s" % (i, f)] = r[f][sel].astype(np.float64)
+        arrays["bfs%d_levels" % i] = np.array([r["levels"]], dtype=np.float64)
+    if ctx is not None:
+        import metacherchant_amd as m
+        span = min(genome_bases, DUMP_GENOME_SPAN)
+        genome = m.native.synth_genome(GENOME_SEED, 0, span)
+        pos = rng.integers(0, span - k + 1, DUMP_SAMPLE)
+        codes = np.concatenate([genome[pos[:, None] + np.arange(k)], rng.integers(0, 4, size=(DUMP_SAMPLE, k), dtype=np.uint8)])
+        hi, lo = np.zeros(len(codes), dtype=np.uint64), np.zeros(len(codes), dtype=np.uint64)
+        for j in range(k):  # (the 2k-bit number hi << 64 | lo, first base most significant, as the walk's seeds are built)
+            hi = (hi << np.uint64(2)) | (lo >> np.uint64(62))
+            lo = (lo << np.uint64(2)) | codes[:, j].astype(np.uint64)
+        arrays["count_sample_kmer"] = np.concatenate([halves(hi), halves(lo)], axis=1)
+        arrays["count_sample_count"] = ctx.get(ctx.kmer_keys(hi, lo)).astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def config2_leg(args, m, torch, dev, local_rank, d_words, d_off, R, L, n_bases):
