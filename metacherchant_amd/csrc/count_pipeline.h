@@ -441,7 +441,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_p2_scatter(const uint64_t *__res
                                                            uint32_t piece = 0, uint32_t n_pieces = 1)
 {
     // piece / n_pieces: a large batch travels in n_pieces pieces that reuse the level-1 buffers one after the other;
-    // every leaf then has n_pieces segments of capacity cap2 and this launch fills segment `piece` (as k_sk2_scatter)
+    // every leaf then has n_pieces segments of capacity cap2 and this launch fills segment `piece`
     __shared__ ScatterLds L;
     const uint32_t tid = threadIdx.x;
     const uint32_t n_buckets = m2;  // leaves per level-1 bucket
@@ -1142,8 +1142,8 @@ __global__ void __launch_bounds__(PT_THREADS) k_sk2_scatter(const uint4 *__restr
                                                             uint64_t cap2, uint4 *out_recs, uint32_t *out_bins, SkSpill sp, uint32_t nseg_in = PT_SEGMENTS,
                                                             int bin_of = 0, uint32_t piece = 0, uint32_t n_pieces = 1)
 {
-    // piece / n_pieces: the batch travels in n_pieces pieces (the level-1 pass of one runs next to this pass of the
-    // one before it); every leaf then has n_pieces segments of capacity cap2 and this launch fills segment `piece`.
+    // piece / n_pieces: the batch travels in n_pieces pieces; every leaf then has n_pieces segments of capacity cap2 and
+    // this launch fills segment `piece` (as k_p2_scatter; the host launches this kernel in one piece).
     // bin_of == 0: super-k-mer records -- the bucket digits come from the bin word inside the record (rec.x) and the
     // second stream (in_bins / out_bins) is the records' read pointers; != 0: other 16-byte payloads (the entries of the
     // solid-table build) whose bin word IS the second stream.

@@ -40,6 +40,7 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1 } ncclDataType_t;
 #include "count_pipeline.h"
 #include "count_long.h"
 #include "tokenizer.h"
+#include "switches.h"
 #include "host/envfinder.h"
 
 using namespace mc;
@@ -111,7 +112,7 @@ struct PoolBuf {  // RAII: a block of a DevPool
 struct TablePool {
     std::mutex mu;
     std::map<int, DevPool> per_device;
-    bool on = [] { const char *e = getenv("MC_TABLE_POOL"); return !(e && !strcmp(e, "0")); }();
+    bool on = read_pool_switches().table_pool;
     hipError_t get(int dev, size_t bytes, void **out, size_t *got)
     {
         if (!on) { *got = bytes; return hipMalloc(out, bytes); }
@@ -150,7 +151,7 @@ struct ScratchPool {
     static constexpr size_t MIN_BYTES = 64ull << 20;
     std::mutex mu;
     std::map<int, DevPool> per_device;
-    bool on = [] { const char *e = getenv("MC_SCRATCH_POOL"); return !(e && !strcmp(e, "0")); }();
+    bool on = read_pool_switches().scratch_pool;
     hipError_t get(int dev, size_t bytes, void **out, size_t *got)
     {
         if (!on || bytes < MIN_BYTES) { *got = bytes; return hipMalloc(out, std::max<size_t>(bytes, 1)); }
@@ -180,7 +181,7 @@ struct ScratchPool {
         std::lock_guard<std::mutex> g(mu);
         per_device[dev].release();
     }
-    size_t max_idle = [] { const char *e = getenv("MC_SCRATCH_POOL_GB"); return (size_t)((e ? atof(e) : 64.0) * 1e9); }();
+    size_t max_idle = read_pool_switches().scratch_idle_max;
 };
 static ScratchPool g_scratch_pool;
 
@@ -214,13 +215,14 @@ struct BfsJobBuffers {
 
 struct mc_ctx {
     mc_config cfg{};
+    mc_switches sw;  // the environment switches, read by mc_create (switches.h)
     std::mutex mu;
     std::string err;
     hipStream_t own_stream = nullptr, stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // the second scatter level of one piece of a batch runs here, next to the first level of the next piece (add_reads_partitioned)
+    // a side stream: the read store's copy of a batch (rs_append) and the walk's companions (mc_bfs_batch) run here
     hipStream_t pipe_stream = nullptr;
-    hipEvent_t ev_piece[8] = {}, ev_p2 = nullptr;
+    hipEvent_t ev_piece[8] = {};
     hipEvent_t ev_seq[16] = {};  // behind every kernel of a per-window run in pieces (add_reads_partitioned_once)
     hipEvent_t ev_t[4] = {};  // P1 start, P1 end, P2 end, P3 end of a pipeline run enqueued without a host round trip in between
     // The read store: the packed bases of every read this context was given since the last mc_clear, batch after
@@ -265,7 +267,6 @@ struct mc_ctx {
     uint32_t solid_lg = 0;
     int solid_cov = -1;  // -1: not built / stale
     bool solid_external = false;  // built by mc_solid_from_pairs_dev, not from this context's counting table
-    bool bfs_direct = true;       // the BFS walks the counting table itself instead of a solid copy (MC_BFS_DIRECT=0: copy)
     bool solid_is_table = false;  // ... and does so now (solid_view)
     bool want_list = false;       // the merge kernel lists the solid keys (count_pipeline.h P3Emit): for exports, and for the copy
     int solid_external_cov = -1;
@@ -308,7 +309,6 @@ struct mc_ctx {
     hipStream_t pin_stream[8] = {};
     int mm_k = 0;        // != 0 (= k): regions are minimizer bins and reads are counted as super-k-mers (kmer_device.h)
     bool virgin = true;  // the table holds no key and its memory is not initialised yet
-    int count_path = 0;  // 0 auto, 1 direct (atomics), 2 partitioned; MC_COUNT_PATH=direct|partition overrides
     bool sk_form = false;  // reads of this context can travel as super-k-mer records (set once; mm_k may be given up later)
     // scratch of the partitioned counting pipeline, kept between calls
     struct Pipe {
@@ -1354,9 +1354,11 @@ static int ensure_buf(mc_ctx *c, T **p, uint64_t *cap, uint64_t need)
 
 // ------------------------------------------------------------------------------------------ equal keys in different regions (dup_check.h)
 
+// MC_DUP_CHECK=0: no join.  The one switch read on every call rather than at mc_create (switches.h): bench.py turns it off on a
+// live context to measure the unchecked rate (config2.value_unchecked).
 static bool dup_check_on()
 {
-    const char *e = getenv("MC_DUP_CHECK");  // (read on every call: the tests switch it)
+    const char *e = getenv("MC_DUP_CHECK");
     return !(e && !strcmp(e, "0"));
 }
 
@@ -1422,13 +1424,12 @@ static void dup_arm(mc_ctx *c, double keys, uint32_t grid)
 {
     mc_ctx::Dup &D = c->dup;
     D.l1_armed = false;
-    static const bool fused = [] { const char *e = getenv("MC_DUP_FUSED"); return !(e && !strcmp(e, "0")); }();
-    if (!fused || !dup_check_on() || keys < 1.0) return;
+    if (!dup_check_on() || keys < 1.0) return;
     const std::string keep = c->err;
     if (dup_small_bufs(c)) { c->err = keep; (void)hipGetLastError(); return; }
     const uint32_t nseg = grid + 1;  // (the last one: keys that enter the table outside the merge kernel)
     uint64_t cap = dup_cap(keys / ((double)DUP_B1 * (double)grid));
-    if (const char *e = getenv("MC_DUP_L1_SCALE")) cap = std::max<uint64_t>(4, (uint64_t)((double)cap * atof(e)));  // (tests: streams that overflow)
+    if (c->sw.dup_l1_scale != 1.0) cap = std::max<uint64_t>(4, (uint64_t)((double)cap * c->sw.dup_l1_scale));  // (tests: streams that overflow)
     if (D.l1_words < (uint64_t)DUP_B1 * nseg * cap) dup_make_room(c, (uint64_t)DUP_B1 * nseg * cap * 8);
     if (ensure_buf(c, &D.l1_keys, &D.l1_words, (uint64_t)DUP_B1 * nseg * cap) || ensure_buf(c, &D.l1_counts, &D.l1_counts_cap, (uint64_t)DUP_B1 * nseg)) {
         c->err = keep;
@@ -1519,7 +1520,7 @@ static int ensure_dups(mc_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     n_used = c->h_scratch[20];
     bool have_l1 = D.l1_armed && (uint32_t)c->h_scratch[21] == 0;
-    if (D.l1_armed && !have_l1 && getenv("MC_INGEST_DEBUG"))
+    if (D.l1_armed && !have_l1 && c->sw.ingest_debug)
         fprintf(stderr, "[join] a segment of the merge kernel's key streams overflowed (the table holds %llu keys): the first level by a sweep\n", (unsigned long long)c->h_scratch[20]);
     D.l1_armed = false;  // (whatever happens next: the streams serve one join)
     if (n_used < 2) { D.checked = true; c->st.dup_keys = 0; return MC_OK; }
@@ -1591,7 +1592,7 @@ static int ensure_dups(mc_ctx *c)
         // more from a sweep, whose streams are sized by the number of keys the table holds
         if (attempt >= 1 || !have_l1)
             return fail(c, MC_EOVERFLOW, "internal: the key streams of the duplicate-key join overflowed (%llu keys)", n_used);
-        if (getenv("MC_INGEST_DEBUG")) fprintf(stderr, "[join] the merge kernel's key streams overflowed (sized for %.0f keys, the table holds %llu): once more from a sweep\n",
+        if (c->sw.ingest_debug) fprintf(stderr, "[join] the merge kernel's key streams overflowed (sized for %.0f keys, the table holds %llu): once more from a sweep\n",
                                                c->cfg.capacity_hint ? (double)c->cfg.capacity_hint : D.expected_keys, n_used);
         have_l1 = false;
     }
@@ -1615,7 +1616,7 @@ struct PipePlan {
     uint32_t b1 = 0, b2 = 1, g = 0;  // b1 level-1 buckets of b2 leaves each (counts, not bits); a leaf covers 2^g regions
     uint64_t np1 = 0, n_leaves = 0, cap1 = 0, cap2 = 0, spill_cap = 0, wb = 0;
     uint32_t nseg1 = PT_SEGMENTS;  // segments of every level-1 bucket = workgroups of the level-1 kernel
-    uint32_t pieces = 1;           // the reads go through P1 / P2 in this many pieces (cap1, cap2: per piece); P3 sees `pieces` segments per leaf
+    uint32_t pieces = 1;           // one key a window: the reads go through P1 / P2 in this many pieces (cap1, cap2: per piece); P3 sees `pieces` segments per leaf
     bool sk = false;  // the streams hold super-k-mer records; capacities are in records
     // compact: the streams hold 16-byte units and no pointer arrays (count_pipeline.h k_sk1w_extract<false, true>, k_sk2_scatter_compact):
     // every level-1 segment = workgroup took chunk_tiles consecutive tiles, the first of them at base position pos0
@@ -1676,7 +1677,6 @@ static const char *plan_levels(const mc_ctx *c, bool records, uint64_t *n_leaves
     uint64_t np1 = PT_MAX_BUCKETS;
     while (np1 < max_b1_big && n_leaves > np1 * max_b2) np1 *= 2;
     np1 = std::min<uint64_t>(n_leaves, np1);
-    if (records) if (const char *e = getenv("MC_SK_B1")) np1 = std::min<uint64_t>(n_leaves, std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), max_b1_big));  // (tuning runs)
     while (n_leaves % np1) np1--;  // (a power of two, or 512 dividing a multiple of 512)
     if (n_leaves / np1 > max_b2) return "the leaves do not fit two scatter levels";
     *n_leaves_out = n_leaves; *g_out = g; *np1_out = np1;
@@ -1742,19 +1742,14 @@ static int pipe_prepare(mc_ctx *c, uint64_t wb, PipePlan *pl, uint64_t n_records
     pl->sk = n_records != 0;
     if (pl->b2 <= 1) pl->pieces = pieces = 1;  // (no second level to overlap with)
     if (!level2_only) {
-        const char *ce = getenv("MC_SK_COMPACT");  // (read on every run: the tests switch it)
-        const bool compact_on = !(ce && !strcmp(ce, "0"));
-        static const bool staged = [] { const char *e = getenv("MC_SK2_STAGED"); return !(e && !strcmp(e, "0")); }();
         const uint64_t chunk = (compact_tiles + nseg1 - 1) / std::max<uint32_t>(nseg1, 1);
         // (not where pipe_resize_by_sample may replace the table between the two levels: the leaf numbers inside the records
         // are those of the table the first level saw)
-        pl->compact = compact_tiles && compact_on && staged && pl->sk && pl->b2 > 1 && pl->b2 <= (1u << (32 - SKC_REL_BITS)) && g == 0 && pieces == 1 &&
+        pl->compact = compact_tiles && c->sw.sk_compact && pl->sk && pl->b2 > 1 && pl->b2 <= (1u << (32 - SKC_REL_BITS)) && g == 0 &&
                       chunk * P1W_TILE <= (1ull << SKC_REL_BITS) && !(pl->guessed && c->virgin);
         // ... unless the table can be given a power of two of regions once the batch's size is known: 512 buckets of 2 .. 1024 leaves
-        const char *ve = getenv("MC_SK_VLEAF");  // (read on every run: the tests switch it)
-        const bool vleaf_on = !(ve && !strcmp(ve, "0"));
         pl->vleaf = false;
-        if (!pl->compact && !lng && vleaf_on && !c->no_vleaf && compact_tiles && compact_on && staged && pl->sk && g == 0 && pieces == 1 && chunk * P1W_TILE <= (1ull << SKC_REL_BITS) &&
+        if (!pl->compact && !lng && c->sw.sk_vleaf && !c->no_vleaf && compact_tiles && c->sw.sk_compact && pl->sk && g == 0 && chunk * P1W_TILE <= (1ull << SKC_REL_BITS) &&
             pl->guessed && c->virgin && c->mm_k > 0 && np1 == PT_MAX_BUCKETS && c->n_regions <= (uint64_t)PT_MAX_BUCKETS * 1024) {
             uint64_t r2 = 2 * PT_MAX_BUCKETS;
             while (r2 < c->n_regions) r2 *= 2;
@@ -1771,7 +1766,7 @@ static int pipe_prepare(mc_ctx *c, uint64_t wb, PipePlan *pl, uint64_t n_records
         }
         // (long records keep the leaf in their second word: 32 bits of position)
         // (... and the bin word, so the table may still be replaced between the levels: a virgin table without a hint qualifies)
-        if (lng) pl->compact = compact_tiles && pl->sk && pl->b2 > 1 && pl->b2 <= 1024 && g == 0 && pieces == 1 && chunk * P1L_TILE < (1ull << 32) &&
+        if (lng) pl->compact = compact_tiles && pl->sk && pl->b2 > 1 && pl->b2 <= 1024 && g == 0 && chunk * P1L_TILE < (1ull << 32) &&
                                !(pl->guessed && !c->virgin);
         pl->chunk_tiles = pl->compact ? (uint32_t)chunk : 0;
         if (listed) pl->compact = true;  // (the listed second level leaves the pointer in the record's first word too: no pointer arrays behind it)
@@ -1782,11 +1777,9 @@ static int pipe_prepare(mc_ctx *c, uint64_t wb, PipePlan *pl, uint64_t n_records
     pl->cap1 = (uint64_t)((double)units / (double)pl->np1 / (double)nseg1 * (tight ? 1.12 : 1.25)) + (pl->sk ? 64 : 256);  // per segment
     const double mean_leaf = (double)units / (double)pl->n_leaves;
     // (records of one locus come in clumps -- one per read covering it -- so leaves vary more than Poisson)
-    double sig2 = pl->sk ? (tight ? 12.0 : 32.0) : 8.0;
-    if (const char *e = getenv("MC_CAP2_SIGMAS")) { const double v = atof(e); if (v >= 1.0 && v <= 64.0) sig2 = v; }  // (tuning runs: how far apart the leaves' streams lie)
+    const double sig2 = pl->sk ? (tight ? 12.0 : 32.0) : 8.0;
     pl->cap2 = (uint64_t)(mean_leaf * 1.15 + sig2 * std::sqrt(mean_leaf) + 64.0);  // (a spilled record also costs the solid list, P3Emit)
-    if (const char *e = getenv("MC_CAP2")) { const long v = atol(e); if (v >= 64) pl->cap2 = (uint64_t)v; }  // (tuning runs)
-    pl->spill_cap = pl->sk ? std::max<uint64_t>(units * pieces / 16, 1u << 16) : std::max<uint64_t>(wb / 64, 1u << 20);
+    pl->spill_cap = pl->sk ? std::max<uint64_t>(units / 16, 1u << 16) : std::max<uint64_t>(wb / 64, 1u << 20);
     if ((!listed && pl->np1 * nseg1 * pl->cap1 >= 0xFFFFFFFFull) || (uint64_t)pl->b2 * pl->cap2 * pieces >= 0xFFFFFFFFull)
         return fail(c, MC_EINVAL, "internal: partitioned batch too large for 32-bit bucket indices");
     // (np1, n_leaves as computed above)
@@ -1794,10 +1787,10 @@ static int pipe_prepare(mc_ctx *c, uint64_t wb, PipePlan *pl, uint64_t n_records
     uint64_t dummy;
 #define ENSURE(ptr, capvar, need) do { rc = ensure_buf(c, &(ptr), &(capvar), (need)); if (rc) return rc; } while (0)
     if (pl->sk) {
-        if (!level2_only && !listed) ENSURE(P.a_recs, P.a_recs_cap, np1 * nseg1 * pl->cap1 * pieces * rw);
+        if (!level2_only && !listed) ENSURE(P.a_recs, P.a_recs_cap, np1 * nseg1 * pl->cap1 * rw);
         if (listed && c->want_list) ENSURE(P.a_recs, P.a_recs_cap, units + units / 4);  // (the solid list's room, as a first level would have left it)
         // (long records into a table nothing vouches for: the second level's buffer first serves as the sample's scratch set, 64 MB)
-        if (pl->b2 > 1) ENSURE(P.b_recs, P.b_recs_cap, std::max<uint64_t>(n_leaves * pl->cap2 * pieces * rw, lng && pl->guessed ? (1ull << 22) : 0));
+        if (pl->b2 > 1) ENSURE(P.b_recs, P.b_recs_cap, std::max<uint64_t>(n_leaves * pl->cap2 * rw, lng && pl->guessed ? (1ull << 22) : 0));
         if (!level2_only) ENSURE(P.spill_recs, P.spill_recs_cap, pl->spill_cap * rw);
     } else {
         { uint64_t cap = P.a_cap; ENSURE(P.a_keys, cap, np1 * nseg1 * pl->cap1); P.a_cap = cap; }
@@ -1876,9 +1869,7 @@ static int pipe_drain_handed_on(mc_ctx *c, uint64_t n_listed, bool lng = false)
 static int pipe_resize_by_sample(mc_ctx *c, PipePlan &pl, uint64_t n_records)
 {
     mc_ctx::Pipe &P = c->pipe;
-    if (!(pl.sk && pl.guessed && c->virgin && pl.b2 > 1 && pl.pieces == 1 && c->mm_k)) return MC_OK;
-    static const bool off = getenv("MC_NO_SAMPLE_RESIZE") != nullptr;
-    if (off) return MC_OK;
+    if (!(pl.sk && pl.guessed && c->virgin && pl.b2 > 1 && c->mm_k)) return MC_OK;
     constexpr uint64_t SET_SLOTS = 1ull << 23;  // 64 MB of P.b_recs, which the second level has not touched yet
     if (P.b_recs_cap * sizeof(uint4) < SET_SLOTS * 8) return MC_OK;
     uint64_t *set = reinterpret_cast<uint64_t *>(P.b_recs);
@@ -1909,14 +1900,13 @@ static int pipe_resize_by_sample(mc_ctx *c, PipePlan &pl, uint64_t n_records)
         while (p2 * 2 <= want) p2 *= 2;
         if (est > 0.45 * (double)(p2 << c->sb)) p2 *= 2;
         uint64_t reach = (uint64_t)PT_MAX_BUCKETS * 1024;
-        if (const char *e = getenv("MC_SK_VLEAF_MAX_REGIONS")) if (*e) reach = std::min<uint64_t>(reach, strtoull(e, nullptr, 10));  // (tests: the way back at a small size)
+        reach = std::min<uint64_t>(reach, c->sw.sk_vleaf_max_regions);  // (tests: the way back at a small size)
         if (p2 > reach) return 5;
         want = p2;
     }
     if (pl.lng && est > 0.40 * (double)(want << c->sb)) return 4;  // (hash keys need their bins roomy, mc_create: the caller takes the per-window form)
     if (pl.lng && want <= c->n_regions) { pl.guessed = false; return MC_OK; }  // (the table it was created with holds the batch)
-    static const bool dbg = getenv("MC_INGEST_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "[count] first bucket: %llu distinct k-mers, %.0f M expected in all; table of %llu regions, %llu wanted\n",
+    if (c->sw.ingest_debug) fprintf(stderr, "[count] first bucket: %llu distinct k-mers, %.0f M expected in all; table of %llu regions, %llu wanted\n",
                      (unsigned long long)c->h_scratch[24], est / 1e6, (unsigned long long)c->n_regions, (unsigned long long)want);
     if (want != c->n_regions) {
         // the new table must split into the level-1 buckets the records are in
@@ -1944,7 +1934,7 @@ static int pipe_resize_by_sample(mc_ctx *c, PipePlan &pl, uint64_t n_records)
 // overflowed even their spill list: the caller then counts the batch with the direct kernel.
 static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false, double ms2_exposed = 0, bool p1_pending = false,
                        bool may_rerun = false)
-{   // p2_done: the caller ran P2 itself, piece by piece next to P1 (ms2_exposed = what of it outlasted P1)
+{   // p2_done: the caller ran P2 itself, piece by piece behind P1 (ms2_exposed = its time)
     // p1_pending: the caller recorded ev_t[0], enqueued P1 and did not wait: P2 and P3 follow on the stream at once and
     // the host hears of all three together (a host round trip between two kernels leaves the device idle for tens of us)
     mc_ctx::Pipe &P = c->pipe;
@@ -1963,8 +1953,7 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
     // threshold to track.  Each P3 workgroup owns a segment.
     const int p3_grid = (int)std::min<uint64_t>(n_leaves, 256 * 2 * 4 * (D2_THREADS < P3_THREADS ? P3_THREADS / D2_THREADS : 1));
     P3Emit emit{nullptr, nullptr, 0, P.flags + 2};
-    static const bool no_list = getenv("MC_NO_SOLID_LIST") != nullptr;
-    if (pl.sk && pl.b2 > 1 && c->mm_k && c->solid_tracked && c->cov_hint > 0 && !no_list && c->want_list) {
+    if (pl.sk && pl.b2 > 1 && c->mm_k && c->solid_tracked && c->cov_hint > 0 && c->want_list) {
         if (!P.emit_counts) HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&P.emit_counts), 256 * 2 * 4 * (D2_THREADS < P3_THREADS ? P3_THREADS / D2_THREADS : 1) * sizeof(uint32_t)));
         HIPCHK(c, hipMemsetAsync(P.emit_counts, 0, 256 * 2 * 4 * (D2_THREADS < P3_THREADS ? P3_THREADS / D2_THREADS : 1) * sizeof(uint32_t), c->stream));
         emit.recs = P.a_recs;
@@ -1973,7 +1962,6 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
     }
     // super-k-mer records, one region and one segment per leaf: the merge kernel that merges identical records first
     // (count_pipeline.h k_p3_dedup; MC_P3_DEDUP=0: the general kernel)
-    static const bool dedup_on = [] { const char *e = getenv("MC_P3_DEDUP"); return !(e && !strcmp(e, "0")); }();
     auto launch_p3_n = [&](uint32_t leaves, int grid, int virgin) {
 #define P3_ARGS lk, lh, lc, lcap, lseg, leaves, pl.g, c->view(), virgin, P.leaf_state, P.leaf_new, P.flags + 1, \
                 (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, emit, c->ptr_tries, P.flags
@@ -1989,7 +1977,7 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
             else if (k == 41) hipLaunchKernelGGL(k_p3_long<41>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
             else hipLaunchKernelGGL(k_p3_long<0>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
 #undef P3L_ARGS
-        } else if (pl.sk && pl.g == 0 && lseg == 1 && dedup_on) {
+        } else if (pl.sk && pl.g == 0 && lseg == 1 && c->sw.p3_dedup) {
             const bool one_gpu = c->ptr_tries == 1 && (emit.recs == nullptr || !(c->solid_tracked && c->cov_hint > 0));
             if (virgin && one_gpu && k == 31) hipLaunchKernelGGL((k_p3_dedup<true, true, true>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
             else if (virgin && one_gpu) hipLaunchKernelGGL((k_p3_dedup<true, true>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
@@ -2018,9 +2006,8 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
     unsigned long long n_spill = 0, n_handed_on = 0;
     const bool virgin0 = c->virgin;
     auto launch_p2 = [&] {
-        static const bool staged = [] { const char *e = getenv("MC_SK2_STAGED"); return !(e && !strcmp(e, "0")); }();
-        static bool told = getenv("MC_INGEST_DEBUG") == nullptr;
-        if (!told) {  // (where the streams lie: the second level's time differs between processes that differ in nothing else)
+        static bool told = false;  // (once a process)
+        if (c->sw.ingest_debug && !told) {  // (where the streams lie: the second level's time differs between processes that differ in nothing else)
             told = true;
             fprintf(stderr, "[count] level-1 stream %p (%llu records a segment), level-2 stream %p (%llu a leaf), table %p\n", (void *)P.a_recs,
                     (unsigned long long)pl.cap1, (void *)P.b_recs, (unsigned long long)pl.cap2, (void *)c->slots);
@@ -2036,11 +2023,8 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
         else if (pl.listed)
             hipLaunchKernelGGL((k_sk2_scatter_staged<MC_SK2_ITEMS, true, false>), dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, pl.in_recs, pl.in_ptrs, (uint64_t)0,
                                P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_recs, nullptr, pl.sks, pl.nseg1, P.skb_seg_start, nullptr);
-        else if (pl.sk && staged && pl.pieces == 1)
-            hipLaunchKernelGGL(k_sk2_scatter_staged<MC_SK2_ITEMS>, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, P.a_hints, pl.cap1,
-                               P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_recs, P.b_hints, pl.sks, pl.nseg1);
         else if (pl.sk)
-            hipLaunchKernelGGL(k_sk2_scatter, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, P.a_hints, pl.cap1,
+            hipLaunchKernelGGL(k_sk2_scatter_staged<MC_SK2_ITEMS>, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, P.a_hints, pl.cap1,
                                P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_recs, P.b_hints, pl.sks, pl.nseg1);
         else
             hipLaunchKernelGGL(k_p2_scatter, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_keys, P.a_hints, pl.cap1,
@@ -2067,8 +2051,7 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
         if (merged == sample_leaves && est <= (c->mm_k ? 0.5 : 0.7) * (double)c->n_slots()) return MC_OK;  // it fits: carry on
         uint64_t want = regions_for(c, c->mm_k ? mm_slots_for(c, est, load) : (uint64_t)(est / load));
         if (want <= c->n_regions) want = regions_for(c, c->n_slots() * 2);
-        static const bool dbg = getenv("MC_INGEST_DEBUG") != nullptr;
-        if (dbg) fprintf(stderr, "[count] table too small: %llu of %llu sampled leaves merged, %llu keys in them: %.0f M keys expected; new table %.1f GB\n",
+        if (c->sw.ingest_debug) fprintf(stderr, "[count] table too small: %llu of %llu sampled leaves merged, %llu keys in them: %.0f M keys expected; new table %.1f GB\n",
                          (unsigned long long)merged, (unsigned long long)sample_leaves, (unsigned long long)added, est / 1e6, (double)(want << c->sb) * 16 / 1e9);
         table_release(c, c->slots, c->slots_bytes);
         c->slots = nullptr;
@@ -2391,7 +2374,7 @@ static int add_reads_long(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_
     HIPCHK(c, hipEventRecord(c->ev_t[0], c->stream));  // (no wait here: pipe_finish enqueues the second level and the merge right behind)
     launch_tile_first(c, offs, nr, n_tiles_abs, P.tile_first, P1L_TILE);
     pl.pos0 = base0 / P1L_TILE * P1L_TILE;
-    if (getenv("MC_INGEST_DEBUG"))
+    if (c->sw.ingest_debug)
         fprintf(stderr, "[count] long records: %u buckets x %u leaves, %u tiles a segment from base %llu, %llu records expected\n", pl.b1, pl.b2, pl.chunk_tiles,
                 (unsigned long long)pl.pos0, (unsigned long long)n_records);
     const SklSpill sp{P.spill_recs, P.spill_count, pl.spill_cap, P.flags};
@@ -2422,22 +2405,16 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
         if (end_abs - base0 > max_run_bases(c, (double)wb / (double)std::max<uint64_t>(end_abs - base0, 1))) return RC_RESPLIT;
     }
     const uint64_t n_records = c->mm_k ? sk_records_bound(c, wb, nr) : 0;
-    // MC_PIPE_PIECES=n (an experiment, off by default): the reads go through the two scatter levels in n pieces, the
-    // second level of piece p on a side stream next to the first level of piece p + 1; the merge kernel then finds n
-    // segments per leaf.  Measured on configs[1] (P1 + exposed P2 + P3): 1 piece 6.1 + 2.7 + 9.3 = 18.2 ms, 2 pieces
-    // 7.0 + 1.4 + 9.5 = 17.9, 4 pieces 7.6 + 0.7 + 10.9 = 19.2 -- the two levels slow each other down by nearly what
-    // the overlap hides, and the merge pays for the shorter segments.
-    uint32_t pieces = 1;
-    if (const char *e = getenv("MC_PIPE_PIECES")) pieces = (uint32_t)std::min<unsigned long>(8, std::max<unsigned long>(1, strtoul(e, nullptr, 10)));
     // One key per window (hash keys, short k): a large batch goes through the two scatter levels in pieces of ~2^30 windows
     // that REUSE the level-1 buffers, one after the other on the same stream, so that a run of twice the windows fits
     // the same scratch and the whole table is rewritten half as often (max_run_bases).
     // (only where the memory is needed: at 0.9 G windows two pieces cost 55 ms against 35 ms in one)
-    if (!n_records) pieces = wb < (3ull << 29) ? 1u : (uint32_t)std::min<uint64_t>(8, (wb + (1ull << 30) - 1) >> 30);
-    int rc = pipe_prepare(c, wb, &pl, n_records, n_records ? (uint32_t)P1W_SEGMENTS : (uint32_t)PT_SEGMENTS, pieces, false,
-                          n_records != 0 && pieces == 1 ? (end_abs + P1W_TILE - 1) / P1W_TILE - base0 / P1W_TILE : 0);
+    // (super-k-mer records go in one piece)
+    int rc = pipe_prepare(c, wb, &pl, n_records, n_records ? (uint32_t)P1W_SEGMENTS : (uint32_t)PT_SEGMENTS,
+                          n_records || wb < (3ull << 29) ? 1u : (uint32_t)std::min<uint64_t>(8, (wb + (1ull << 30) - 1) >> 30), false,
+                          n_records ? (end_abs + P1W_TILE - 1) / P1W_TILE - base0 / P1W_TILE : 0);
     if (rc) return rc;
-    pieces = pl.pieces;
+    const uint32_t pieces = pl.pieces;
     const uint64_t *offs = d_off + r0;
     // tiles are cut over the absolute base positions [0, end_abs); the ones before base0 hold no read of ours
     const uint32_t tile_size = pl.sk ? P1W_TILE : (uint32_t)PT_TILE;
@@ -2445,7 +2422,7 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
     rc = ensure_buf(c, &P.tile_first, &P.tiles1_cap, n_tiles_abs);
     if (rc) return rc;
     double ms1 = 0;
-    if (pieces > 1 && !pl.sk) {
+    if (pieces > 1) {
         const uint64_t t_first = base0 / tile_size, per = (n_tiles_abs - t_first + pieces - 1) / pieces;
         // (the two levels alternate on one stream; an event behind every kernel books each level's time where it belongs --
         // round 3 booked both under the first level and reported k_p2_scatter: 0.0 for configs[2] at full size)
@@ -2475,41 +2452,12 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
             ms2 += f2;
         }
         rc = pipe_finish(c, pl, ms1, true, ms2, false, true);
-    } else if (pieces > 1) {
-        const uint64_t t_first = base0 / tile_size, per = (n_tiles_abs - t_first + pieces - 1) / pieces;
-        const uint64_t a_stride = pl.np1 * pl.nseg1 * pl.cap1, c_stride = pl.np1 * pl.nseg1;
-        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-        launch_tile_first(c, offs, nr, n_tiles_abs, P.tile_first, tile_size);
-        for (uint32_t pc = 0; pc < pieces; pc++) {
-            const uint64_t lo_t = t_first + pc * per, hi_t = std::min<uint64_t>(n_tiles_abs, lo_t + per);
-            if (lo_t < hi_t)
-                hipLaunchKernelGGL(k_sk1w_extract<false>, dim3(P1W_SEGMENTS), dim3(P1W_THREADS), 0, c->stream, d_words, offs, nr,
-                                   pc == 0 ? base0 : lo_t * tile_size, end_abs, hi_t, P.tile_first, c->cfg.k, pl.b1, P.seg_counts1 + pc * c_stride,
-                                   pl.cap1, P.a_recs + pc * a_stride, P.a_hints + pc * a_stride, pl.sks, c->cur_ptr_base);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(c->ev_piece[pc], c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->pipe_stream, c->ev_piece[pc], 0));
-            hipLaunchKernelGGL(k_sk2_scatter, dim3((unsigned)pl.np1), dim3(PT_THREADS), 0, c->pipe_stream, P.a_recs + pc * a_stride,
-                               P.a_hints + pc * a_stride, pl.cap1, P.seg_counts1 + pc * c_stride, (uint32_t)pl.np1, pl.b1, pl.b2, P.cursors2,
-                               pl.cap2, P.b_recs, P.b_hints, pl.sks, pl.nseg1, 0, pc, pieces);
-            HIPCHK(c, hipGetLastError());
-        }
-        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_p2, c->pipe_stream));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_p2, 0));
-        HIPCHK(c, hipEventSynchronize(c->ev_p2));
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        float f1 = 0, f2 = 0;
-        HIPCHK(c, hipEventElapsedTime(&f1, c->ev0, c->ev1));
-        HIPCHK(c, hipEventElapsedTime(&f2, c->ev1, c->ev_p2));  // what the last piece's second level adds behind the first levels
-        ms1 = f1;
-        rc = pipe_finish(c, pl, ms1, true, f2 > 0 ? f2 : 0, false, true);
     } else {
         HIPCHK(c, hipEventRecord(c->ev_t[0], c->stream));  // (no wait here: pipe_finish enqueues P2 and P3 right behind)
         launch_tile_first(c, offs, nr, n_tiles_abs, P.tile_first, tile_size);
         if (pl.sk && pl.compact) {
             pl.pos0 = base0 / P1W_TILE * P1W_TILE;
-            if (getenv("MC_INGEST_DEBUG"))
+            if (c->sw.ingest_debug)
                 fprintf(stderr, "[count] compact records: %u buckets x %u leaves%s, %u tiles a segment from base %llu\n", pl.b1, pl.vleaf ? 1024u : pl.b2,
                         pl.vleaf ? " (whatever the table: it is sized behind the first level)" : "", pl.chunk_tiles, (unsigned long long)pl.pos0);
             hipLaunchKernelGGL((k_sk1w_extract<false, true>), dim3(P1W_SEGMENTS), dim3(P1W_THREADS), 0, c->stream, d_words, offs, nr, base0, end_abs,
@@ -2526,7 +2474,7 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
         rc = pipe_resize_by_sample(c, pl, n_records);
         if (rc == 5 && !c->no_vleaf) {  // (the batch wants a table beyond the reach of the records' leaf bits: once more, the two-array way)
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (getenv("MC_INGEST_DEBUG")) fprintf(stderr, "[count] the batch wants a table beyond the reach of its records' ten leaf bits: the first level again, two arrays\n");
+            if (c->sw.ingest_debug) fprintf(stderr, "[count] the batch wants a table beyond the reach of its records' ten leaf bits: the first level again, two arrays\n");
             c->no_vleaf = true;
             rc = add_reads_partitioned(c, d_words, d_off, r0, r1, base0, end_abs, wb);
             c->no_vleaf = false;
@@ -2744,11 +2692,10 @@ static int rs_append(mc_ctx *c, const uint64_t *d_words, uint64_t first_off, uin
 // Every run reads and rewrites the whole table, so fewer, larger runs are what a large read set wants.
 static uint64_t max_run_bases(const mc_ctx *c, double windows_per_base)
 {   // windows_per_base: of the read set at hand (88 / 150 for 150-base reads at k = 63): the scratch is per window
-    static const uint64_t env = [] { const char *e = getenv("MC_MAX_RUN_BASES"); return e && *e ? strtoull(e, nullptr, 10) : 0ull; }();
-    if (env) return std::max<uint64_t>(env, 1u << 20);
+    if (c->sw.max_run_bases) return std::max<uint64_t>(c->sw.max_run_bases, 1u << 20);
     if (c->mm_k) return 1ull << 34;
     // (tests: the per-window form's limit alone, so that a run cut for long records is too large for it)
-    if (const char *e = getenv("MC_MAX_RUN_BASES_PER_WINDOW")) if (*e) return std::max<uint64_t>(strtoull(e, nullptr, 10), 1u << 20);
+    if (c->sw.max_run_bases_per_window) return c->sw.max_run_bases_per_window;
     // a key and a read pointer per window, in pieces (add_reads_partitioned): ~16.5 bytes of scratch per window.  Two
     // thirds of what the device has free may go there (the table is allocated already), between 2^31 and 2^33 bases: every
     // run reads and rewrites the whole table, so few, large runs (configs[2]: 2 instead of 4).
@@ -2773,7 +2720,7 @@ static int add_reads_impl(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_
         return w;
     };
     const uint64_t total = windows_of(0, n_reads);
-    const bool partition = c->count_path == 2 || (c->count_path == 0 && total >= (1ull << 22));
+    const bool partition = c->sw.count_path == 2 || (c->sw.count_path == 0 && total >= (1ull << 22));
     if (partition) {
         uint64_t max_bases = max_run_bases(c, 1.0);
         uint64_t r = 0;
@@ -2864,7 +2811,6 @@ int mc_create(const mc_config *cfg, mc_ctx **out)
     CREATE_CHK(hipEventCreate(&c->ev1));
     CREATE_CHK(hipStreamCreateWithFlags(&c->pipe_stream, hipStreamNonBlocking));
     for (auto &e : c->ev_piece) CREATE_CHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreate(&c->ev_p2));
     for (auto &e : c->ev_t) CREATE_CHK(hipEventCreate(&e));
     CREATE_CHK(hipMalloc(reinterpret_cast<void **>(&c->d_ctr), 16 * sizeof(unsigned long long)));
     CREATE_CHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_scratch), 32 * sizeof(unsigned long long), hipHostMallocDefault));
@@ -2874,19 +2820,17 @@ int mc_create(const mc_config *cfg, mc_ctx **out)
     CREATE_CHK(hipMemsetAsync(c->d_ctr, 0, 16 * sizeof(unsigned long long), c->stream));
 
 #undef CREATE_CHK
-    if (const char *e = getenv("MC_COUNT_PATH")) c->count_path = !strcmp(e, "direct") ? 1 : !strcmp(e, "partition") ? 2 : 0;
-    if (const char *e = getenv("MC_BFS_DIRECT")) c->bfs_direct = strcmp(e, "0") != 0;
-    c->want_list = (cfg->flags & MC_FLAG_SOLID_LIST) != 0 || !c->bfs_direct;
+    c->sw = read_switches();
+    c->want_list = (cfg->flags & MC_FLAG_SOLID_LIST) != 0 || !c->sw.bfs_direct;
     // packed keys of at least SK_MIN_K bases: table regions = minimizer bins, reads counted as super-k-mers
     // (MC_SUPERKMERS=0 keeps the per-window pipeline: for A/B measurements)
     if (cfg->key_mode == MC_KEY_PACKED && cfg->k >= SK_MIN_K) c->mm_k = cfg->k;
-    if (const char *e = getenv("MC_SUPERKMERS")) if (!strcmp(e, "0")) c->mm_k = 0;
+    if (!c->sw.superkmers) c->mm_k = 0;
     c->sk_form = c->mm_k != 0;
     // polynomial keys of 33 .. 63 bases in a table sized by a capacity hint: minimizer bins too, reads counted as long records
     // (count_long.h; hash_bins() above says what such a table cannot do and what happens then).  MC_LONG_RECORDS=0: the per-window pipeline.
     if (cfg->key_mode == MC_KEY_POLY && cfg->k >= SKL_MIN_K && cfg->k <= SKL_MAX_K) {
-        const char *e = getenv("MC_LONG_RECORDS");
-        if (!(e && !strcmp(e, "0"))) c->mm_k = cfg->k;
+        if (c->sw.long_records) c->mm_k = cfg->k;
     }
     uint64_t want_slots = 1ull << 22;  // 4 M slots = 64 MB to start with
     if (cfg->capacity_hint) {
@@ -2899,7 +2843,6 @@ int mc_create(const mc_config *cfg, mc_ctx **out)
         // regions and the merge kernel sweeps each leaf twice.
         double load = 0.7;
         if (c->mm_k) load = std::min(0.36, std::max(0.25, 0.25 + 0.05 * std::log2((double)cfg->capacity_hint / (double)(64u << 20))));
-        if (const char *e = getenv("MC_TABLE_LOAD")) { const double v = atof(e); if (v > 0.05 && v < 0.95) load = v; }  // (tuning runs)
         want_slots = std::max<uint64_t>(want_slots, (uint64_t)((double)cfg->capacity_hint / load));
         if (c->mm_k) want_slots = std::max<uint64_t>(1ull << 22, mm_slots_for(c, (double)cfg->capacity_hint, load));
         // Long records need their bins roomy: at k = 63 a region holds the k-mers of four or five loci (each with the error variants
@@ -2909,13 +2852,11 @@ int mc_create(const mc_config *cfg, mc_ctx **out)
         // skl_word2: mm_k < 0 -- half again as many, smaller loci a region: even enough up to load ~0.55, scripts/bin_model.py);
         // beyond that, and with MC_LONG_BINS=1 (tuning runs; 2: two smallest for every table), the per-window pipeline.
         const bool crowded = hash_bins(c) && (double)cfg->capacity_hint > 0.40 * (double)want_slots;
-        const char *be = getenv("MC_LONG_BINS");
-        const bool two = hash_bins(c) && (be ? !strcmp(be, "2") : crowded);
+        const bool two = hash_bins(c) && (c->sw.long_bins ? c->sw.long_bins == 2 : crowded);
         if (two && (double)cfg->capacity_hint <= 0.56 * (double)want_slots) c->mm_k = -cfg->k;
         else if (crowded) {
             c->mm_k = 0;
             want_slots = std::max<uint64_t>(1ull << 22, (uint64_t)((double)cfg->capacity_hint / 0.7));
-            if (const char *e = getenv("MC_TABLE_LOAD")) { const double v = atof(e); if (v > 0.05 && v < 0.95) want_slots = std::max<uint64_t>(1ull << 22, (uint64_t)((double)cfg->capacity_hint / v)); }
         }
     }
     int rc = table_alloc(c, regions_for(c, want_slots));
@@ -2969,7 +2910,6 @@ void mc_destroy(mc_ctx *c)
     g_scratch_pool.put(c->cfg.device, c->rs_words, c->rs_cap_words * 8);
     for (auto &e : c->ev_piece) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_seq) if (e) (void)hipEventDestroy(e);
-    if (c->ev_p2) (void)hipEventDestroy(c->ev_p2);
     for (auto &e : c->ev_t) if (e) (void)hipEventDestroy(e);
     if (c->pipe_stream) { (void)hipStreamSynchronize(c->pipe_stream); (void)hipStreamDestroy(c->pipe_stream); }
     c->tok_pool.release();
@@ -3109,8 +3049,7 @@ static int add_reads_dev_locked(mc_ctx *c, const uint64_t *d_words, const uint64
 static bool h2d_pinned(mc_ctx *c, void *dst, const void *src, size_t bytes, int fd, uint64_t file_off)
 {
     constexpr size_t CHUNK = 8u << 20;
-    static constexpr int TMAX = 8;
-    static const int T = [] { const char *e = getenv("MC_H2D_THREADS"); const int v = e && *e ? atoi(e) : 8; return std::min(std::max(v, 1), TMAX); }();
+    constexpr int T = 8;  // staging threads, two pinned buffers each (mc_ctx::pin, pin_stream)
     std::lock_guard<std::mutex> g(c->pin_mu);
     if (hipSetDevice(c->cfg.device) != hipSuccess) return false;
     if (!c->pin[0]) {
@@ -3120,7 +3059,7 @@ static bool h2d_pinned(mc_ctx *c, void *dst, const void *src, size_t bytes, int 
             if (hipStreamCreateWithFlags(&c->pin_stream[i], hipStreamNonBlocking) != hipSuccess) return false;
     }
     const size_t n_chunks = (bytes + CHUNK - 1) / CHUNK;
-    bool failed[TMAX] = {};
+    bool failed[T] = {};
     const int device = c->cfg.device;
     std::vector<std::thread> th;
     for (int t = 0; t < T && (size_t)t < n_chunks; t++)
@@ -3154,7 +3093,7 @@ static bool h2d_pinned(mc_ctx *c, void *dst, const void *src, size_t bytes, int 
             (void)hipEventDestroy(ev[1]);
         });
     for (auto &x : th) x.join();
-    for (int t = 0; t < TMAX; t++)
+    for (int t = 0; t < T; t++)
         if (failed[t]) return false;
     return true;
 }
@@ -3246,7 +3185,7 @@ static int add_reads_dev_counted(mc_ctx *c, const uint64_t *d_words, const uint6
         if (rc) return rc;
         c->ptr_tries = 1;
     }
-    const bool partition = c->count_path == 2 || (c->count_path == 0 && total >= (1ull << 22));
+    const bool partition = c->sw.count_path == 2 || (c->sw.count_path == 0 && total >= (1ull << 22));
     const double wpb = last_off > first_off ? (double)total / (double)(last_off - first_off) : 1.0;  // windows per base
     if (partition && last_off - first_off < max_run_bases(c, wpb)) {  // one batch: no need for the offsets on the host
         int rc = total ? add_reads_partitioned_any(c, d_words, d_off, 0, n_reads, first_off, last_off, total) : MC_OK;
@@ -3325,7 +3264,7 @@ int mc_add_keys_dev(mc_ctx *c, const int64_t *d_keys, const uint32_t *d_hints, u
     std::lock_guard<std::mutex> g(c->mu);
     if (!d_keys && n) return fail(c, MC_EINVAL, "mc_add_keys_dev: null pointer");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    const bool partition = c->count_path == 2 || (c->count_path == 0 && n >= (1ull << 22));
+    const bool partition = c->sw.count_path == 2 || (c->sw.count_path == 0 && n >= (1ull << 22));
     if (partition) {
         const uint64_t max_batch = (1ull << 31) - (1ull << 24);
         for (uint64_t i = 0; i < n; i += max_batch) {
@@ -3436,7 +3375,7 @@ static int tokenize_chunk_locked(mc_ctx *c, const mch::PlainReadsFile &f, const 
     const uint64_t n = (uint64_t)(e - b);
     if (n == 0) return MC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    const bool dbg = getenv("MC_INGEST_DEBUG") != nullptr;
+    const bool dbg = c->sw.ingest_debug;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t1 = now();
     struct { uint8_t *p; } text{d_text};  // (padded with zero bytes to whole tiles of the newline passes: tok_text_bytes)
@@ -3628,14 +3567,12 @@ int mc_add_reads_file(mc_ctx *c, const char *path, uint64_t *n_reads)
         // Uncompressed FASTA / FASTQ: the bytes go to the device in chunks cut at record starts and are tokenised there
         // (csrc/tokenizer.h); a chunk the device declines goes through the host parser, as does any other kind of file
         // (MC_TOKENIZER=host: every file).  Host batches hold 2^20 reads; the context's lock is taken per batch / chunk.
-        const char *mode = getenv("MC_TOKENIZER");
         mch::PlainReadsFile f;
-        if (!(mode && !strcmp(mode, "host")) && mch::map_plain_reads(path, &f)) {
+        if (!c->sw.tokenizer_host && mch::map_plain_reads(path, &f)) {
             // chunks of 256 MB: the bytes of chunk i + 1 cross the link (a helper thread, pinned staging buffers) while
             // the kernels tokenise and count chunk i
-            const char *e_chunk = getenv("MC_TOKENIZER_CHUNK_BYTES");
-            const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(e_chunk && *e_chunk ? strtoull(e_chunk, nullptr, 10) : (1ull << 28), 64), 3ull << 29);
-            const bool dbg = getenv("MC_INGEST_DEBUG") != nullptr;
+            const uint64_t chunk = c->sw.tokenizer_chunk_bytes;
+            const bool dbg = c->sw.ingest_debug;
             auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
             const double t_begin = now();
             std::vector<std::pair<const char *, const char *>> cuts;
@@ -4023,8 +3960,7 @@ int mc_extract_superkmers_dev(mc_ctx *c, const uint64_t *d_words, const uint64_t
 // coarse buckets an owner's records are dealt to by the first level (*sub)
 static uint32_t skb_fine_buckets(const mc_ctx *c, uint32_t n_owners, uint32_t *sub)
 {
-    static const bool off = [] { const char *e = getenv("MC_EXCHANGE_BINNED"); return e && !strcmp(e, "0"); }();
-    if (off || !c->sk_form || !c->mm_k || n_owners == 0 || n_owners > PT_MAX_BUCKETS) return 0;
+    if (!c->sw.exchange_binned || !c->sk_form || !c->mm_k || n_owners == 0 || n_owners > PT_MAX_BUCKETS) return 0;
     uint64_t n_leaves, np1;
     uint32_t g;
     if (plan_levels(c, true, &n_leaves, &g, &np1)) return 0;
@@ -4552,8 +4488,7 @@ int solid_build(mc_ctx *c, uint64_t n, int min_cov, double *ms, const PairSource
 {
     c->n_solid = n;
     c->st.solid_kmers = n;
-    uint64_t factor = 4;  // slots per solid key (load factor <= 1/4)
-    if (const char *e = getenv("MC_SOLID_FACTOR")) factor = std::max<uint64_t>(2, strtoull(e, nullptr, 10));
+    constexpr uint64_t factor = 4;  // slots per solid key (load factor <= 1/4)
     uint32_t lg = c->sb;
     while (lg < 34 && (1ull << lg) < factor * n) lg++;
     if (lg < SOLID_SB + 1) lg = SOLID_SB + 1;
@@ -4639,7 +4574,7 @@ int solid_build(mc_ctx *c, uint64_t n, int min_cov, double *ms, const PairSource
 // Builds (or reuses) the solid table for this threshold.
 int ensure_solid(mc_ctx *c, int min_cov, double *ms)
 {
-    if (c->d_shards || (c->bfs_direct && !c->solid_external)) {  // the walk looks its k-mers up in the counting table(s): nothing to build
+    if (c->d_shards || (c->sw.bfs_direct && !c->solid_external)) {  // the walk looks its k-mers up in the counting table(s): nothing to build
         c->solid_is_table = true;
         c->solid_cov = min_cov;
         return MC_OK;
@@ -5073,8 +5008,7 @@ int mc_bfs_batch(mc_ctx *c, const mc_bfs_job *jobs, uint32_t n_jobs, int min_cov
         HIPCHK(c, hipMemcpyAsync(c->d_bfs_stage, c->h_bfs_stage, launch == 0 ? stage_bytes : (uint64_t)n_jobs * sizeof(BfsState), hipMemcpyHostToDevice, c->stream));
         // Few jobs: each gets a second workgroup that scouts ahead while the first verifies (bfs_device.h ScoutBox).  The
         // pair must be on the chip together to gain anything (it is correct either way), so not for large batches.
-        static const bool no_comp = getenv("MC_BFS_COMPANION") && !strcmp(getenv("MC_BFS_COMPANION"), "0");
-        const int companions = !no_comp && n_jobs <= 64 && c->solid_view().reads != nullptr ? 1 : 0;
+        const int companions = c->sw.bfs_companion && n_jobs <= 64 && c->solid_view().reads != nullptr ? 1 : 0;
         hipLaunchKernelGGL(k_bfs_reset, dim3(n_jobs <= 8 ? 64 : 8, n_jobs), dim3(256), 0, c->stream, d_states, launch == 0 ? 1 : 0);
         HIPCHK(c, hipGetLastError());
         pack_bytes = 0;
@@ -5155,14 +5089,13 @@ int mc_bfs_batch(mc_ctx *c, const mc_bfs_job *jobs, uint32_t n_jobs, int min_cov
 
     int ret = MC_OK;
     {   // debug: every walk checked on the device (bfs_device.h k_bfs_check); the rounds' trace of a tuning build written out
-        const char *sc = getenv("MC_BFS_SELFCHECK");
-        const char *dump = getenv("MC_BFS_TRACE_DUMP");
+        const std::string &dump = c->sw.bfs_trace_dump;
         std::string report;
-        if (sc && *sc && *sc != '0') {
+        if (c->sw.bfs_selfcheck) {
             int rc = bfs_selfcheck(c, n_jobs, ctl, min_cov, max_kmers, max_radius, &report);
             if (rc) return rc;
         }
-        if (!report.empty() || (dump && *dump)) bfs_trace_dump(c, n_jobs, ctl, report.empty() ? dump : (dump && *dump ? dump : "/dev/stderr"), report);
+        if (!report.empty() || !dump.empty()) bfs_trace_dump(c, n_jobs, ctl, dump.empty() ? "/dev/stderr" : dump.c_str(), report);
         if (!report.empty()) return fail(c, MC_ECHECK, "mc_bfs: self-check failed: %s", report.c_str());
     }
     for (uint32_t j = 0; j < n_jobs; j++) {
@@ -5173,7 +5106,7 @@ int mc_bfs_batch(mc_ctx *c, const mc_bfs_job *jobs, uint32_t n_jobs, int min_cov
         o->rounds = ctl[j].rounds_narrow + ctl[j].chunks_wide + 2 * (ctl[j].scout_hops + box_iters[j]);
         o->device_ms = total_ms;
         {
-            static const bool stats = getenv("MC_BFS_STATS") != nullptr;
+            const bool stats = c->sw.bfs_stats;
             if (stats) fprintf(stderr, "[bfs job %u] slow rounds: after a partly verified round %llu, first level mismatch %llu, nothing predicted %llu; companion runs ended: stuck %llu, no candidates %llu, budget %llu, aborted %llu\n",
                                j, ctl[j].slow_forced, ctl[j].slow_mismatch, ctl[j].slow_starved, box_e[j][0], box_e[j][1], box_e[j][2], box_e[j][3]);
             if (stats)
@@ -5448,6 +5381,7 @@ struct mc_group {
     std::vector<ncclComm_t> comm;
     bool peer_all = true;       // every pair of distinct devices has peer access (else HIP stages those copies through the host)
     bool gather_reads = false;  // every device's reads are brought to the first device's store, and every record carries a pointer into it
+    mc_switches sw;             // the environment switches, read by mc_group_create (switches.h)
 };
 
 namespace {
@@ -5504,6 +5438,7 @@ int mc_group_create(const mc_config *cfg, const int32_t *devices, uint32_t n_dev
     mc_group *g = new (std::nothrow) mc_group;
     if (!g) return fail(nullptr, MC_ENOMEM, "mc_group_create: out of host memory");
     g->cfg = *cfg;
+    g->sw = read_switches();
     for (uint32_t r = 0; r < n_devices; r++) {
         mc_config c = *cfg;
         c.device = devices[r];
@@ -5517,8 +5452,7 @@ int mc_group_create(const mc_config *cfg, const int32_t *devices, uint32_t n_dev
         // reads are tokenised there in the first place) and every device works its pointers out as if its reads sat in that store
         // -- a walk that had only the first device's reads to follow took 20 times as long at 8 devices (include/mcgpu.h
         // mc_set_read_pointers).  MC_EXCHANGE_GATHER_READS=0: the other devices' records carry no pointers.
-        static const bool gather = [] { const char *e = getenv("MC_EXCHANGE_GATHER_READS"); return !(e && !strcmp(e, "0")); }();
-        g->gather_reads = gather && n_devices > 1;
+        g->gather_reads = g->sw.group_gather_reads && n_devices > 1;
         if (n_devices > 1) (void)mc_set_read_pointers(x, g->gather_reads ? ((r == 0 ? 1 : 2) | MC_PTRS_ON_EVERY_RECORD) : (r == 0 ? 1 : 0));
     }
     // peer access between every pair of different devices (already enabled: fine).  A pair without it still works -- HIP
@@ -5540,9 +5474,7 @@ int mc_group_create(const mc_config *cfg, const int32_t *devices, uint32_t n_dev
             }
         }
     {   // transport of the exchange
-        const char *e = getenv("MC_GROUP_TRANSPORT");
-        g->use_rccl = (cfg->flags & MC_FLAG_GROUP_RCCL) != 0 || (e && !strcmp(e, "rccl"));
-        if (e && !strcmp(e, "peer")) g->use_rccl = false;
+        g->use_rccl = ((cfg->flags & MC_FLAG_GROUP_RCCL) != 0 || g->sw.group_transport == 1) && g->sw.group_transport != 2;
         if (g->use_rccl && n_devices > 1) {
             for (uint32_t a = 0; a < n_devices; a++)
                 for (uint32_t b = a + 1; b < n_devices; b++)
@@ -5662,7 +5594,7 @@ int group_exchange_count(mc_group *g, std::vector<GroupRank> &R)
         // overflow), and dealt to the SAME owners: those of the keys' minimizers
         sk_batch = false;
         for (mc_ctx *c : g->ctx) c->err.clear();
-        if (getenv("MC_INGEST_DEBUG")) fprintf(stderr, "[ingest] group: an owner's piece of the record form overflowed; this batch travels as keys, dealt by minimizer\n");
+        if (g->sw.ingest_debug) fprintf(stderr, "[ingest] group: an owner's piece of the record form overflowed; this batch travels as keys, dealt by minimizer\n");
         rc = per_rank(W, [&](size_t r) -> int { return extract(r, false); });
     }
     if (rc) {
@@ -5859,21 +5791,19 @@ int mc_group_add_reads_file(mc_group *g, const char *path, uint64_t *n_reads)
         // Batches of 2^24 reads per device (2.5 G bases of 150-base reads: 0.6 GB of host memory per device): every batch is
         // one exchange and one counting run on every device, and a counting run rewrites the device's whole table -- with
         // 2^20 reads a batch, as before, a billion reads meant 119 rewrites of a 100 GB-class table per device.
-        static const uint64_t per_dev = [] { const char *e = getenv("MC_GROUP_BATCH_READS"); return e && *e ? std::max<uint64_t>(strtoull(e, nullptr, 10), 1024) : 1ull << 24; }();
+        const uint64_t per_dev = g->sw.group_batch_reads;
         int rc = MC_OK;
         // Uncompressed FASTA / FASTQ: tokenised on the FIRST device (csrc/tokenizer.h, chunk i + 1 crossing PCIe while chunk i
         // is tokenised), into its read store -- the one the walk reads --; when W x per_dev reads have gathered, or the file
         // ends, the other devices fetch their shares of the packed reads from it (device to device) and the batch is exchanged
         // and counted.  A chunk the device declines goes through the host reader like any other file.
-        const char *mode = getenv("MC_TOKENIZER");
         mch::PlainReadsFile f;
-        if (!(mode && !strcmp(mode, "host")) && g->ctx[0]->rs_enabled && mch::map_plain_reads(path, &f)) {
+        if (!g->sw.tokenizer_host && g->ctx[0]->rs_enabled && mch::map_plain_reads(path, &f)) {
             std::lock_guard<std::mutex> lk(g->mu);
             g->dirty = true;
             mc_ctx *c0 = g->ctx[0];
             const size_t W = g->ctx.size();
-            const char *e_chunk = getenv("MC_TOKENIZER_CHUNK_BYTES");
-            const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(e_chunk && *e_chunk ? strtoull(e_chunk, nullptr, 10) : (1ull << 28), 64), 3ull << 29);
+            const uint64_t chunk = g->sw.tokenizer_chunk_bytes;
             std::vector<std::pair<const char *, const char *>> cuts;
             for (const char *b = f.p, *end = f.p + f.n; b < end;) {
                 const char *e = (uint64_t)(end - b) <= chunk + chunk / 4 ? end : mch::plain_record_start(f, b + chunk);
@@ -6016,7 +5946,7 @@ int mc_group_add_reads_file(mc_group *g, const char *path, uint64_t *n_reads)
             if (rc == MC_OK) rc = flush();
             drop_pend();
             if (rc != MC_OK) return rc;
-            if (getenv("MC_INGEST_DEBUG"))
+            if (g->sw.ingest_debug)
                 fprintf(stderr, "[ingest] group: %zu chunk(s) tokenised on device %d, %llu reads in %llu exchange(s) over %zu devices\n", cuts.size(), c0->cfg.device,
                         (unsigned long long)total, (unsigned long long)n_flushes, W);
             if (n_reads) *n_reads = total;
@@ -6086,10 +6016,9 @@ int mc_group_bfs_batch(mc_group *g, const mc_bfs_job *jobs, uint32_t n_jobs, int
     // the solid k-mers, no second table -- and what made configs[3] impossible: 5 G gathered solid k-mers do not fit beside
     // rank 0's counting table.  MC_GROUP_WALK=gather keeps round 3's way (and a group without peer
     // access between all its devices has no other).
-    static const bool want_gather = getenv("MC_GROUP_WALK") && !strcmp(getenv("MC_GROUP_WALK"), "gather");
-    if (!want_gather && g->peer_all) {
+    if (!g->sw.group_walk_gather && g->peer_all) {
         mc_ctx *c0 = g->ctx[0];
-        static const bool dbg = getenv("MC_INGEST_DEBUG") != nullptr;
+        const bool dbg = g->sw.ingest_debug;
         const auto t_0 = std::chrono::steady_clock::now();
         if (g->dirty || !c0->d_shards) {
             std::vector<ShardWire> w(W);
