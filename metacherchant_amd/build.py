@@ -6,6 +6,7 @@ travel to the GPU box with the gpurun snapshot).
 import os
 import shutil
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -14,8 +15,9 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmcgpu.so")
 CLI = os.path.join(LIBDIR, "metacherchant")
 
-HIP_SOURCES = ["mcgpu.hip", os.path.join("host", "envfinder.cpp")]  # (the read-file entry point uses the host reader)
-# every header under csrc/ (mcgpu.hip includes them all; a stale library would travel to the GPU box unnoticed)
+# the library's units (csrc/context.h says what each holds), and the host reader the read-file entry point uses
+HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", os.path.join("host", "envfinder.cpp")]
+# every header under csrc/ makes every object stale (a stale library would travel to the GPU box unnoticed)
 HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "envfinder.h"), os.path.join("test", "bfs_old_race.h"),
                                                                       os.path.join(ROOT, "include", "mcgpu.h")]
 
@@ -25,6 +27,15 @@ def _hipcc():
         if cand and os.path.exists(cand):
             return cand
     raise RuntimeError("hipcc not found (need ROCm to build libmcgpu.so)")
+
+
+MAX_JOBS = 16  # compilers at once, whatever the machine's CPU count says
+
+
+def _run(cmd, verbose):
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
 
 
 def _stale(target, sources):
@@ -43,12 +54,41 @@ def build_lib(force=False, verbose=False, variant=None, defines=()):
     out = LIB if not variant else os.path.join(LIBDIR, "libmcgpu_%s.so" % variant)
     if not force and not _stale(out, deps):
         return out
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
-           "-I", os.path.join(ROOT, "include"), "-o", out] + ["-D" + d for d in defines] + srcs + ["-lz", "-ldl"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
+    # one hipcc -c per unit, side by side, into an object directory of this library's own; then one link
+    objdir = os.path.join(LIBDIR, "obj_" + os.path.splitext(os.path.basename(out))[0])
+    os.makedirs(objdir, exist_ok=True)
+    objs = [os.path.join(objdir, os.path.splitext(os.path.basename(s))[0] + ".o") for s in srcs]
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")]
+    cmds = [[_hipcc(), "-c"] + flags + ["-D" + d for d in defines] + ["-o", o, s] for s, o in zip(srcs, objs)]
+    with ThreadPoolExecutor(min(len(cmds), MAX_JOBS)) as ex:
+        list(ex.map(lambda c: _run(c, verbose), cmds))
+    _run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + ["-lz", "-ldl"], verbose)
     return out
+
+
+def code_objects(lib, outdir):
+    """Paths of every gfx950 code object inside a library, written to outdir.  .hip_fatbin holds one offload bundle per unit, one
+    behind the other, and clang-offload-bundler reads only the first: the section is cut at every bundle's magic and each piece
+    unbundled on its own."""
+    llvm = "/opt/rocm/lib/llvm/bin"
+    fat = os.path.join(outdir, "fatbin")
+    subprocess.check_call([os.path.join(llvm, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, lib, os.path.join(outdir, "stripped.so")])
+    with open(fat, "rb") as f:
+        data = f.read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    starts, i = [], data.find(magic)
+    while i >= 0:
+        starts.append(i)
+        i = data.find(magic, i + 1)
+    cos = []
+    for n, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
+        piece, co = os.path.join(outdir, "bundle%d" % n), os.path.join(outdir, "unit%d.co" % n)
+        with open(piece, "wb") as f:
+            f.write(data[a:b])
+        subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + piece,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+        cos.append(co)
+    return cos
 
 
 HOSTTEST = os.path.join(LIBDIR, "mc_hosttest")
@@ -113,14 +153,12 @@ def build_variant(name, force=False, verbose=False):
 
 
 def build_variants(force=False, verbose=False, names=DEFAULT_VARIANTS):
-    from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max(len(names), 1)) as ex:
         return list(ex.map(lambda n: build_variant(n, force, verbose), names))
 
 
 def build_all(force=False, verbose=False):
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(2) as ex:  # (hipcc runs a minute per library: the product and the fuzzed walk side by side)
+    with ThreadPoolExecutor(2) as ex:  # (the product and the fuzzed walk side by side)
         v = ex.submit(build_variants, force, verbose)
         build_lib(force, verbose)
         v.result()

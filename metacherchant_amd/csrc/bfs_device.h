@@ -21,7 +21,7 @@
 //             leading levels that are exactly what the sequential BFS would have found; anything
 //             else falls back to an exact one-level replay (bfs_narrow).
 #pragma once
-#include "kmer_device.h"
+#include "device_types.h"
 
 namespace mc {
 
@@ -148,37 +148,6 @@ constexpr uint32_t BFS_TRACE_RECORDS = 1u << 16;
 #else
 #define BFS_TRACE(S, w0, w1, w2, w3, w4, w5, w6, w7) do {} while (0)
 #endif
-
-struct BfsCtl {
-    unsigned long long n;       // |distanceToKmer|
-    unsigned long long lb, le;  // current frontier = entries [lb, le)
-    unsigned long long c0;      // next candidate rank inside the frontier (wide path)
-    unsigned long long lookups;
-    unsigned long long rounds_narrow, rounds_slow, chunks_wide, scout_hops, scout_levels, scout_calls, scout_nf, scout_m0, slow_mismatch, slow_starved, slow_forced;
-    unsigned long long tacc[8];  // MC_BFS_TIMING builds: 10 ns ticks per phase of a narrow round
-    unsigned long long trace_n;  // MC_BFS_TRACE builds: records written to BfsState::trace so far
-    long long level;            // distance of the frontier
-    int status;
-    int seeds_done;
-};
-
-struct ScoutBox;
-struct BfsState {
-    uint64_t *hi, *lo;  // distanceToKmer keys in insertion order
-    int32_t *dist;
-    int16_t *cov;
-    uint32_t *flags;    // bit0: in lastKmers; bit1: seed window queued more than once.  Pre-zeroed.
-    uint64_t dcap;
-    uint64_t *vis;      // index of the arrays above: buckets of two (fingerprint << 32 | index) entries
-    uint64_t bmask;     // number of buckets - 1
-    BfsCtl *ctl;
-    uint64_t *path;     // SCOUT_MAX_F * PATH_WORDS words: the predicted paths of the walkers (scout_run)
-    ScoutBox *box;      // mailbox between this job's workgroup and its scouting companion (nullptr: none)
-    uint32_t *trace;    // MC_BFS_TRACE builds: BFS_TRACE_RECORDS records of 8 words (nullptr: none)
-    const uint64_t *seed_hi, *seed_lo;
-    uint64_t n_seeds;
-    int dir;
-};
 
 // The walk state in BfsCtl is written by thread 0 and read by every thread behind a barrier.  Those reads decide what the
 // whole workgroup does next, so every wave must see the same value: they are L1-bypassing loads (a wave that read a

@@ -21,9 +21,10 @@
 // empty in 994 runs of 1000 at that size; when it is not, mcgpu.hip (dup_fixup) sweeps the table once for the listed keys' slots,
 // writes the SUM of a key's counters into each of them -- so the walk, which comes by bases, and mc_get's sweep read the reference's
 // count wherever they look -- and remembers the slots: exports and "Hashtable size" count a key once, and the slots get their own
-// counts back before the table takes more reads or moves to hash-prefix regions.
+// counts back before the table takes more reads or moves to hash-prefix regions.  The plain types the context holds (DupL1, DupL2,
+// DupSet, DupTwin, PhantomQ) are in device_types.h; the walk asks for the check through mcgpu.hip (phantom_verify).
 #pragma once
-#include "kmer_device.h"
+#include "device_types.h"
 
 namespace mc {
 
@@ -41,16 +42,6 @@ __host__ __device__ __forceinline__ uint32_t dup_mix3(uint64_t key)
     x ^= x >> 15;
     return x;
 }
-
-// level-1 stream: keys[((b * nseg) + seg) * cap + i], counts[b * nseg + seg]; the last segment of every bucket takes the keys
-// that enter the table outside the merge kernel (the drain of handed-on occurrences, spilled records), by a global atomic
-struct DupL1 {
-    uint64_t *keys;    // nullptr: nobody collects
-    uint32_t *counts;
-    uint32_t nseg;
-    uint64_t cap;
-    uint32_t *lost;    // set when a segment overflows: the stream is then not used
-};
 
 __device__ __forceinline__ void dup_l1_extra(const DupL1 &d, uint64_t key)
 {
@@ -86,19 +77,6 @@ __global__ void __launch_bounds__(256) k_dup_sweep(const Slot *__restrict__ slot
 // level 2.  Workgroup (b, s): slice s of bucket b's segments -> F2 sub-buckets; it owns segment s of every sub-bucket (b, f), so its
 // fill levels live in LDS and no stream is shared (a first version took each tile's place in a shared stream with a global atomic a
 // sub-bucket and tile: 57 M of them for configs[2] scaled, 3.2 ms for 7.4 GB).  Keys of (b, f, s) at bucket(b) + ((f * slices + s) * cap + i).
-struct DupL2 {
-    uint64_t *out_a, *out_b;   // buckets [0, split) in out_a, the others in out_b (the pipeline's two idle streams serve as one buffer)
-    uint32_t split;
-    uint32_t *counts;          // [(b << f2_lg | f) * slices + s]
-    uint32_t f2_lg, slices;
-    uint64_t cap;              // keys a segment holds
-    uint32_t *lost;
-    __host__ __device__ __forceinline__ uint64_t *bucket(uint32_t b) const
-    {
-        const uint64_t per = ((uint64_t)slices << f2_lg) * cap;
-        return b < split ? out_a + (uint64_t)b * per : out_b + (uint64_t)(b - split) * per;
-    }
-};
 constexpr uint32_t DUP_MAX_SLICE_SEGS = 960;   // segments of a bucket one workgroup of level 2 takes at most (the host launches enough slices; two workgroups' LDS a CU)
 constexpr uint32_t DUP_MAX_SLICES = 8;
 struct DupScatterLds {
@@ -305,15 +283,6 @@ __global__ void __launch_bounds__(DUP_FIND_THREADS) k_dup_find(DupL2 in, DupOut 
     }
 }
 
-// ---- the fix-up: the listed keys as a small set in global memory (qk: ~0 = free), per entry the sum of the key's counters, the
-// lowest slot that holds it (the one exports count) and the number of slots
-struct DupSet {
-    unsigned long long *qk;
-    unsigned long long *tot;
-    unsigned long long *prim;
-    uint64_t mask;               // slots - 1; 0 with qk == nullptr: no set
-    unsigned long long *n_keys;  // distinct keys in the set
-};
 __device__ __forceinline__ bool dup_set_find(const DupSet &q, uint64_t key, uint64_t *at)
 {
     for (uint64_t s = fmix64(key) & q.mask;; s = (s + 1) & q.mask) {
@@ -334,8 +303,6 @@ __global__ void k_dupq_build(const unsigned long long *__restrict__ keys, uint64
         }
     }
 }
-// every slot of a listed key: (slot index, its own count, the set entry) noted, count added to the entry's sum
-struct DupTwin { unsigned long long slot; uint32_t own, entry; };
 __global__ void k_dupq_sweep(const Slot *__restrict__ slots, uint64_t n_slots, DupSet q, DupTwin *tw, unsigned long long *n_tw, uint64_t tw_cap)
 {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -379,11 +346,6 @@ __device__ __forceinline__ bool dup_is_shadow(const DupSet &q, uint64_t key, uin
 // table's keys as the join left them (DupL2: a few thousand keys a sub-bucket, only the sub-bucket of a query is read).  A hit gets a
 // slot in the bin of the string that asked (count 0), the join runs again -- the key now sits in two slots, both take the sum -- and the
 // walk is repeated.  In all but ~1e-5 of the runs there is no hit and this costs one small kernel and a scan of the queried sub-buckets.
-struct PhantomQ {
-    unsigned long long *key, *hi, *lo;   // the hash that was asked for and the string that asked
-    unsigned long long *n;               // how many (may pass cap: the caller then asks again with more room)
-    uint64_t cap;
-};
 // items: n k-mers (hi may be null: k <= 32); nb = 0: the k-mers themselves (seeds), else their nb neighbours in direction dir
 template <int MODE>
 __global__ void __launch_bounds__(256) k_phantom_queries(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, uint64_t n, int nb, int dir, int k,

@@ -1,468 +1,24 @@
 // libmcgpu.so -- MI355X (gfx950) k-mer counting + de Bruijn BFS behind the C ABI of include/mcgpu.h.
 // Hand-written HIP for CDNA4: wave64, 16-byte table slots read with one dwordx4, memory-side
 // 64-bit CAS / 32-bit add atomics, LDS-staged ordered compaction.  No MFMA: integer/hash work.
+// This unit: the table, the key join, the counting pipeline and the context ABI (context.h lists the others).
 //
 // Reference lines each piece replaces are cited at the definitions (src/... and itmo!/... as in
 // include/mcgpu.h).  Nothing in this file links or calls oracle/.
-#include <hip/hip_runtime.h>
 #include <unistd.h>
 
-#include <algorithm>
-#include <array>
-#include <atomic>
-#include <chrono>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
-#include <string>
 #include <thread>
-#include <map>
-#include <vector>
 
-#include <dlfcn.h>
-#if __has_include(<rccl/rccl.h>)
-#include <rccl/rccl.h>
-#else
-// librccl is loaded at run time (RcclApi below); without its headers the library still builds, from the few declarations
-// of <rccl/rccl.h> the transport uses
-typedef struct ncclComm *ncclComm_t;
-typedef enum { ncclSuccess = 0 } ncclResult_t;
-typedef enum { ncclInt8 = 0, ncclUint8 = 1 } ncclDataType_t;
-#endif
-
-#include "../../include/mcgpu.h"
-#include "kmer_device.h"
-#include "bfs_device.h"
+#include "context.h"
 #include "count_pipeline.h"
 #include "count_long.h"
-#include "tokenizer.h"
-#include "switches.h"
-#include "host/envfinder.h"
 
-using namespace mc;
-
-// ------------------------------------------------------------------------------------------ ctx
-
-// Device scratch of the tokeniser (csrc/tokenizer.h), kept between calls: a file is read in chunks of the same size,
-// and hipMalloc / hipFree of gigabyte buffers cost milliseconds each.  Best fit with at most 2x slack; at most 48 idle
-// blocks (the smallest goes first).
-struct DevPool {
-    std::vector<std::pair<void *, size_t>> idle;
-    hipError_t get(size_t bytes, void **out, size_t *got)
-    {
-        bytes = std::max<size_t>((bytes + 255) / 256 * 256, 256);
-        size_t best = idle.size();
-        for (size_t i = 0; i < idle.size(); i++)
-            if (idle[i].second >= bytes && idle[i].second <= 2 * bytes + (1u << 20) && (best == idle.size() || idle[i].second < idle[best].second)) best = i;
-        if (best < idle.size()) {
-            *out = idle[best].first;
-            *got = idle[best].second;
-            idle.erase(idle.begin() + (long)best);
-            return hipSuccess;
-        }
-        *got = bytes;
-        hipError_t e = hipMalloc(out, bytes);
-        if (e == hipErrorOutOfMemory && !idle.empty()) {  // give the idle blocks back and try once more
-            release();
-            e = hipMalloc(out, bytes);
-        }
-        return e;
-    }
-    void put(void *p, size_t bytes)
-    {
-        idle.emplace_back(p, bytes);
-        if (idle.size() > 48) {
-            size_t small = 0;
-            for (size_t i = 1; i < idle.size(); i++)
-                if (idle[i].second < idle[small].second) small = i;
-            (void)hipFree(idle[small].first);
-            idle.erase(idle.begin() + (long)small);
-        }
-    }
-    void release()
-    {
-        for (auto &b : idle) (void)hipFree(b.first);
-        idle.clear();
-    }
-};
-template <class T>
-struct PoolBuf {  // RAII: a block of a DevPool
-    T *p = nullptr;
-    size_t bytes = 0;
-    DevPool *pool = nullptr;
-    PoolBuf() = default;
-    PoolBuf(const PoolBuf &) = delete;
-    PoolBuf &operator=(const PoolBuf &) = delete;
-    ~PoolBuf() { if (p) pool->put(p, bytes); }
-    hipError_t alloc(DevPool *pl, size_t n)
-    {
-        pool = pl;
-        return pl->get(std::max<size_t>(n, 1) * sizeof(T), reinterpret_cast<void **>(&p), &bytes);
-    }
-};
-
-// Table memory, kept across tables: fresh device memory comes zero-filled by the driver at ~30 GB/s (0.7 s for the 22 GB
-// table of configs[1]), which a context without a capacity hint paid every time its table went to its real size.  A
-// table that is given up goes here instead of back to the driver (the two largest idle blocks per device are kept) and the
-// next table of about its size takes it; any allocation that fails for lack of memory empties the pool and tries again.
-struct TablePool {
-    std::mutex mu;
-    std::map<int, DevPool> per_device;
-    bool on = read_pool_switches().table_pool;
-    hipError_t get(int dev, size_t bytes, void **out, size_t *got)
-    {
-        if (!on) { *got = bytes; return hipMalloc(out, bytes); }
-        std::lock_guard<std::mutex> g(mu);
-        return per_device[dev].get(bytes, out, got);
-    }
-    void put(int dev, void *p, size_t bytes)
-    {
-        if (!p) return;
-        if (!on) { (void)hipFree(p); return; }
-        std::lock_guard<std::mutex> g(mu);
-        DevPool &P = per_device[dev];
-        P.put(p, bytes);
-        while (P.idle.size() > 2) {
-            size_t small = 0;
-            for (size_t i = 1; i < P.idle.size(); i++)
-                if (P.idle[i].second < P.idle[small].second) small = i;
-            (void)hipFree(P.idle[small].first);
-            P.idle.erase(P.idle.begin() + (long)small);
-        }
-    }
-    void release(int dev)
-    {
-        std::lock_guard<std::mutex> g(mu);
-        per_device[dev].release();
-    }
-};
-static TablePool g_table_pool;
-
-// The large scratch buffers of the counting pipeline (record and key streams: gigabytes per context), kept across contexts
-// the same way: memory handed back with hipFree is reclaimed by the driver lazily and in bulk -- every third fresh context
-// of a process that counted configs[1] stalled 1.5 - 4 s in its first launch while that happened.  Blocks of 64 MB or more
-// go to this pool (DevPool's limits: best fit with at most 2x slack, 48 idle blocks); an allocation that fails for lack of
-// memory empties both pools and tries again.
-struct ScratchPool {
-    static constexpr size_t MIN_BYTES = 64ull << 20;
-    std::mutex mu;
-    std::map<int, DevPool> per_device;
-    bool on = read_pool_switches().scratch_pool;
-    hipError_t get(int dev, size_t bytes, void **out, size_t *got)
-    {
-        if (!on || bytes < MIN_BYTES) { *got = bytes; return hipMalloc(out, std::max<size_t>(bytes, 1)); }
-        std::lock_guard<std::mutex> g(mu);
-        return per_device[dev].get(bytes, out, got);
-    }
-    void put(int dev, void *p, size_t bytes)
-    {
-        if (!p) return;
-        if (!on || bytes < MIN_BYTES) { (void)hipFree(p); return; }
-        std::lock_guard<std::mutex> g(mu);
-        DevPool &P = per_device[dev];
-        P.put(p, bytes);
-        for (;;) {  // at most max_idle bytes stay idle (MC_SCRATCH_POOL_GB, default 64): the largest blocks go first
-            size_t total = 0, big = 0;
-            for (size_t i = 0; i < P.idle.size(); i++) {
-                total += P.idle[i].second;
-                if (P.idle[i].second > P.idle[big].second) big = i;
-            }
-            if (total <= max_idle || P.idle.empty()) break;
-            (void)hipFree(P.idle[big].first);
-            P.idle.erase(P.idle.begin() + (long)big);
-        }
-    }
-    void release(int dev)
-    {
-        std::lock_guard<std::mutex> g(mu);
-        per_device[dev].release();
-    }
-    size_t max_idle = read_pool_switches().scratch_idle_max;
-};
-static ScratchPool g_scratch_pool;
-
-// device buffers of one BFS job, kept in the context between calls
-struct BfsJobBuffers {
-    BfsState S{};
-    uint64_t *d_seed_hi = nullptr, *d_seed_lo = nullptr;
-    uint64_t seed_cap = 0;
-    BfsJobBuffers() = default;
-    BfsJobBuffers(const BfsJobBuffers &) = delete;
-    BfsJobBuffers &operator=(const BfsJobBuffers &) = delete;
-    void free_arrays()
-    {
-        (void)hipFree(S.hi); (void)hipFree(S.lo); (void)hipFree(S.dist); (void)hipFree(S.cov);
-        (void)hipFree(S.flags); (void)hipFree(S.vis);
-        S.hi = S.lo = nullptr; S.dist = nullptr; S.cov = nullptr; S.flags = nullptr; S.vis = nullptr;
-    }
-    ~BfsJobBuffers()
-    {
-        free_arrays();
-        (void)hipFree(S.ctl);
-        (void)hipFree(S.path);
-        (void)hipFree(S.box);
-        (void)hipFree(S.trace);
-        (void)hipFree(d_seed_hi);
-        (void)hipFree(d_seed_lo);
-    }
-};
-
-
-
-struct mc_ctx {
-    mc_config cfg{};
-    mc_switches sw;  // the environment switches, read by mc_create (switches.h)
-    std::mutex mu;
-    std::string err;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // a side stream: the read store's copy of a batch (rs_append) and the walk's companions (mc_bfs_batch) run here
-    hipStream_t pipe_stream = nullptr;
-    hipEvent_t ev_piece[8] = {};
-    hipEvent_t ev_seq[16] = {};  // behind every kernel of a per-window run in pieces (add_reads_partitioned_once)
-    hipEvent_t ev_t[4] = {};  // P1 start, P1 end, P2 end, P3 end of a pipeline run enqueued without a host round trip in between
-    // The read store: the packed bases of every read this context was given since the last mc_clear, batch after
-    // batch (each starting on a word boundary).  Table slots point into it (kmer_device.h ptr_encode) and the BFS
-    // reads its look-ahead from it.  rs_from: a BFS-only context (mc_solid_from_pairs_dev) borrows the store of the
-    // context that counted this rank's reads (mc_share_read_store).
-    uint64_t *rs_words = nullptr;
-    uint64_t rs_cap_words = 0, rs_bases = 0;
-    bool rs_enabled = true;
-    // mc_set_read_pointers' other modes.  rs_virtual: this context keeps no store, but the reads it extracts or counts sit in ANOTHER
-    // context's store (the walking rank's, mc_read_store_import_dev) from rs_bases on: their pointers are worked out as if they were
-    // appended here, and only the bookkeeping is done.  all_ptrs: every record mc_add_superkmers*_dev is handed carries a pointer.
-    // rs_hi_bases: how far the store is filled by imports (a real store; never below what rs_bases has reached).
-    bool rs_virtual = false, all_ptrs = false;
-    bool no_vleaf = false;  // (add_reads_partitioned: this batch's sample asked for a table beyond 2^19 regions; the first level runs again in the two-array form)
-    uint64_t rs_hi_bases = 0;
-    uint64_t rs_end() const { return std::max(rs_bases, rs_hi_bases); }
-    mc_ctx *rs_from = nullptr;
-    uint64_t cur_ptr_base = ~0ull;  // store position of base 0 of the batch being counted (~0: no pointers for it)
-    uint32_t ptr_tries = 1;         // count_pipeline.h k_p3_merge: 16 while the records of other ranks (no pointers) are merged
-    // The solid list P3 left in pipe.a_recs (count_pipeline.h P3Emit): valid for threshold cov_hint until anything
-    // else touches the table or the pipeline buffers.
-    bool solid_list_fresh = false;
-    uint32_t solid_list_segs = 0;
-    uint64_t solid_list_segcap = 0;
-
-    // table
-    Slot *slots = nullptr;
-    size_t slots_bytes = 0;    // size of the block `slots` sits in (it may come from g_table_pool, a little larger than asked for)
-    uint64_t n_regions = 0;    // regions of 2^sb slots: a power of two, or (minimizer-bin tables of >= 512 regions) any multiple of 512
-    uint32_t rb = 0, sb = MC_REGION_LG;  // rb = log2(n_regions) when that is a power of two (else its floor)
-    unsigned long long *d_ctr = nullptr;  // [0] n_used, [1] empty_cnt, [2] scratch counter, [3] solid n_used, [4..5] read summary, [6] keys with count >= cov_hint,
-                                          // [7] parked additions, [8] the `fatal` flag (d_fatal points here), [10..13] read summary of a device batch
-    unsigned long long *h_scratch = nullptr;  // 32 pinned words: where the small device-to-host copies land (a copy into pageable memory is staged)
-    uint32_t *d_fatal = nullptr;
-    uint64_t n_used_host = 0;
-    bool finalized = false;
-
-    // "solid" table (kmer_device.h): only the keys with count >= solid_cov, sparse.
-    // Built lazily by mc_bfs_batch; the BFS never touches the counting table.
-    Slot *solid = nullptr;
-    uint32_t solid_lg = 0;
-    int solid_cov = -1;  // -1: not built / stale
-    bool solid_external = false;  // built by mc_solid_from_pairs_dev, not from this context's counting table
-    bool solid_is_table = false;  // ... and does so now (solid_view)
-    bool want_list = false;       // the merge kernel lists the solid keys (count_pipeline.h P3Emit): for exports, and for the copy
-    int solid_external_cov = -1;
-    double pending_solid_ms = 0;
-    uint64_t n_solid = 0;
-    // mc_set_coverage_hint: the merge kernel of the counting pipeline keeps d_ctr[6] = #keys with
-    // count >= cov_hint, so ensure_solid needs no counting sweep.  Only additions that go through that
-    // kernel maintain it; any other kind of addition clears solid_tracked until mc_clear.
-    int cov_hint = 0;
-    bool solid_tracked = true;
-
-    mc_stats st{};
-    std::vector<std::unique_ptr<BfsJobBuffers>> bfs_pool;
-
-    char *pin[16] = {};                // pinned staging buffers of h2d_fast, made on first use
-    DevPool tok_pool;                  // scratch of the device tokeniser
-    int64_t extract_in_store = -1;     // mc_group: the reads the next mc_extract_*_dev call is given sit in the read store already, from this word on (consumed by that call)
-    // Several GPUs: the walk of this context reads the counting tables of all ranks where they are (mc_shard_attach; mc_group
-    // with peer access).  h_shards[i] describes rank i's table (this context's own among them), d_shards is the same array in
-    // device memory, ipc_opened the mappings of other processes' tables this context holds.
-    std::vector<ShardRef> h_shards;
-    ShardRef *d_shards = nullptr;
-    uint32_t shard_self = 0;
-    bool shards_dropped = false;  // an attachment was dropped because the table changed: the next walk must not quietly read this rank's table alone
-    int shard_owner_mm_k = 0;
-    // A walker attaches the same tables step after step (bench.py: every step; the CLI: every batch of seeds): a mapping stays
-    // open while its handle keeps coming (in_use: part of the current attachment) and is closed when it has not for a while.
-    struct IpcMap { hipIpcMemHandle_t h; void *p; bool in_use; uint64_t addr, bytes; };  // (addr, bytes: the block in its owner's process -- a handle alone may be handed out again for another block)
-    std::vector<IpcMap> ipc_opened;
-    bool extract_by_minimizer = false; // mc_group: the next mc_extract_keys_dev call deals the keys to the owners of their minimizers (sk_owner), as the group's records are dealt (consumed by that call)
-    uint4 *d_ovf_tmp = nullptr;        // pipe_drain_handed_on: the list moved aside while it is drained
-    uint32_t *d_ovf_leaf_tmp = nullptr;
-    uint64_t ovf_tmp_cap = 0, ovf_leaf_tmp_cap = 0;
-    bool rs_copy_pending = false;      // a batch is on its way into the read store on pipe_stream (rs_append)
-    // mc_bfs_batch: job states + seeds go up in one copy (pinned h_bfs_stage -> d_bfs_stage), results come back packed
-    // (d_bfs_pack: a header block and the jobs' arrays back to back; h_bfs_hdr: the headers, pinned)
-    char *h_bfs_stage = nullptr, *d_bfs_stage = nullptr, *d_bfs_pack = nullptr, *h_bfs_hdr = nullptr;
-    uint64_t bfs_stage_cap = 0, bfs_pack_cap = 0, bfs_hdr_cap = 0;
-    std::mutex pin_mu;                 // the pinned buffers serve one copy at a time
-    hipStream_t pin_stream[8] = {};
-    int mm_k = 0;        // != 0 (= k): regions are minimizer bins and reads are counted as super-k-mers (kmer_device.h)
-    bool virgin = true;  // the table holds no key and its memory is not initialised yet
-    bool sk_form = false;  // reads of this context can travel as super-k-mer records (set once; mm_k may be given up later)
-    // scratch of the partitioned counting pipeline, kept between calls
-    struct Pipe {
-        uint64_t *a_keys = nullptr, *b_keys = nullptr, *spill_keys = nullptr;
-        uint32_t *a_hints = nullptr, *b_hints = nullptr, *spill_hints = nullptr, *tile_first = nullptr;
-        uint4 *a_recs = nullptr, *b_recs = nullptr, *spill_recs = nullptr;  // super-k-mer form (their bin words use a_hints / b_hints)
-        uint64_t a_recs_cap = 0, b_recs_cap = 0, spill_recs_cap = 0;
-        uint32_t *solid_cursors = nullptr;  // leaf fill levels of the solid-table build (minimizer-bin tables)
-        uint64_t solid_cursors_cap = 0;
-        uint32_t *emit_counts = nullptr;  // fill levels of the solid list's segments (one per P3 workgroup)
-        uint32_t *cursors1 = nullptr, *seg_counts1 = nullptr, *cursors2 = nullptr, *leaf_state = nullptr, *leaf_new = nullptr, *flags = nullptr;  // cursors1: owner cursors (multi-GPU split); cursors2: leaf fill levels; flags: [0] spill lost, [1] any leaf failed, [2] a segment of the solid list overflowed
-        unsigned long long *spill_count = nullptr;
-        uint64_t a_cap = 0, b_cap = 0, spill_cap = 0, tiles1_cap = 0, leaves_cap = 0, segs1_cap = 0, a_hints_cap = 0, b_hints_cap = 0, cursors2_cap = 0;
-        // the binned exchange (mc_extract_superkmers_binned_dev / mc_add_superkmers_binned_dev): every first-level workgroup's row of
-        // (owner, fine bucket) counters; where every cell starts in the packed stream; where every listed segment of the second level starts
-        uint32_t *skb_rows = nullptr;
-        unsigned long long *skb_cell_start = nullptr, *skb_seg_start = nullptr, *skb_small = nullptr;  // skb_small: owner offsets / windows / part offsets / a flag
-        uint64_t skb_rows_cap = 0, skb_cell_start_cap = 0, skb_seg_start_cap = 0, skb_small_cap = 0;
-        void release(int dev)
-        {   // (the large streams go to g_scratch_pool: ensure_buf took them from there)
-            g_scratch_pool.put(dev, skb_rows, skb_rows_cap * 4); g_scratch_pool.put(dev, skb_cell_start, skb_cell_start_cap * 8);
-            g_scratch_pool.put(dev, skb_seg_start, skb_seg_start_cap * 8); g_scratch_pool.put(dev, skb_small, skb_small_cap * 8);
-            g_scratch_pool.put(dev, a_keys, a_cap * 8); g_scratch_pool.put(dev, b_keys, b_cap * 8); (void)hipFree(spill_keys);
-            g_scratch_pool.put(dev, a_recs, a_recs_cap * sizeof(uint4)); g_scratch_pool.put(dev, b_recs, b_recs_cap * sizeof(uint4));
-            (void)hipFree(spill_recs); (void)hipFree(solid_cursors); (void)hipFree(emit_counts);
-            g_scratch_pool.put(dev, a_hints, a_hints_cap * 4); g_scratch_pool.put(dev, b_hints, b_hints_cap * 4); (void)hipFree(spill_hints); (void)hipFree(tile_first);
-            (void)hipFree(cursors1); (void)hipFree(seg_counts1); (void)hipFree(cursors2); (void)hipFree(leaf_state); (void)hipFree(leaf_new); (void)hipFree(flags);
-            // (spill_count lives behind flags, in the same allocation)
-            *this = Pipe{};
-        }
-    } pipe;
-
-    // Hash keys in minimizer bins: the join of the table's keys by key (dup_check.h) and what it found.
-    struct Dup {
-        // level 1: the merge kernel's (or the sweep's) key streams
-        uint64_t *l1_keys = nullptr;
-        uint64_t l1_words = 0;
-        uint32_t *l1_counts = nullptr;
-        uint64_t l1_counts_cap = 0;
-        uint32_t l1_nseg = 0;
-        uint64_t l1_cap = 0;
-        bool l1_armed = false;       // the last long run's merge kernel collected into the streams (and nothing else has touched the table since)
-        double expected_keys = 0;    // what the sample of the batch said the table will hold (a context without a hint)
-        // levels 2 and 3
-        uint64_t *l2_own = nullptr;  // where the pipeline's idle streams are too small to serve
-        uint64_t l2_own_words = 0;
-        uint32_t *l2_counts = nullptr;
-        uint64_t l2_counts_cap = 0;
-        uint32_t *flags = nullptr;            // [0] a level-1 segment overflowed, [1] a level-2 stream did
-        unsigned long long *ctr = nullptr;    // [0] keys listed, [1] distinct keys in the set, [2] slots noted
-        unsigned long long *list = nullptr;   // the listed keys (LIST_CAP)
-        static constexpr uint64_t LIST_CAP = 1u << 16;
-        // what the fix-up left: the set of keys held by more than one slot, their slots with their own counts
-        DupSet set{nullptr, nullptr, nullptr, 0, nullptr};
-        uint64_t set_slots = 0;
-        DupTwin *tw = nullptr;
-        uint64_t tw_cap = 0, n_tw = 0, n_keys = 0;
-        bool merged = false;         // the noted slots hold their keys' sums now (else: their own counts)
-        long long solid_delta = 0;   // what merging added to d_ctr[6] (keys at the coverage hint)
-        bool checked = false;        // the table as it is has been joined
-        DupL2 l2{nullptr, nullptr, 0, nullptr, 0, 0, 0, nullptr};  // the table's keys by key, as the last join left them (valid while l2_valid)
-        bool l2_valid = false;
-        // the check of a walk's "absent" look-ups by key (dup_check.h PhantomQ): queries, their order by sub-bucket, the hits
-        unsigned long long *pq_mem = nullptr;
-        uint64_t pq_cap = 0;
-        uint32_t *pq_groups = nullptr;  // [G]: the first query of every sub-bucket's list
-        uint64_t pq_groups_cap = 0;
-    } dup;
-    DupL1 dup_l1_view() const
-    {
-        if (!dup.l1_armed) return DupL1{nullptr, nullptr, 0, 0, nullptr};
-        return DupL1{dup.l1_keys, dup.l1_counts, dup.l1_nseg, dup.l1_cap, dup.flags};
-    }
-    DupSet dup_filter() const { return dup.merged && dup.n_tw ? dup.set : DupSet{nullptr, nullptr, nullptr, 0, nullptr}; }
-
-    uint64_t n_slots() const { return n_regions << sb; }
-    SolidView solid_view() const
-    {
-        SolidView t;
-        t.slots = solid;
-        t.shift = 64 - solid_lg;
-        t.rmask = (1u << 11) - 1;  // SOLID_REGION - 1
-        t.mm_k = 0;
-        t.n_regions = 0;
-        if (solid_is_table) {  // the counting table itself
-            t.slots = slots;
-            t.shift = 64 - (rb + sb);
-            t.rmask = (1u << sb) - 1;
-            t.mm_k = mm_k;
-            t.n_regions = (uint32_t)n_regions;
-        }
-        t.empty_cnt = d_ctr + 1;
-        t.fatal = d_fatal;
-        const mc_ctx *rs = rs_from ? rs_from : this;
-        t.reads = rs->rs_end() && rs->rs_words ? rs->rs_words : nullptr;
-        t.reads_bases = rs->rs_words ? rs->rs_end() : 0;
-        t.shards = d_shards;
-        t.n_shards = d_shards ? (uint32_t)h_shards.size() : 0u;
-        t.owner_mm_k = shard_owner_mm_k;
-        return t;
-    }
-    TableView view() const
-    {
-        TableView t;
-        t.slots = slots;
-        t.shift = 64 - (rb + sb);  // (hash-prefix regions: n_regions is a power of two)
-        t.rmask = (1u << sb) - 1;
-        t.n_regions = (uint32_t)n_regions;
-        t.mm_k = mm_k;
-        t.n_used = d_ctr;
-        t.empty_cnt = d_ctr + 1;
-        t.fatal = d_fatal;
-        t.ovf = d_ovf;
-        t.ovf_n = d_ctr + 7;
-        t.ovf_cap = d_ovf ? OVF_CAP : 0;
-        t.ovf_leaf = d_ovf_leaf;
-        return t;
-    }
-    static constexpr uint64_t OVF_CAP = 1ull << 22;
-    uint4 *d_ovf = nullptr;  // TableView::ovf
-    uint32_t *d_ovf_leaf = nullptr;  // TableView::ovf_leaf
-};
-
-static thread_local std::string g_create_err;
-
-static int fail(mc_ctx *c, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf; else g_create_err = buf;
-    return code;
-}
-
-#define HIPCHK(c, call)                                                                               \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return fail((c), e_ == hipErrorOutOfMemory ? MC_ENOMEM : MC_EHIP, "%s: %s (%s:%d)", #call, \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                   \
-    } while (0)
-
-template <typename T>
-struct DevBuf {  // RAII device buffer for temporaries
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    void reset() { if (p) (void)hipFree(p); p = nullptr; }
-    hipError_t alloc(size_t n) { reset(); return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(T)); }
-};
+TablePool g_table_pool;
+ScratchPool g_scratch_pool;
+thread_local std::string g_create_err;
 
 // ------------------------------------------------------------------------------------------ kernels: table
 
@@ -977,18 +533,10 @@ __global__ void k_synth_reads(uint64_t gseed, uint64_t n_contigs, uint64_t conti
 
 // ------------------------------------------------------------------------------------------ host: table management
 
-static int grid_for(uint64_t work_items, int block, int max_blocks = 256 * 8)
-{
-    uint64_t g = (work_items + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > (uint64_t)max_blocks) g = max_blocks;
-    return (int)g;
-}
-
 // Number of regions for a table of at least `slots` slots.  Hash-prefix regions need a power of two; minimizer bins
 // are numbered by multiplication (count_pipeline.h mulhi32), so those tables come in steps of 512 regions (2 M slots,
 // 32 MB), of 1024 beyond 2^19 regions -- times 2^g beyond 2^20, where a leaf of the counting pipeline covers 2^g regions.
-static uint64_t regions_for(const mc_ctx *c, uint64_t slots)
+uint64_t regions_for(const mc_ctx *c, uint64_t slots)
 {
     uint64_t want = std::max<uint64_t>((slots + (1ull << c->sb) - 1) >> c->sb, 1);
     uint64_t p2 = 1;
@@ -1043,7 +591,6 @@ static int table_alloc(mc_ctx *c, uint64_t n_regions)
 }
 
 // the direct kernels, lookups and exports need real (EMPTY-initialised) slots
-namespace { void shard_detach_locked(mc_ctx *c); }
 // The table is about to hold other counts (or to move: growing and rehashing give the old block back to the pool): results
 // read before are void, and so is a walker's view of the ranks' tables (mc_shard_attach) -- it names this table's block
 // and geometry as they were.  ADVICE r4: the attachment used to survive, and the next walk read a freed block.
@@ -1055,7 +602,7 @@ static inline void counts_changed(mc_ctx *c)
     c->dup.l2_valid = false;
 }
 
-static int materialize(mc_ctx *c)
+int materialize(mc_ctx *c)
 {
     if (!c->virgin) return MC_OK;
     hipLaunchKernelGGL(k_fill_empty, dim3(grid_for(c->n_slots(), 256)), dim3(256), 0, c->stream, c->slots,
@@ -1065,7 +612,7 @@ static int materialize(mc_ctx *c)
     return MC_OK;
 }
 
-static int read_counters(mc_ctx *c, unsigned long long *n_used, uint32_t *fatal)
+int read_counters(mc_ctx *c, unsigned long long *n_used, uint32_t *fatal)
 {
     unsigned long long *h = c->h_scratch;
     HIPCHK(c, hipMemcpyAsync(h, c->d_ctr, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -1104,12 +651,11 @@ struct TableSwap {
 // Hash keys in minimizer bins (count_long.h: polynomial keys, k > 32, counted as long records): nothing that has only the key
 // can find it there, and such a table cannot be rebuilt with another number of bins either.  Everything that works by key --
 // mc_get, key streams, the direct kernel, growing -- first moves the table to hash-prefix regions, for good (by_key_ready).
-static inline bool hash_bins(const mc_ctx *c) { return c->mm_k != 0 && c->cfg.key_mode != MC_KEY_PACKED; }
 __global__ void k_ctr_add(unsigned long long *p, long long d) { if (threadIdx.x == 0 && blockIdx.x == 0) *p += (unsigned long long)d; }
 // The slots of keys that sit in several regions (dup_check.h) get their own counts back: before the table takes more reads (the
 // merge kernel adds to whichever slot a k-mer's bin holds) and before its keys move to hash-prefix regions (where equal keys meet
 // and their counts add up by themselves).
-static int dup_unmerge(mc_ctx *c)
+int dup_unmerge(mc_ctx *c)
 {
     mc_ctx::Dup &D = c->dup;
     if (!D.merged || !D.n_tw) { D.merged = false; return MC_OK; }
@@ -1136,9 +682,9 @@ static void dup_forget(mc_ctx *c)
 // copy of the solid k-mers), 2 a small batch took the direct kernel, 3 the long form declined a batch (nothing vouched for the table's
 // size), 4 bins overflowed or the table had to grow, 5 more keys sat in several regions than the join's lists take
 static int to_hash_regions(mc_ctx *c, int why = 1);
-static inline int by_key_ready(mc_ctx *c, int why = 1) { return hash_bins(c) ? to_hash_regions(c, why) : MC_OK; }
+int by_key_ready(mc_ctx *c, int why) { return hash_bins(c) ? to_hash_regions(c, why) : MC_OK; }
 
-static int table_grow(mc_ctx *c, uint64_t new_regions)
+int table_grow(mc_ctx *c, uint64_t new_regions)
 {
     if (hash_bins(c) && c->virgin) {  // nothing to move: another empty table, still in minimizer bins
         table_release(c, c->slots, c->slots_bytes);
@@ -1212,7 +758,7 @@ static int to_hash_regions(mc_ctx *c, int why)
 
 // Additions that found their region full were parked (TableView::ovf): enlarge the table -- twice as many regions
 // split the bins that were crowded together -- and add them again, until none is left.
-static int drain_parked(mc_ctx *c)
+int drain_parked(mc_ctx *c)
 {
     for (int attempt = 0;; attempt++) {
         unsigned long long n = 0;
@@ -1272,20 +818,6 @@ static int table_reserve(mc_ctx *c, uint64_t incoming, uint64_t *allowed)
     }
 }
 
-template <typename F>
-static int timed(mc_ctx *c, double *acc_ms, F &&launch)
-{
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    launch();
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *acc_ms += ms;
-    return MC_OK;
-}
-
 static void launch_count(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t r0, uint64_t r1)
 {
     const int block = 256;
@@ -1309,7 +841,7 @@ static void launch_count(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_o
 }
 
 // hipMalloc that gives the pools' idle blocks back to the driver before it reports "out of memory"
-static hipError_t dev_malloc(mc_ctx *c, void **p, size_t bytes)
+hipError_t dev_malloc(mc_ctx *c, void **p, size_t bytes)
 {
     hipError_t e = hipMalloc(p, bytes);
     if (e == hipErrorOutOfMemory) {
@@ -1321,42 +853,11 @@ static hipError_t dev_malloc(mc_ctx *c, void **p, size_t bytes)
     return e;
 }
 
-template <typename T>
-static int ensure_buf(mc_ctx *c, T **p, uint64_t *cap, uint64_t need)
-{   // (blocks of 64 MB and more come from and go to g_scratch_pool: *cap may come out above `need`)
-    if (*cap >= need && *p) return MC_OK;
-    if (*p) {  // (a block that goes back to the pool may be handed out at once: what is queued on it must be done)
-        (void)hipStreamSynchronize(c->stream);
-        if (c->pipe_stream) (void)hipStreamSynchronize(c->pipe_stream);
-        g_scratch_pool.put(c->cfg.device, *p, *cap * sizeof(T));
-    }
-    *p = nullptr;
-    *cap = 0;
-    const size_t bytes = std::max<uint64_t>(need, 1) * sizeof(T);
-    size_t got = 0;
-    hipError_t e = g_scratch_pool.get(c->cfg.device, bytes, reinterpret_cast<void **>(p), &got);
-    if (e == hipErrorOutOfMemory) {  // (idle blocks are given back first)
-        (void)hipGetLastError();
-        g_table_pool.release(c->cfg.device);
-        g_scratch_pool.release(c->cfg.device);
-        e = g_scratch_pool.get(c->cfg.device, bytes, reinterpret_cast<void **>(p), &got);
-    }
-    if (e != hipSuccess) {
-        size_t fr = 0, tot = 0;
-        (void)hipMemGetInfo(&fr, &tot);
-        *p = nullptr;
-        return fail(c, e == hipErrorOutOfMemory ? MC_ENOMEM : MC_EHIP, "scratch of %.2f GB: %s (%.2f of %.2f GB free on the device)",
-                    bytes / 1e9, hipGetErrorString(e), fr / 1e9, tot / 1e9);
-    }
-    *cap = std::max<uint64_t>(need, got / sizeof(T));
-    return MC_OK;
-}
-
 // ------------------------------------------------------------------------------------------ equal keys in different regions (dup_check.h)
 
 // MC_DUP_CHECK=0: no join.  The one switch read on every call rather than at mc_create (switches.h): bench.py turns it off on a
 // live context to measure the unchecked rate (config2.value_unchecked).
-static bool dup_check_on()
+bool dup_check_on()
 {
     const char *e = getenv("MC_DUP_CHECK");
     return !(e && !strcmp(e, "0"));
@@ -1501,7 +1002,7 @@ static int dup_fixup(mc_ctx *c, uint64_t n_listed)
 
 // mc_finalize_counts: a table of hash keys in minimizer bins is joined by key (dup_check.h) unless that has been done for the
 // table as it is.
-static int ensure_dups(mc_ctx *c)
+int ensure_dups(mc_ctx *c)
 {
     mc_ctx::Dup &D = c->dup;
     mc_ctx::Pipe &P = c->pipe;
@@ -2631,7 +2132,7 @@ static int add_records_binned(mc_ctx *c, const uint4 *d_recs, const uint32_t *d_
 // Appends the packed bases [first_off, last_off) of a batch (word-aligned copy from the batch's own buffer) to the read
 // store and sets cur_ptr_base so that store position = cur_ptr_base + position in the batch.  in_place >= 0: the batch
 // already sits in the store from word `in_place` on (mc_add_reads_packed uploads straight into it).
-static int rs_reserve(mc_ctx *c, uint64_t more_words)
+int rs_reserve(mc_ctx *c, uint64_t more_words)
 {
     const uint64_t used = c->rs_words ? c->rs_end() / 32 : 0, need = std::max(c->rs_bases / 32 + more_words, used) + 2;  // (used: what must survive a move)
     if (need <= c->rs_cap_words) return MC_OK;
@@ -3037,8 +2538,7 @@ int mc_set_stream(mc_ctx *c, void *hip_stream)
     return MC_OK;
 }
 
-static int add_reads_dev_locked(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t n_reads, uint64_t n_bases,
-                                int64_t in_store = -1);
+}  // extern "C"
 
 // Host (pageable) memory to the device.  A plain hipMemcpy of pageable memory stages through one thread; a few
 // threads each staging 8 MB pieces through their own pinned buffers and stream reach the link rate
@@ -3046,7 +2546,7 @@ static int add_reads_dev_locked(mc_ctx *c, const uint64_t *d_words, const uint64
 // fd >= 0: the bytes come from that file at file_off instead (pread straight into the pinned buffers: no page faults on
 // a mapping).  Touches no state of the context but the pinned buffers (under their own lock), so the file reader can
 // run it beside the kernels of the chunk before; returns a hipError_t-free verdict for the caller to report.
-static bool h2d_pinned(mc_ctx *c, void *dst, const void *src, size_t bytes, int fd, uint64_t file_off)
+bool h2d_pinned(mc_ctx *c, void *dst, const void *src, size_t bytes, int fd, uint64_t file_off)
 {
     constexpr size_t CHUNK = 8u << 20;
     constexpr int T = 8;  // staging threads, two pinned buffers each (mc_ctx::pin, pin_stream)
@@ -3098,7 +2598,7 @@ static bool h2d_pinned(mc_ctx *c, void *dst, const void *src, size_t bytes, int 
     return true;
 }
 
-static int h2d_fast(mc_ctx *c, void *dst, const void *src, size_t bytes)
+int h2d_fast(mc_ctx *c, void *dst, const void *src, size_t bytes)
 {
     if (bytes < (32u << 20)) {
         HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
@@ -3108,6 +2608,8 @@ static int h2d_fast(mc_ctx *c, void *dst, const void *src, size_t bytes)
     if (!h2d_pinned(c, dst, src, bytes, -1, 0)) return fail(c, MC_EHIP, "host-to-device copy failed");
     return MC_OK;
 }
+
+extern "C" {
 
 int mc_add_reads_packed(mc_ctx *c, const uint64_t *words, const uint64_t *off, uint64_t n_reads)
 {
@@ -3150,10 +2652,11 @@ int mc_add_reads_packed(mc_ctx *c, const uint64_t *words, const uint64_t *off, u
     return rc;
 }
 
+}  // extern "C"
+
 // reads resident in HBM (the context's lock is held)
 static int add_reads_dev_counted(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t n_reads, uint64_t n_bases, int64_t in_store);
-static int add_reads_dev_locked(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t n_reads, uint64_t n_bases,
-                                int64_t in_store)
+int add_reads_dev_locked(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t n_reads, uint64_t n_bases, int64_t in_store)
 {
     const int rc = add_reads_dev_counted(c, d_words, d_off, n_reads, n_bases, in_store);
     if (c->rs_copy_pending) {  // the caller's buffer is his again when this returns, and later work on the stream may read the store
@@ -3247,6 +2750,8 @@ static int add_reads_dev_counted(mc_ctx *c, const uint64_t *d_words, const uint6
     return add_reads_impl(c, d_words, d_off, h_off.data(), n_reads);
 }
 
+extern "C" {
+
 int mc_add_reads_packed_dev(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t n_reads,
                             uint64_t n_bases)
 {
@@ -3324,387 +2829,6 @@ int mc_add_pairs_dev(mc_ctx *c, const int64_t *d_keys, const int16_t *d_counts, 
     counts_changed(c);
     c->solid_cov = -1; c->solid_external = false;
     return MC_OK;
-}
-
-// ---- f1 on the device: csrc/tokenizer.h driven over one chunk of an uncompressed FASTA / FASTQ file
-
-// exclusive scan of n 32-bit counts into 64-bit offsets; *total on the host
-static int tok_scan(mc_ctx *c, const uint32_t *d_in, uint64_t n, unsigned long long *d_out, uint64_t *total)
-{
-    const uint64_t m = std::max<uint64_t>((n + tok::SCAN_TILE - 1) / tok::SCAN_TILE, 1);
-    PoolBuf<unsigned long long> sums;
-    HIPCHK(c, sums.alloc(&c->tok_pool, m + 1));
-    hipLaunchKernelGGL(tok::k_scan_sums, dim3((unsigned)m), dim3(tok::T_THREADS), 0, c->stream, d_in, n, sums.p);
-    hipLaunchKernelGGL(tok::k_scan_one, dim3(1), dim3(1024), 0, c->stream, sums.p, m, sums.p + m);
-    hipLaunchKernelGGL(tok::k_scan_apply, dim3((unsigned)m), dim3(tok::T_THREADS), 0, c->stream, d_in, n, sums.p, d_out);
-    HIPCHK(c, hipGetLastError());
-    unsigned long long t = 0;
-    HIPCHK(c, hipMemcpyAsync(&t, sums.p + m, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *total = t;
-    return MC_OK;
-}
-
-// Text bytes [b, e) of a mapped file (a whole number of records) -> packed reads in HBM -> counted.  *declined: the
-// device saw something the host parser has to deal with; nothing was added.  The context's lock is held.
-// The chunks of one file, tokenised into the read store back to back and counted together when the file ends: one run
-// of the counting pipeline (which reads and rewrites the whole table) instead of one per 256 MB of text.
-struct TokPending {
-    PoolBuf<uint64_t> off;     // read offsets of all chunks so far (+ the end), relative to the first chunk's first base
-    uint64_t off_cap = 0;
-    uint64_t reads = 0, bases = 0;
-    int64_t base_word = -1;    // where the first chunk starts in the read store
-};
-static int tok_flush_locked(mc_ctx *c, TokPending &P)
-{
-    if (P.reads == 0) { P.base_word = -1; P.bases = 0; return MC_OK; }
-    if ((uint64_t)P.base_word != c->rs_bases / 32)  // (the chunks sit behind the store's end until they are counted)
-        return fail(c, MC_ESTATE, "mc_add_reads_file: the context took other reads while a file was being read");
-    int rc = add_reads_dev_locked(c, c->rs_words + P.base_word, P.off.p, P.reads, P.bases, P.base_word);
-    if (!rc) HIPCHK(c, hipStreamSynchronize(c->stream));
-    P.reads = P.bases = 0;
-    P.base_word = -1;
-    return rc;
-}
-
-static int tokenize_chunk_locked(mc_ctx *c, const mch::PlainReadsFile &f, const char *b, const char *e, uint8_t *d_text, uint64_t *n_reads_out,
-                                 bool *declined, TokPending *pend = nullptr)
-{
-    *declined = false;
-    *n_reads_out = 0;
-    const uint64_t n = (uint64_t)(e - b);
-    if (n == 0) return MC_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const bool dbg = c->sw.ingest_debug;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t1 = now();
-    struct { uint8_t *p; } text{d_text};  // (padded with zero bytes to whole tiles of the newline passes: tok_text_bytes)
-    {
-        const uint64_t n_padded = (n + tok::T_TILE - 1) / tok::T_TILE * tok::T_TILE;
-        if (n_padded > n) HIPCHK(c, hipMemsetAsync(text.p + n, 0, n_padded - n, c->stream));
-    }
-    int rc = MC_OK;
-    PoolBuf<uint32_t> flags;
-    HIPCHK(c, flags.alloc(&c->tok_pool, 1));
-    HIPCHK(c, hipMemsetAsync(flags.p, 0, 4, c->stream));
-    // pass 1: newline positions
-    const uint64_t n_tiles = (n + tok::T_TILE - 1) / tok::T_TILE;
-    if (n_tiles > 0x7FFFFFFFull) { *declined = true; return MC_OK; }
-    PoolBuf<uint32_t> tile_counts;
-    PoolBuf<unsigned long long> tile_off, nl;
-    HIPCHK(c, tile_counts.alloc(&c->tok_pool, n_tiles));
-    HIPCHK(c, tile_off.alloc(&c->tok_pool, n_tiles));
-    hipLaunchKernelGGL(tok::k_nl_count, dim3((unsigned)n_tiles), dim3(tok::T_THREADS), 0, c->stream, text.p, tile_counts.p);
-    uint64_t n_nl = 0;
-    rc = tok_scan(c, tile_counts.p, n_tiles, tile_off.p, &n_nl);
-    if (rc) return rc;
-    HIPCHK(c, nl.alloc(&c->tok_pool, n_nl));
-    hipLaunchKernelGGL(tok::k_nl_write, dim3((unsigned)n_tiles), dim3(tok::T_THREADS), 0, c->stream, text.p, tile_off.p, nl.p);
-    HIPCHK(c, hipGetLastError());
-    const uint64_t n_lines = n_nl + (e[-1] != '\n' ? 1 : 0);
-    if (n_lines >= 0xFFFFFFF0ull) { *declined = true; return MC_OK; }
-
-    auto read_flags = [&](uint32_t *out) -> int {
-        HIPCHK(c, hipMemcpyAsync(out, flags.p, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return MC_OK;
-    };
-    // where the packed words go: straight into the read store when the context keeps one
-    PoolBuf<uint64_t> own_words;
-    PoolBuf<uint64_t> offsets;
-    uint64_t *dst = nullptr;
-    int64_t in_store = -1;
-    uint64_t dst_base = 0;  // this chunk's first base in `dst` (deferred counting: behind the chunks before it)
-    uint64_t *off_out = nullptr;
-    const bool defer = pend != nullptr && c->rs_enabled;
-    auto reserve_words = [&](uint64_t total_bases, uint64_t n_reads_chunk) -> int {
-        const uint64_t n_words = (total_bases + 31) / 32 + 1;
-        if (defer) {
-            if (pend->base_word < 0) { pend->base_word = (int64_t)(c->rs_bases / 32); pend->bases = 0; pend->reads = 0; }
-            if ((uint64_t)pend->base_word != c->rs_bases / 32)
-                return fail(c, MC_ESTATE, "mc_add_reads_file: the context took other reads while a file was being read");
-            dst_base = pend->bases;
-            // (the caller reserved the store for the whole file: no reallocation may move the chunks packed so far)
-            if ((uint64_t)pend->base_word + (dst_base + total_bases + 31) / 32 + 2 > c->rs_cap_words)
-                return fail(c, MC_EINVAL, "internal: the read store was not reserved for the whole file");
-            dst = c->rs_words + pend->base_word;
-            in_store = pend->base_word;
-            const uint64_t first_new = (dst_base + 31) / 32;  // words before it hold bases of earlier chunks
-            HIPCHK(c, hipMemsetAsync(dst + first_new, 0, ((dst_base + total_bases + 31) / 32 + 1 - first_new) * 8, c->stream));
-            const uint64_t need = pend->reads + n_reads_chunk + 1;
-            if (need > pend->off_cap) {
-                PoolBuf<uint64_t> bigger;
-                const uint64_t cap = std::max<uint64_t>(need * 2, 1u << 20);
-                HIPCHK(c, bigger.alloc(&c->tok_pool, cap));
-                if (pend->reads) HIPCHK(c, hipMemcpyAsync(bigger.p, pend->off.p, (pend->reads + 1) * 8, hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                std::swap(pend->off.p, bigger.p);
-                std::swap(pend->off.bytes, bigger.bytes);
-                std::swap(pend->off.pool, bigger.pool);
-                pend->off_cap = cap;
-            }
-            off_out = pend->off.p + pend->reads;
-            return MC_OK;
-        }
-        if (c->rs_enabled) {
-            int r = rs_reserve(c, n_words);
-            if (r) return r;
-            in_store = (int64_t)(c->rs_bases / 32);
-            dst = c->rs_words + in_store;
-        } else {
-            HIPCHK(c, own_words.alloc(&c->tok_pool, n_words));
-            dst = own_words.p;
-        }
-        HIPCHK(c, hipMemsetAsync(dst, 0, n_words * 8, c->stream));
-        return MC_OK;
-    };
-    uint64_t n_reads = 0, total_bases = 0;
-    uint32_t fl = 0;
-    if (!f.fastq) {
-        PoolBuf<uint32_t> line_hdr, line_len, keep_len, rec_first, rec_keep;
-        PoolBuf<uint8_t> line_n, rec_n;
-        PoolBuf<unsigned long long> hdr_before, rec_len, out_off, rec_out;
-        HIPCHK(c, line_hdr.alloc(&c->tok_pool, n_lines));
-        HIPCHK(c, line_len.alloc(&c->tok_pool, n_lines));
-        HIPCHK(c, line_n.alloc(&c->tok_pool, n_lines));
-        HIPCHK(c, hdr_before.alloc(&c->tok_pool, n_lines));
-        hipLaunchKernelGGL(tok::k_fa_lines, dim3(grid_for(n_lines, 4, 1 << 14)), dim3(tok::T_THREADS), 0, c->stream, text.p, n, nl.p, n_nl, n_lines, line_hdr.p,
-                           line_len.p, line_n.p, flags.p);
-        uint64_t n_hdr = 0;
-        rc = tok_scan(c, line_hdr.p, n_lines, hdr_before.p, &n_hdr);
-        if (rc) return rc;
-        rc = read_flags(&fl);
-        if (rc) return rc;
-        if (fl) { *declined = true; return MC_OK; }
-        const uint64_t n_rec = n_hdr + 1;  // (record 0: the lines in front of the first header)
-        HIPCHK(c, rec_n.alloc(&c->tok_pool, n_rec));
-        HIPCHK(c, rec_len.alloc(&c->tok_pool, n_rec));
-        HIPCHK(c, rec_first.alloc(&c->tok_pool, n_rec));
-        HIPCHK(c, rec_keep.alloc(&c->tok_pool, n_rec));
-        HIPCHK(c, rec_out.alloc(&c->tok_pool, n_rec));
-        HIPCHK(c, keep_len.alloc(&c->tok_pool, n_lines));
-        HIPCHK(c, out_off.alloc(&c->tok_pool, n_lines));
-        HIPCHK(c, hipMemsetAsync(rec_n.p, 0, n_rec, c->stream));
-        HIPCHK(c, hipMemsetAsync(rec_len.p, 0, n_rec * 8, c->stream));
-        HIPCHK(c, hipMemsetAsync(rec_first.p, 0xFF, n_rec * 4, c->stream));
-        const int g = grid_for(n_lines, 256, 1 << 16);
-        hipLaunchKernelGGL(tok::k_fa_records, dim3(g), dim3(256), 0, c->stream, hdr_before.p, line_hdr.p, line_len.p, line_n.p, n_lines, rec_n.p, rec_len.p,
-                           rec_first.p);
-        hipLaunchKernelGGL(tok::k_fa_keep, dim3(g), dim3(256), 0, c->stream, hdr_before.p, line_hdr.p, line_len.p, n_lines, rec_n.p, keep_len.p);
-        hipLaunchKernelGGL(tok::k_fa_rec_keep, dim3(grid_for(n_rec, 256, 1 << 16)), dim3(256), 0, c->stream, rec_n.p, rec_len.p, n_rec, rec_keep.p);
-        rc = tok_scan(c, keep_len.p, n_lines, out_off.p, &total_bases);
-        if (rc) return rc;
-        rc = tok_scan(c, rec_keep.p, n_rec, rec_out.p, &n_reads);
-        if (rc) return rc;
-        if (n_reads) {
-            rc = reserve_words(total_bases, n_reads);
-            if (rc) return rc;
-            if (!off_out) { HIPCHK(c, offsets.alloc(&c->tok_pool, n_reads + 1)); off_out = offsets.p; }
-            hipLaunchKernelGGL(tok::k_fa_offsets, dim3(grid_for(n_rec, 256, 1 << 16)), dim3(256), 0, c->stream, rec_keep.p, rec_out.p, rec_first.p, out_off.p,
-                               n_rec, n_reads, total_bases, off_out, dst_base);
-            hipLaunchKernelGGL(tok::k_fa_pack, dim3(grid_for(n_lines, 4, 1 << 14)), dim3(tok::T_THREADS), 0, c->stream, text.p, n, nl.p, n_nl,
-                               n_lines, keep_len.p, out_off.p, dst, flags.p, dst_base);
-            HIPCHK(c, hipGetLastError());
-        }
-    } else {
-        if (n_lines % 4) { *declined = true; return MC_OK; }
-        const uint64_t n_rec = n_lines / 4;
-        PoolBuf<uint32_t> rec_pieces, rec_bases;
-        PoolBuf<unsigned long long> piece_at, base_at;
-        HIPCHK(c, rec_pieces.alloc(&c->tok_pool, n_rec));
-        HIPCHK(c, rec_bases.alloc(&c->tok_pool, n_rec));
-        HIPCHK(c, piece_at.alloc(&c->tok_pool, n_rec));
-        HIPCHK(c, base_at.alloc(&c->tok_pool, n_rec));
-        const int g = grid_for(n_rec, 4, 1 << 14);  // a wave per record
-        hipLaunchKernelGGL(tok::k_fq_records, dim3(g), dim3(tok::T_THREADS), 0, c->stream, text.p, n, nl.p, n_nl, n_rec, f.offset, rec_pieces.p, rec_bases.p,
-                           flags.p);
-        rc = tok_scan(c, rec_pieces.p, n_rec, piece_at.p, &n_reads);
-        if (rc) return rc;
-        rc = tok_scan(c, rec_bases.p, n_rec, base_at.p, &total_bases);
-        if (rc) return rc;
-        rc = read_flags(&fl);
-        if (rc) return rc;
-        if (fl) { *declined = true; return MC_OK; }
-        if (n_reads) {
-            rc = reserve_words(total_bases, n_reads);
-            if (rc) return rc;
-            if (!off_out) { HIPCHK(c, offsets.alloc(&c->tok_pool, n_reads + 1)); off_out = offsets.p; }
-            hipLaunchKernelGGL(tok::k_fq_emit, dim3(g), dim3(tok::T_THREADS), 0, c->stream, text.p, n, nl.p, n_nl, n_rec, f.offset, piece_at.p, base_at.p,
-                               rec_bases.p, n_reads, total_bases, off_out, dst, dst_base);
-            HIPCHK(c, hipGetLastError());
-        }
-    }
-    rc = read_flags(&fl);
-    if (rc) return rc;
-    if (fl) { *declined = true; return MC_OK; }  // (cannot happen after the line pass; the read store was not advanced)
-    const double t2 = now();
-    if (n_reads && defer) {  // counted with the rest of the file (tok_flush_locked)
-        pend->reads += n_reads;
-        pend->bases += total_bases;
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // (the text buffer goes back to its pool)
-    } else if (n_reads) {
-        rc = add_reads_dev_locked(c, dst, off_out, n_reads, total_bases, in_store);
-        if (rc) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (dbg)
-        fprintf(stderr, "[ingest] device tokeniser: %.1f MB text, %llu lines, %llu reads, %llu bases: tokenise %.3f s, count %.3f s\n", n / 1e6,
-                (unsigned long long)n_lines, (unsigned long long)n_reads, (unsigned long long)total_bases, t2 - t1, now() - t2);
-    *n_reads_out = n_reads;
-    return MC_OK;
-}
-
-int mc_add_reads_file(mc_ctx *c, const char *path, uint64_t *n_reads)
-{
-    if (!c) return MC_EINVAL;
-    if (n_reads) *n_reads = 0;
-    if (!path) return fail(c, MC_EINVAL, "mc_add_reads_file: null path");
-    try {
-        int rc = MC_OK;
-        auto sink = [&](mch::PackedBatch &b) {
-            if (rc == MC_OK) rc = mc_add_reads_packed(c, b.words.data(), b.offsets.data(), b.n_reads());
-        };
-        // Uncompressed FASTA / FASTQ: the bytes go to the device in chunks cut at record starts and are tokenised there
-        // (csrc/tokenizer.h); a chunk the device declines goes through the host parser, as does any other kind of file
-        // (MC_TOKENIZER=host: every file).  Host batches hold 2^20 reads; the context's lock is taken per batch / chunk.
-        mch::PlainReadsFile f;
-        if (!c->sw.tokenizer_host && mch::map_plain_reads(path, &f)) {
-            // chunks of 256 MB: the bytes of chunk i + 1 cross the link (a helper thread, pinned staging buffers) while
-            // the kernels tokenise and count chunk i
-            const uint64_t chunk = c->sw.tokenizer_chunk_bytes;
-            const bool dbg = c->sw.ingest_debug;
-            auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-            const double t_begin = now();
-            std::vector<std::pair<const char *, const char *>> cuts;
-            for (const char *b = f.p, *end = f.p + f.n; b < end;) {
-                const char *e = (uint64_t)(end - b) <= chunk + chunk / 4 ? end : mch::plain_record_start(f, b + chunk);
-                cuts.emplace_back(b, e);
-                b = e;
-            }
-            struct Upload {
-                PoolBuf<uint8_t> text;
-                std::thread th;
-                bool ok = true;
-            };
-            if (c->rs_enabled) {  // the read store grows once, not chunk by chunk (FASTA: a base a byte at most; FASTQ: half that)
-                std::lock_guard<std::mutex> g(c->mu);
-                HIPCHK(c, hipSetDevice(c->cfg.device));
-                int r = rs_reserve(c, (f.fastq ? f.n / 2 : f.n) / 32 + 2 * cuts.size() + 2);
-                if (r) return r;
-            }
-            std::unique_ptr<Upload> cur, nxt;
-            auto start_upload = [&](size_t i, std::unique_ptr<Upload> &u) -> int {
-                u.reset(new Upload);
-                const uint64_t n = (uint64_t)(cuts[i].second - cuts[i].first);
-                {
-                    std::lock_guard<std::mutex> g(c->mu);
-                    HIPCHK(c, hipSetDevice(c->cfg.device));
-                    HIPCHK(c, u->text.alloc(&c->tok_pool, (n + tok::T_TILE - 1) / tok::T_TILE * tok::T_TILE));
-                }
-                Upload *up = u.get();
-                const char *b = cuts[i].first;
-                up->th = std::thread([c, up, b, n, &f] { up->ok = h2d_pinned(c, up->text.p, b, n, f.fd, (uint64_t)(b - f.p)); });
-                return MC_OK;
-            };
-            auto finish = [&](std::unique_ptr<Upload> &u) {  // (the pool is the context's: blocks go back under its lock)
-                if (!u) return;
-                if (u->th.joinable()) u->th.join();
-                std::lock_guard<std::mutex> g(c->mu);
-                u.reset();
-            };
-            std::unique_ptr<TokPending> pend(new TokPending);  // (its pool block goes back under the context's lock)
-            auto drop_pend = [&] {
-                std::lock_guard<std::mutex> g(c->mu);
-                pend.reset();
-            };
-            uint64_t total = 0;
-            rc = cuts.empty() ? MC_OK : start_upload(0, cur);
-            for (size_t i = 0; i < cuts.size() && rc == MC_OK; i++) {
-                cur->th.join();
-                if (!cur->ok) {
-                    std::lock_guard<std::mutex> g(c->mu);
-                    rc = fail(c, MC_EHIP, "mc_add_reads_file: host-to-device copy failed");
-                    break;
-                }
-                if (i + 1 < cuts.size()) {
-                    rc = start_upload(i + 1, nxt);
-                    if (rc != MC_OK) break;
-                }
-                uint64_t got = 0;
-                bool declined = false;
-                {
-                    std::lock_guard<std::mutex> g(c->mu);
-                    rc = tokenize_chunk_locked(c, f, cuts[i].first, cuts[i].second, cur->text.p, &got, &declined, pend.get());
-                    if (rc == MC_OK && declined) rc = tok_flush_locked(c, *pend);  // (the host's batches are appended behind what is counted)
-                }
-                if (rc != MC_OK) break;
-                if (declined) {
-                    try {
-                        got = mch::parse_plain_range(f, cuts[i].first, cuts[i].second, 1u << 20, sink);
-                    } catch (...) {
-                        finish(cur);
-                        finish(nxt);
-                        drop_pend();
-                        throw;
-                    }
-                    if (rc != MC_OK) break;
-                }
-                total += got;
-                if (i == 0 && cuts.size() > 1) {
-                    // No capacity hint that still holds: the first chunk says how many distinct k-mers a byte of this file
-                    // brings, the file's size says how many chunks follow -- the table goes to its final size now, with one
-                    // chunk's keys to move, instead of being rebuilt every other chunk (10 M reads with 1 % errors in six
-                    // chunks: 110 ms of counting against ~45).  An over-estimate (the later chunks repeat k-mers of the first)
-                    // costs memory, bounded by a third of what the device has free.
-                    std::lock_guard<std::mutex> g(c->mu);
-                    unsigned long long used = 0;
-                    uint32_t fatal = 0;
-                    rc = read_counters(c, &used, &fatal);
-                    if (rc != MC_OK) break;
-                    const bool hint_holds = c->cfg.capacity_hint && used < c->cfg.capacity_hint;
-                    if (!hint_holds && used) {
-                        const double scale = (double)f.n / (double)(cuts[0].second - cuts[0].first);
-                        const double load = c->mm_k ? 0.36 : 0.6;
-                        size_t fr = 0, tot = 0;
-                        if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
-                        uint64_t want_slots = (uint64_t)((double)used * scale / load);
-                        want_slots = std::min<uint64_t>(want_slots, fr / 3 / sizeof(Slot));
-                        const uint64_t want = regions_for(c, want_slots);
-                        if (want > c->n_regions && want_slots > c->n_slots()) {
-                            if (dbg) fprintf(stderr, "[ingest] %llu distinct k-mers after %.0f MB of %.0f MB: table to %.1f GB\n", used,
-                                             (cuts[0].second - cuts[0].first) / 1e6, f.n / 1e6, (double)(want << c->sb) * sizeof(Slot) / 1e9);
-                            rc = table_grow(c, want);
-                            if (rc != MC_OK) break;
-                            c->solid_list_fresh = false;
-                        }
-                    }
-                }
-                finish(cur);
-                cur = std::move(nxt);
-            }
-            finish(cur);
-            finish(nxt);
-            if (rc == MC_OK) {
-                std::lock_guard<std::mutex> g(c->mu);
-                rc = tok_flush_locked(c, *pend);
-            }
-            drop_pend();
-            if (rc != MC_OK) return rc;
-            if (dbg) fprintf(stderr, "[ingest] device tokeniser: %zu chunk(s), %.1f MB in %.3f s\n", cuts.size(), f.n / 1e6, now() - t_begin);
-            if (n_reads) *n_reads = total;
-            return MC_OK;
-        }
-        const uint64_t n = mch::load_reads_file(path, 1u << 20, sink);
-        if (rc != MC_OK) return rc;
-        if (n_reads) *n_reads = n;
-        return MC_OK;
-    } catch (const mch::Error &e) {
-        std::lock_guard<std::mutex> g(c->mu);
-        return fail(c, MC_EINVAL, "%s", e.what());
-    } catch (const std::bad_alloc &) {
-        std::lock_guard<std::mutex> g(c->mu);
-        return fail(c, MC_ENOMEM, "mc_add_reads_file: out of host memory");
-    }
 }
 
 int mc_finalize_counts(mc_ctx *c, uint64_t *n_distinct)
@@ -4384,101 +3508,11 @@ int mc_synth_genome(uint64_t gseed, uint64_t start, uint64_t n, uint8_t *codes)
     return MC_OK;
 }
 
-// ------------------------------------------------------------------------------------------ BFS driver
+}  // extern "C"
 
-// The arrays of a BFS result are page-locked host memory from a process-wide pool (a block serves again once
-// mc_bfs_result_free has returned it): the copies from the device run at the link rate without a staging pass, and a
-// reused block costs no page faults -- 0.4 ms of a 29 ms step for two passes of 10^5 k-mers.  A 64-byte header in front
-// of every array says what it is; pageable memory takes over when page-locked memory cannot be had.
-namespace {
-struct ResHeader {
-    uint64_t kind;   // 1: page-locked block of the pool, 2: malloc
-    uint64_t bytes;  // of the whole block
-    uint64_t pad[6];
-};
-static_assert(sizeof(ResHeader) == 64, "arrays stay 64-byte aligned");
-struct ResPool {
-    std::mutex mu;
-    std::vector<std::pair<void *, size_t>> idle;
-    size_t idle_bytes = 0;
-} g_res_pool;
-
-void *res_alloc(size_t bytes)
-{
-    size_t want = 64 + std::max<size_t>(bytes, 1);
-    want = (want + 4095) / 4096 * 4096;
-    void *blk = nullptr;
-    size_t got = 0;
-    {
-        std::lock_guard<std::mutex> g(g_res_pool.mu);
-        size_t best = g_res_pool.idle.size();
-        for (size_t i = 0; i < g_res_pool.idle.size(); i++) {
-            const size_t b = g_res_pool.idle[i].second;
-            if (b >= want && b <= 2 * want + (64u << 10) && (best == g_res_pool.idle.size() || b < g_res_pool.idle[best].second)) best = i;
-        }
-        if (best < g_res_pool.idle.size()) {
-            blk = g_res_pool.idle[best].first;
-            got = g_res_pool.idle[best].second;
-            g_res_pool.idle_bytes -= got;
-            g_res_pool.idle.erase(g_res_pool.idle.begin() + (long)best);
-        }
-    }
-    uint64_t kind = 1;
-    if (!blk) {
-        got = want;
-        if (hipHostMalloc(&blk, got) != hipSuccess) {
-            (void)hipGetLastError();
-            blk = malloc(got);
-            kind = 2;
-            if (!blk) return nullptr;
-        }
-    }
-    ResHeader *h = static_cast<ResHeader *>(blk);
-    h->kind = kind;
-    h->bytes = got;
-    return static_cast<char *>(blk) + 64;
-}
-
-void res_free(void *p)
-{
-    if (!p) return;
-    ResHeader *h = reinterpret_cast<ResHeader *>(static_cast<char *>(p) - 64);
-    if (h->kind == 2) { free(h); return; }
-    std::lock_guard<std::mutex> g(g_res_pool.mu);
-    if (g_res_pool.idle.size() >= 64 || g_res_pool.idle_bytes + h->bytes > (512u << 20)) {
-        (void)hipHostFree(h);
-        return;
-    }
-    g_res_pool.idle_bytes += h->bytes;
-    g_res_pool.idle.emplace_back(h, (size_t)h->bytes);
-}
-}  // namespace
-
-void mc_bfs_result_free(mc_bfs_result *r)
-{
-    if (!r) return;
-    res_free(r->hi);  // (one block holds all five arrays: mc_bfs_batch)
-    memset(r, 0, sizeof *r);
-}
+// ------------------------------------------------------------------------------------------ the walk's solid table and its checks
 
 namespace {
-
-int bfs_alloc(mc_ctx *c, BfsState &S, uint64_t dcap)
-{
-    S.dcap = dcap;
-    uint64_t vcap = 1024;
-    while (vcap < 4 * dcap) vcap <<= 1;
-    S.bmask = vcap / 2 - 1;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.hi), dcap * 8));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.lo), dcap * 8));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.dist), dcap * 4));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.cov), dcap * 2));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.flags), dcap * 4));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.vis), vcap * 8));
-    HIPCHK(c, hipMemsetAsync(S.vis, 0xFF, vcap * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(S.flags, 0, dcap * 4, c->stream));
-    return MC_OK;
-}
 
 struct PairSource { const int64_t *keys; const int16_t *counts; const uint32_t *hints; uint64_t n; };
 
@@ -4571,6 +3605,8 @@ int solid_build(mc_ctx *c, uint64_t n, int min_cov, double *ms, const PairSource
     return MC_OK;
 }
 
+}  // namespace
+
 // Builds (or reuses) the solid table for this threshold.
 int ensure_solid(mc_ctx *c, int min_cov, double *ms)
 {
@@ -4606,195 +3642,6 @@ int ensure_solid(mc_ctx *c, int min_cov, double *ms)
     HIPCHK(c, hipMemcpy(&n, cursor, sizeof n, hipMemcpyDeviceToHost));
     return solid_build(c, n, min_cov, ms, nullptr, from_list);
 }
-
-// What mc_bfs_batch used to do with 4 fills per job before the launch and 5 + 2 copies per job behind it (each a
-// launch of its own, 10-25 us apart: 0.7 ms of a 9 ms walk on two jobs) is one kernel either side.
-// k_bfs_reset: blockIdx.y = job.  full: index emptied, flags and control block cleared (a fresh run); always: the mailbox.
-__global__ void __launch_bounds__(256) k_bfs_reset(const BfsState *__restrict__ states, int full)
-{
-    const BfsState S = states[blockIdx.y];
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x, stride = (uint64_t)gridDim.x * 256;
-    if (full) {
-        uint4 *vis = reinterpret_cast<uint4 *>(S.vis);  // (bmask + 1 buckets of 16 bytes)
-        for (uint64_t i = t; i <= S.bmask; i += stride) vis[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
-        for (uint64_t i = t; i < S.dcap; i += stride) S.flags[i] = 0;
-        uint32_t *ctl = reinterpret_cast<uint32_t *>(S.ctl);
-        for (uint64_t i = t; i < sizeof(BfsCtl) / 4; i += stride) ctl[i] = 0;
-    }
-    if (S.box) {
-        uint32_t *box = reinterpret_cast<uint32_t *>(S.box);
-        for (uint64_t i = t; i < sizeof(ScoutBox) / 4; i += stride) box[i] = 0;
-    }
-}
-
-// the header of a job's packed results
-struct BfsPackHdr {
-    BfsCtl ctl;
-    ScoutBox box;
-    unsigned long long offset;  // of the job's arrays in the data block: hi[n] lo[n] dist[n] cov[n] last[n], each padded to 8 bytes
-    unsigned long long levels;  // max distance
-};
-__host__ __device__ inline uint64_t bfs_pack_bytes(uint64_t n) { return 16 * n + ((4 * n + 7) & ~7ull) + ((2 * n + 7) & ~7ull) + ((n + 7) & ~7ull); }
-
-// k_bfs_pack: blockIdx.y = job.  Control block and mailbox into the job's header, its arrays (the first ctl.n entries)
-// into the data block behind the arrays of the jobs before it; `last` from bit 0 of the flags; the largest distance.
-__global__ void __launch_bounds__(256) k_bfs_pack(const BfsState *__restrict__ states, uint32_t n_jobs, BfsPackHdr *hdr, char *data, uint64_t data_cap)
-{
-    (void)n_jobs;
-    const uint32_t j = blockIdx.y;
-    const BfsState S = states[j];
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x, stride = (uint64_t)gridDim.x * 256;
-    unsigned long long off = 0;
-    for (uint32_t i = 0; i < j; i++) off += bfs_pack_bytes(ctl_ld(&states[i].ctl->n));
-    const uint64_t n = ctl_ld(&S.ctl->n);
-    if (blockIdx.x == 0) {
-        uint32_t *h = reinterpret_cast<uint32_t *>(&hdr[j]);
-        const uint32_t *ctl = reinterpret_cast<const uint32_t *>(S.ctl), *box = reinterpret_cast<const uint32_t *>(S.box);
-        for (uint32_t i = threadIdx.x; i < sizeof(BfsCtl) / 4; i += 256) h[i] = __hip_atomic_load(&ctl[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (uint32_t i = threadIdx.x; i < sizeof(ScoutBox) / 4; i += 256)
-            h[sizeof(BfsCtl) / 4 + i] = box ? __hip_atomic_load(&box[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        if (threadIdx.x == 0) hdr[j].offset = off;
-    }
-    if (off + bfs_pack_bytes(n) > data_cap) return;  // (the host sizes the block from the jobs' capacities: cannot happen)
-    uint64_t *hi = reinterpret_cast<uint64_t *>(data + off), *lo = hi + n;
-    int32_t *dist = reinterpret_cast<int32_t *>(lo + n);
-    int16_t *cov = reinterpret_cast<int16_t *>(reinterpret_cast<char *>(dist) + ((4 * n + 7) & ~7ull));
-    uint8_t *last = reinterpret_cast<uint8_t *>(reinterpret_cast<char *>(cov) + ((2 * n + 7) & ~7ull));
-    unsigned long long mx = 0;
-    for (uint64_t i = t; i < n; i += stride) {
-        hi[i] = S.hi[i];
-        lo[i] = S.lo[i];
-        const int32_t d = S.dist[i];
-        dist[i] = d;
-        cov[i] = S.cov[i];
-        last[i] = (uint8_t)(S.flags[i] & 1u);
-        mx = max(mx, (unsigned long long)(uint32_t)d);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned long long)__shfl_down(mx, o));
-    if ((threadIdx.x & 63) == 0 && mx) atomicMax(&hdr[j].levels, mx);
-}
-
-// MC_BFS_SELFCHECK: the finished walks of a batch against the invariants of k_bfs_check; *report names what was found
-int bfs_selfcheck(mc_ctx *c, uint32_t n_jobs, const std::vector<BfsCtl> &ctl, int min_cov, int64_t max_kmers, int64_t max_radius,
-                  std::string *report)
-{
-    const SolidView t = c->solid_view();
-    BfsCheck *d_out = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d_out), sizeof(BfsCheck)));
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        const BfsState &S = c->bfs_pool[j]->S;
-        const uint64_t n = ctl[j].n;
-        if (n == 0) continue;
-        uint64_t cap = 1024;
-        while (cap < 4 * n) cap <<= 1;
-        uint32_t *d_set = nullptr;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d_set), cap * 4));
-        HIPCHK(c, hipMemsetAsync(d_set, 0xFF, cap * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(d_out, 0, sizeof(BfsCheck), c->stream));
-        const unsigned grid = (unsigned)std::min<uint64_t>(grid_for(n, 256), 4096);
-        hipLaunchKernelGGL(k_bfs_check_index, dim3(grid), dim3(256), 0, c->stream, S, n, d_set, (uint32_t)(cap - 1), d_out);
-        switch (c->cfg.key_mode) {
-        case MC_KEY_PACKED:
-            hipLaunchKernelGGL(k_bfs_check<KEY_PACKED>, dim3(grid), dim3(256), 0, c->stream, S, n, t, c->cfg.k, min_cov, (long long)max_kmers,
-                               (long long)max_radius, d_set, (uint32_t)(cap - 1), d_out);
-            break;
-        case MC_KEY_POLY:
-            hipLaunchKernelGGL(k_bfs_check<KEY_POLY>, dim3(grid), dim3(256), 0, c->stream, S, n, t, c->cfg.k, min_cov, (long long)max_kmers,
-                               (long long)max_radius, d_set, (uint32_t)(cap - 1), d_out);
-            break;
-        default:
-            hipLaunchKernelGGL(k_bfs_check<KEY_FNV1A>, dim3(grid), dim3(256), 0, c->stream, S, n, t, c->cfg.k, min_cov, (long long)max_kmers,
-                               (long long)max_radius, d_set, (uint32_t)(cap - 1), d_out);
-        }
-        HIPCHK(c, hipGetLastError());
-        BfsCheck h;
-        HIPCHK(c, hipMemcpyAsync(&h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(d_set);
-        if (h.dup | h.cov | h.order | h.orphan | h.open) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "job %u (dir %d, n %llu): %llu duplicate, %llu wrong coverage, %llu out of order, %llu without parent, %llu solid neighbours left out;",
-                     j, S.dir, (unsigned long long)n, h.dup, h.cov, h.order, h.orphan, h.open);
-            *report += buf;
-            static const char *kind[] = {"?", "dup", "cov", "order", "orphan", "open"};
-            for (uint32_t i = 0; i < std::min<uint32_t>(h.n_first, 16); i++) {
-                snprintf(buf, sizeof buf, " [%s entry %u other %u dist %u]", kind[std::min<uint32_t>(h.first[i][0], 5)], h.first[i][1], h.first[i][2], h.first[i][3]);
-                *report += buf;
-            }
-        }
-    }
-    (void)hipFree(d_out);
-    return MC_OK;
-}
-
-// the rounds' trace of every job (MC_BFS_TRACE builds; nothing otherwise), oldest record first, as text
-void bfs_trace_dump(mc_ctx *c, uint32_t n_jobs, const std::vector<BfsCtl> &ctl, const char *path, const std::string &why)
-{
-    FILE *f = fopen(path, "a");
-    if (!f) return;
-    if (!why.empty()) fprintf(f, "# %s\n", why.c_str());
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        const BfsState &S = c->bfs_pool[j]->S;
-        fprintf(f, "# job %u dir %d n %llu level %lld status %d rounds_narrow %llu slow %llu trace records %llu\n", j, S.dir, ctl[j].n, ctl[j].level, ctl[j].status,
-                ctl[j].rounds_narrow, ctl[j].rounds_slow, ctl[j].trace_n);
-        if (!S.trace || !ctl[j].trace_n) continue;
-        std::vector<uint32_t> ring((size_t)BFS_TRACE_RECORDS * 8);
-        if (hipMemcpy(ring.data(), S.trace, ring.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) continue;
-        const unsigned long long tn = ctl[j].trace_n, first = tn > BFS_TRACE_RECORDS ? tn - BFS_TRACE_RECORDS : 0;
-        for (unsigned long long r = first; r < tn; r++) {
-            const uint32_t *w = &ring[(size_t)(r & (BFS_TRACE_RECORDS - 1)) * 8];
-            const uint32_t kind = w[0] >> 24;
-            if (kind == 8)
-                fprintf(f, "%llu companion seq %u F %u team %u stopped %u levels %u %u budget %u stuck %u %u iters %u\n", r, w[0] & 0xFFFFFF, w[1] & 0xFF, (w[1] >> 8) & 0xFF,
-                        (w[1] >> 16) & 1, w[2], w[3], w[4], w[5] & 0xFF, (w[5] >> 8) & 0xFF, w[6]);
-            else
-                fprintf(f, "%llu %s round %u n %u F %u H %u %s %u force_slow %u comp %u level %u pend %u %s %u seq %u open %u resp %08x %s %u %u\n", r,
-                        kind == 1 ? "fast" : kind == 2 ? "slow" : "root_bad", w[0] & 0xFFFFFF, w[1], w[2] & 0xFF, (w[2] >> 8) & 0xFF, kind == 2 ? "n_new" : "J", (w[2] >> 16) & 0xFF,
-                        (w[2] >> 24) & 1, (w[2] >> 25) & 1, w[3], w[4] & 0xFFFF, kind == 2 ? "F_next" : "bad_lvl", w[4] >> 16, w[5] & 0x7FFFFFFF, w[5] >> 31, w[6],
-                        kind == 2 ? "n_after" : "plen0/ppos0", kind == 2 ? w[7] : w[7] & 0xFFFF, kind == 2 ? 0u : w[7] >> 16);
-        }
-    }
-    fclose(f);
-}
-
-void launch_bfs(mc_ctx *c, hipStream_t stream, const BfsState *d_states, uint32_t n_jobs, int min_cov, int64_t max_kmers,
-                int64_t max_radius, unsigned long long max_rounds, int companions)
-{
-    const SolidView t = c->solid_view();
-    // companions: the scouts' kernel beside the walk's, on the side stream -- behind what the main stream has enqueued so far (the
-    // mailboxes' reset), and the main stream takes nothing up behind the walk before the scouts have left (they leave when the walk
-    // sets `quit`, which it does on every way out)
-    hipStream_t side = companions && c->pipe_stream ? c->pipe_stream : nullptr;
-    if (companions && !side) companions = 0;
-    if (side) {
-        if (hipEventRecord(c->ev_piece[0], stream) != hipSuccess || hipStreamWaitEvent(side, c->ev_piece[0], 0) != hipSuccess) { side = nullptr; companions = 0; }
-    }
-    // (SH: the walk over several ranks' tables, every look-up through its key's owner; the one-table kernel carries none of that)
-#define BFS_LAUNCH(MODE)                                                                                                          \
-    do {                                                                                                                          \
-        if (t.n_shards > 1) {                                                                                                     \
-            if (side) hipLaunchKernelGGL((k_bfs_scout<MODE, true>), dim3(n_jobs), dim3(BFS_THREADS), 0, side, d_states, t, c->cfg.k, min_cov); \
-            hipLaunchKernelGGL((k_bfs<MODE, true>), dim3(n_jobs), dim3(BFS_THREADS), 0, stream, d_states, t, c->cfg.k, min_cov,    \
-                               (long long)max_kmers, (long long)max_radius, max_rounds, companions);                              \
-        } else {                                                                                                                  \
-            if (side) hipLaunchKernelGGL((k_bfs_scout<MODE, false>), dim3(n_jobs), dim3(BFS_THREADS), 0, side, d_states, t, c->cfg.k, min_cov); \
-            hipLaunchKernelGGL((k_bfs<MODE, false>), dim3(n_jobs), dim3(BFS_THREADS), 0, stream, d_states, t, c->cfg.k, min_cov,   \
-                               (long long)max_kmers, (long long)max_radius, max_rounds, companions);                              \
-        }                                                                                                                         \
-    } while (0)
-    switch (c->cfg.key_mode) {
-    case MC_KEY_PACKED: BFS_LAUNCH(KEY_PACKED); break;
-    case MC_KEY_POLY: BFS_LAUNCH(KEY_POLY); break;
-    default: BFS_LAUNCH(KEY_FNV1A);
-    }
-#undef BFS_LAUNCH
-    if (side) {
-        (void)hipEventRecord(c->ev_piece[1], side);
-        (void)hipStreamWaitEvent(stream, c->ev_piece[1], 0);
-    }
-}
-
 
 // After a walk over a table of hash keys in minimizer bins: every look-up of it that came back "absent" is asked again by key
 // (dup_check.h, "Look-ups of k-mers that were never counted").  *redo: a key turned up that a string nobody counted had asked for;
@@ -4876,10 +3723,8 @@ int phantom_verify(mc_ctx *c, uint32_t n_jobs, std::vector<std::unique_ptr<BfsJo
     return MC_OK;
 }
 
-}  // namespace
-
-int mc_solid_from_pairs_dev(mc_ctx *c, const int64_t *d_keys, const int16_t *d_counts, const uint32_t *d_hints, uint64_t n,
-                            int min_cov, uint64_t *n_solid)
+extern "C" int mc_solid_from_pairs_dev(mc_ctx *c, const int64_t *d_keys, const int16_t *d_counts, const uint32_t *d_hints, uint64_t n,
+                                       int min_cov, uint64_t *n_solid)
 {
     if (!c) return MC_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
@@ -4911,1186 +3756,3 @@ int mc_solid_from_pairs_dev(mc_ctx *c, const int64_t *d_keys, const int16_t *d_c
     return MC_OK;
 }
 
-int mc_bfs_batch(mc_ctx *c, const mc_bfs_job *jobs, uint32_t n_jobs, int min_cov, int64_t max_kmers,
-                 int64_t max_radius, mc_bfs_result *out)
-{
-    if (!c) return MC_EINVAL;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!out || !jobs || n_jobs == 0) return fail(c, MC_EINVAL, "mc_bfs: null argument");
-    memset(out, 0, sizeof(mc_bfs_result) * n_jobs);
-    if (!c->finalized) return fail(c, MC_ESTATE, "mc_bfs: call mc_finalize_counts first");
-    if (c->shards_dropped)
-        return fail(c, MC_ESTATE, "mc_bfs: the table changed after mc_shard_attach, which dropped the attachment: export and attach the ranks' tables again (or mc_shard_detach to walk this table alone)");
-    if (max_kmers < 0 && max_radius < 0)
-        return fail(c, MC_EINVAL, "At least one of --maxkmers and --maxradius parameters should be set");
-    if (min_cov < 0)
-        return fail(c, MC_EINVAL, "mc_bfs: negative coverage threshold (absent k-mers read as -1 and would pass)");
-    if (n_jobs > 4096) return fail(c, MC_EINVAL, "mc_bfs: too many jobs in one batch");
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        if (jobs[j].dir < -1 || jobs[j].dir > 1) return fail(c, MC_EINVAL, "mc_bfs: dir must be -1, 0 or +1");
-        if (jobs[j].n_seeds && !jobs[j].seed_lo) return fail(c, MC_EINVAL, "mc_bfs: seed_lo is null");
-        if (c->cfg.k > 32 && jobs[j].n_seeds && !jobs[j].seed_hi)
-            return fail(c, MC_EINVAL, "mc_bfs: seed_hi is null with k > 32");
-        if (max_kmers >= (int64_t)0x3FFFF000ll || jobs[j].n_seeds >= 0x3FFFF000ull)
-            return fail(c, MC_EINVAL, "mc_bfs: more than 2^30 vertices requested");
-    }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    double total_ms = c->pending_solid_ms;
-    c->pending_solid_ms = 0;
-    {
-        int rc = ensure_solid(c, min_cov, &total_ms);
-        // (hash keys in minimizer bins: the join of mc_finalize_counts, should anything have skipped it)
-        if (!rc && hash_bins(c) && c->solid_is_table && !c->d_shards && dup_check_on() && !c->dup.checked) {
-            c->dup.l1_armed = false;
-            rc = ensure_dups(c);
-            if (!rc) rc = ensure_solid(c, min_cov, &total_ms);
-        }
-        if (rc) return rc;
-    }
-
-    while (c->bfs_pool.size() < n_jobs) c->bfs_pool.emplace_back(new BfsJobBuffers);
-    auto &B = c->bfs_pool;
-    // ---- one upload: the job states, then every job's seeds (lo, hi)
-    uint64_t stage_bytes = ((uint64_t)n_jobs * sizeof(BfsState) + 63) & ~63ull, pack_bytes = 0;
-    std::vector<uint64_t> seed_at(n_jobs);
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        seed_at[j] = stage_bytes;
-        stage_bytes += 2 * std::max<uint64_t>(jobs[j].n_seeds, 1) * 8;
-    }
-    if (c->bfs_stage_cap < stage_bytes) {
-        if (c->h_bfs_stage) (void)hipHostFree(c->h_bfs_stage);
-        if (c->d_bfs_stage) (void)hipFree(c->d_bfs_stage);
-        c->h_bfs_stage = c->d_bfs_stage = nullptr;
-        c->bfs_stage_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(stage_bytes * 2, 1u << 16);
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_bfs_stage), cap, hipHostMallocDefault));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_bfs_stage), cap));
-        c->bfs_stage_cap = cap;
-    }
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        BfsJobBuffers &J = *B[j];
-        BfsState &S = J.S;
-        const uint64_t ns = jobs[j].n_seeds;
-        uint64_t *h_lo = reinterpret_cast<uint64_t *>(c->h_bfs_stage + seed_at[j]), *h_hi = h_lo + std::max<uint64_t>(ns, 1);
-        if (ns) memcpy(h_lo, jobs[j].seed_lo, ns * 8);
-        if (ns && jobs[j].seed_hi) memcpy(h_hi, jobs[j].seed_hi, ns * 8);
-        const uint64_t dcap = max_kmers >= 0 ? std::max<uint64_t>((uint64_t)max_kmers, ns) + 2 * BFS_THREADS
-                                             : std::max<uint64_t>(1ull << 20, ns + 2 * BFS_THREADS);
-        if (S.dcap < dcap || S.dcap > 4 * dcap || !S.hi) {
-            J.free_arrays();
-            int rc = bfs_alloc(c, S, dcap);
-            if (rc) return rc;
-        }  // (reused arrays: k_bfs_reset empties the index and clears the flags)
-        if (!S.ctl) HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.ctl), sizeof(BfsCtl)));
-        if (!S.path) HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.path), (size_t)SCOUT_MAX_F * PATH_WORDS * 8));
-        if (!S.box) HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.box), sizeof(ScoutBox)));
-#ifdef MC_BFS_TRACE
-        if (!S.trace) HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&S.trace), (size_t)BFS_TRACE_RECORDS * 32));
-#endif
-        uint64_t *d_lo = reinterpret_cast<uint64_t *>(c->d_bfs_stage + seed_at[j]);
-        S.seed_hi = jobs[j].seed_hi ? d_lo + std::max<uint64_t>(ns, 1) : nullptr;
-        S.seed_lo = d_lo;
-        S.n_seeds = ns;
-        S.dir = jobs[j].dir;
-    }
-    BfsState *const d_states = reinterpret_cast<BfsState *>(c->d_bfs_stage);
-    BfsState *const h_states = reinterpret_cast<BfsState *>(c->h_bfs_stage);
-    std::vector<BfsCtl> ctl(n_jobs);
-    const unsigned long long max_rounds = 1ull << 17;  // bounds one launch; unfinished jobs are relaunched
-    std::vector<std::array<unsigned long long, 4>> box_e(n_jobs, std::array<unsigned long long, 4>{0, 0, 0, 0});
-    std::vector<unsigned long long> box_iters(n_jobs, 0), box_hops(n_jobs, 0), box_levels(n_jobs, 0), box_calls(n_jobs, 0), box_nf(n_jobs, 0), box_m0(n_jobs, 0);
-    const uint64_t hdr_bytes = (uint64_t)n_jobs * sizeof(BfsPackHdr);
-    BfsPackHdr *h_hdr = nullptr;
-    for (int pass = 0;; pass++) {  // (a pass more where the check of the walk's look-ups by key gave the table a slot: phantom_verify)
-    for (int launch = 0;; launch++) {
-        for (uint32_t j = 0; j < n_jobs; j++) h_states[j] = B[j]->S;
-        // (first launch: states and seeds; later ones, after a job's arrays grew: the states)
-        HIPCHK(c, hipMemcpyAsync(c->d_bfs_stage, c->h_bfs_stage, launch == 0 ? stage_bytes : (uint64_t)n_jobs * sizeof(BfsState), hipMemcpyHostToDevice, c->stream));
-        // Few jobs: each gets a second workgroup that scouts ahead while the first verifies (bfs_device.h ScoutBox).  The
-        // pair must be on the chip together to gain anything (it is correct either way), so not for large batches.
-        const int companions = c->sw.bfs_companion && n_jobs <= 64 && c->solid_view().reads != nullptr ? 1 : 0;
-        hipLaunchKernelGGL(k_bfs_reset, dim3(n_jobs <= 8 ? 64 : 8, n_jobs), dim3(256), 0, c->stream, d_states, launch == 0 ? 1 : 0);
-        HIPCHK(c, hipGetLastError());
-        pack_bytes = 0;
-        for (uint32_t j = 0; j < n_jobs; j++) pack_bytes += bfs_pack_bytes(B[j]->S.dcap);
-        if (c->bfs_pack_cap < hdr_bytes + pack_bytes) {
-            if (c->d_bfs_pack) (void)hipFree(c->d_bfs_pack);
-            c->d_bfs_pack = nullptr;
-            c->bfs_pack_cap = 0;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->d_bfs_pack), hdr_bytes + pack_bytes));
-            c->bfs_pack_cap = hdr_bytes + pack_bytes;
-        }
-        if (c->bfs_hdr_cap < hdr_bytes) {
-            if (c->h_bfs_hdr) (void)hipHostFree(c->h_bfs_hdr);
-            c->h_bfs_hdr = nullptr;
-            c->bfs_hdr_cap = 0;
-            HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_bfs_hdr), hdr_bytes * 2, hipHostMallocDefault));
-            c->bfs_hdr_cap = hdr_bytes * 2;
-        }
-        // (the walk, the packing of its results and the copy of their headers are enqueued together: one wait)
-        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-        launch_bfs(c, c->stream, d_states, n_jobs, min_cov, max_kmers, max_radius, max_rounds, companions);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-        int rc;
-        // ---- the results packed on the device: headers (control block, mailbox, offset, levels), then the jobs' arrays
-        h_hdr = reinterpret_cast<BfsPackHdr *>(c->h_bfs_hdr);
-        HIPCHK(c, hipMemsetAsync(c->d_bfs_pack, 0, hdr_bytes, c->stream));
-        hipLaunchKernelGGL(k_bfs_pack, dim3(n_jobs <= 8 ? 64 : 8, n_jobs), dim3(256), 0, c->stream, d_states, n_jobs,
-                           reinterpret_cast<BfsPackHdr *>(c->d_bfs_pack), c->d_bfs_pack + hdr_bytes, pack_bytes);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h_hdr, c->d_bfs_pack, hdr_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        {
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            total_ms += ms;
-        }
-        for (uint32_t j = 0; j < n_jobs; j++) {
-            ctl[j] = h_hdr[j].ctl;
-            if (!companions) continue;
-            const ScoutBox &hb = h_hdr[j].box;
-            box_iters[j] += hb.iters; box_e[j][0] += hb.e_stuck; box_e[j][1] += hb.e_nc0; box_e[j][2] += hb.e_budget; box_e[j][3] += hb.e_stop; box_hops[j] += hb.hops; box_levels[j] += hb.levels; box_calls[j] += hb.calls; box_nf[j] += hb.nf; box_m0[j] += hb.m0;
-        }
-        bool all_done = true;
-        for (uint32_t j = 0; j < n_jobs; j++) {
-            if (ctl[j].status == BFS_DONE) continue;
-            all_done = false;
-            if (ctl[j].status != BFS_NEED_GROW) continue;
-            // grow distanceToKmer and its index (only reachable without --maxkmers)
-            BfsState &S = B[j]->S;
-            BfsState N = S;
-            N.hi = N.lo = nullptr; N.dist = nullptr; N.cov = nullptr; N.flags = nullptr; N.vis = nullptr;  // (ctl and path stay)
-            rc = bfs_alloc(c, N, S.dcap * 2);
-            if (rc) return rc;
-            const uint64_t n = ctl[j].n;
-            HIPCHK(c, hipMemcpyAsync(N.hi, S.hi, n * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(N.lo, S.lo, n * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(N.dist, S.dist, n * 4, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(N.cov, S.cov, n * 2, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(N.flags, S.flags, n * 4, hipMemcpyDeviceToDevice, c->stream));
-            if (n) {
-                hipLaunchKernelGGL(k_vis_rebuild, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, N, n);
-                HIPCHK(c, hipGetLastError());
-            }
-            const int running = BFS_RUNNING;
-            HIPCHK(c, hipMemcpyAsync(&S.ctl->status, &running, sizeof running, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            B[j]->free_arrays();
-            S = N;
-        }
-        if (all_done) break;
-    }
-    bool redo = false;
-    if (int vrc = phantom_verify(c, n_jobs, B, ctl, &redo)) return vrc;
-    if (!redo) break;
-    if (pass >= 8) return fail(c, MC_EOVERFLOW, "mc_bfs: the walk keeps finding keys that strings nobody counted ask for");
-    }
-
-    int ret = MC_OK;
-    {   // debug: every walk checked on the device (bfs_device.h k_bfs_check); the rounds' trace of a tuning build written out
-        const std::string &dump = c->sw.bfs_trace_dump;
-        std::string report;
-        if (c->sw.bfs_selfcheck) {
-            int rc = bfs_selfcheck(c, n_jobs, ctl, min_cov, max_kmers, max_radius, &report);
-            if (rc) return rc;
-        }
-        if (!report.empty() || !dump.empty()) bfs_trace_dump(c, n_jobs, ctl, dump.empty() ? "/dev/stderr" : dump.c_str(), report);
-        if (!report.empty()) return fail(c, MC_ECHECK, "mc_bfs: self-check failed: %s", report.c_str());
-    }
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        const uint64_t n = ctl[j].n;
-        mc_bfs_result *o = &out[j];
-        o->lookups = ctl[j].lookups;
-        // (a scout hop: the read, then its k-mers; the members of a companion's team hop side by side)
-        o->rounds = ctl[j].rounds_narrow + ctl[j].chunks_wide + 2 * (ctl[j].scout_hops + box_iters[j]);
-        o->device_ms = total_ms;
-        {
-            const bool stats = c->sw.bfs_stats;
-            if (stats) fprintf(stderr, "[bfs job %u] slow rounds: after a partly verified round %llu, first level mismatch %llu, nothing predicted %llu; companion runs ended: stuck %llu, no candidates %llu, budget %llu, aborted %llu\n",
-                               j, ctl[j].slow_forced, ctl[j].slow_mismatch, ctl[j].slow_starved, box_e[j][0], box_e[j][1], box_e[j][2], box_e[j][3]);
-            if (stats)
-                fprintf(stderr, "[bfs job %u] n=%llu level=%lld rounds_narrow=%llu (slow %llu) chunks_wide=%llu scout calls=%llu hops=%llu (team hops %llu) levels=%llu notfound=%llu m0=%llu lookups=%llu\n", j,
-                        ctl[j].n, ctl[j].level, ctl[j].rounds_narrow, ctl[j].rounds_slow, ctl[j].chunks_wide, ctl[j].scout_calls + box_calls[j], ctl[j].scout_hops + box_hops[j], box_iters[j],
-                        ctl[j].scout_levels + box_levels[j], ctl[j].scout_nf + box_nf[j], ctl[j].scout_m0 + box_m0[j], ctl[j].lookups);
-        }
-#ifdef MC_BFS_TIMING
-        {
-            const double r_ = 0.01 / std::max(1ull, ctl[j].rounds_narrow);
-            fprintf(stderr, "[bfs job %u] rounds_narrow=%llu (slow %llu) chunks_wide=%llu levels~%lld  us/round: gen+issue %.2f table %.2f vis+check %.2f accept %.2f publish %.2f (%.2f %.2f)\n",
-                    j, ctl[j].rounds_narrow, ctl[j].rounds_slow, ctl[j].chunks_wide, ctl[j].level, ctl[j].tacc[0] * r_,
-                    ctl[j].tacc[1] * r_, ctl[j].tacc[2] * r_, ctl[j].tacc[3] * r_, ctl[j].tacc[4] * r_, ctl[j].tacc[5] * r_,
-                    ctl[j].tacc[6] * r_);
-        }
-#endif
-        if (n == 0) continue;  // the reference's "fail": no seed k-mer passes (out[j].n == 0)
-        // one block per job (mc_bfs_result_free releases it through `hi`), laid out as k_bfs_pack wrote it
-        char *blk = static_cast<char *>(res_alloc(bfs_pack_bytes(n)));
-        if (!blk) {
-            ret = fail(c, MC_ENOMEM, "mc_bfs: out of host memory");
-            break;
-        }
-        o->n = n;
-        o->hi = reinterpret_cast<uint64_t *>(blk);
-        o->lo = o->hi + n;
-        o->dist = reinterpret_cast<int32_t *>(o->lo + n);
-        o->cov = reinterpret_cast<int16_t *>(reinterpret_cast<char *>(o->dist) + ((4 * n + 7) & ~7ull));
-        o->last = reinterpret_cast<uint8_t *>(reinterpret_cast<char *>(o->cov) + ((2 * n + 7) & ~7ull));
-        o->levels = h_hdr[j].levels;
-        const hipError_t e = hipMemcpyAsync(blk, c->d_bfs_pack + hdr_bytes + h_hdr[j].offset, bfs_pack_bytes(n), hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) {
-            ret = fail(c, MC_EHIP, "mc_bfs: %s", hipGetErrorString(e));
-            break;
-        }
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess && ret == MC_OK) ret = fail(c, MC_EHIP, "mc_bfs: copying the results failed");
-    if (ret != MC_OK)
-        for (uint32_t j = 0; j < n_jobs; j++) mc_bfs_result_free(&out[j]);
-    return ret;
-}
-
-int mc_bfs(mc_ctx *c, const uint64_t *seed_hi, const uint64_t *seed_lo, uint64_t n_seeds, int dir, int min_cov,
-           int64_t max_kmers, int64_t max_radius, mc_bfs_result *out)
-{
-    if (!c) return MC_EINVAL;
-    if (!out) return fail(c, MC_EINVAL, "mc_bfs: out is null");
-    mc_bfs_job job{seed_hi, seed_lo, n_seeds, dir};
-    int rc = mc_bfs_batch(c, &job, 1, min_cov, max_kmers, max_radius, out);
-    if (rc) return rc;
-    if (out->n == 0) return fail(c, MC_ENOSEED, "Could not find any k-mers of the target gene in the input");
-    return MC_OK;
-}
-
-}  // extern "C"
-
-
-// ---- the walk over several ranks' tables where they are (include/mcgpu.h mc_shard_*) -------------------------------------
-namespace {
-struct ShardWire {  // what a mc_shard_handle holds
-    hipIpcMemHandle_t ipc;  // of the table's block (all zero: none could be made; the handle then only serves its own process)
-    uint64_t addr, bytes;   // the table in the exporting process
-    uint32_t shift, rmask, n_regions;
-    int32_t mm_k;
-    uint64_t empty;         // count of the key that equals EMPTY_KEY (hash modes)
-    int32_t pid;
-    int16_t device;
-    uint8_t k, key_mode;
-    uint64_t token;         // drawn once per process: ranks in separate PID namespaces can share a pid, and a foreign address must never be taken for a local one
-    uint32_t magic, has_ipc;
-};
-static_assert(sizeof(ShardWire) == 128, "the wire format of a shard handle");
-uint64_t process_token()
-{
-    static const uint64_t tok = [] {
-        uint64_t v = 0;
-        if (FILE *f = fopen("/dev/urandom", "rb")) { if (fread(&v, sizeof v, 1, f) != 1) v = 0; fclose(f); }
-        v ^= ((uint64_t)getpid() << 32) ^ (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() ^ (uint64_t)(uintptr_t)&v;
-        return v ? v : 1;
-    }();
-    return tok;
-}
-static_assert(sizeof(ShardWire) <= sizeof(mc_shard_handle), "mc_shard_handle is too small");
-constexpr uint32_t SHARD_MAGIC = 0x4D435348u;  // "MCSH"
-
-// this context's counting table, ready to be read by another walker: initialised, nothing parked, counters read
-int shard_describe(mc_ctx *c, ShardWire *w, bool want_ipc)
-{
-    memset(w, 0, sizeof *w);
-    if (!c->finalized) return fail(c, MC_ESTATE, "mc_shard_export: call mc_finalize_counts first");
-    if (c->solid_external) return fail(c, MC_ESTATE, "mc_shard_export: a BFS-only context has no counting table to share");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = by_key_ready(c);  // (the walkers of other ranks come with keys)
-    if (!rc) rc = materialize(c);  // (a rank that owns nothing of the batch still offers a valid, empty table)
-    if (rc) return rc;
-    unsigned long long *h = c->h_scratch;
-    HIPCHK(c, hipMemcpyAsync(h, c->d_ctr, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const TableView t = c->view();
-    w->addr = (uint64_t)(uintptr_t)c->slots;
-    w->bytes = c->n_slots() * sizeof(Slot);
-    w->shift = t.shift; w->rmask = t.rmask; w->n_regions = t.n_regions; w->mm_k = t.mm_k;
-    w->empty = h[1];
-    w->pid = (int32_t)getpid(); w->device = (int16_t)c->cfg.device; w->k = (uint8_t)c->cfg.k; w->key_mode = (uint8_t)c->cfg.key_mode;
-    w->token = process_token();
-    w->magic = SHARD_MAGIC;
-    if (want_ipc) {
-        const hipError_t e = hipIpcGetMemHandle(&w->ipc, c->slots);
-        w->has_ipc = e == hipSuccess;
-        if (e != hipSuccess) (void)hipGetLastError();  // (the handle still serves this process)
-    }
-    return MC_OK;
-}
-
-void shard_detach_locked(mc_ctx *c)
-{
-    (void)hipSetDevice(c->cfg.device);
-    for (auto &m : c->ipc_opened) m.in_use = false;  // (closed when the next attachments do not ask for them: shard_attach_locked)
-    if (c->d_shards) (void)hipFree(c->d_shards);
-    c->d_shards = nullptr;
-    c->h_shards.clear();
-    c->shard_owner_mm_k = 0;
-}
-
-int shard_attach_locked(mc_ctx *c, const ShardWire *w, uint32_t n, uint32_t self, int by_minimizer)
-{
-    shard_detach_locked(c);
-    c->shards_dropped = false;
-    if (!c->finalized) return fail(c, MC_ESTATE, "mc_shard_attach: call mc_finalize_counts first");
-    if (n == 0 || n > 512 || self >= n) return fail(c, MC_EINVAL, "mc_shard_attach: bad number of shards / own index");
-    if (by_minimizer && !(c->cfg.key_mode == MC_KEY_PACKED && c->cfg.k >= SK_MIN_K))
-        return fail(c, MC_EINVAL, "mc_shard_attach: keys are dealt by minimizer only where reads travel as super-k-mer records (packed keys, k >= %d)", SK_MIN_K);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    std::vector<ShardRef> refs(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const ShardWire &x = w[i];
-        if (x.magic != SHARD_MAGIC) return fail(c, MC_EINVAL, "mc_shard_attach: shard %u is not a handle of mc_shard_export", i);
-        if (x.k != c->cfg.k || x.key_mode != c->cfg.key_mode) return fail(c, MC_EINVAL, "mc_shard_attach: shard %u was counted with k = %d, key mode %d", i, x.k, x.key_mode);
-        Slot *slots = nullptr;
-        if (i == self) {
-            if (x.addr != (uint64_t)(uintptr_t)c->slots || x.token != process_token())
-                return fail(c, MC_EINVAL, "mc_shard_attach: shard %u is not this context's table as it is now (export again after counting)", i);
-            slots = c->slots;
-        } else if (x.token == process_token()) {  // another context of this process: its pointer, through peer access when it is another device's
-            slots = reinterpret_cast<Slot *>((uintptr_t)x.addr);
-            if (x.device != c->cfg.device) {
-                int can = 0;
-                if (hipDeviceCanAccessPeer(&can, c->cfg.device, x.device) != hipSuccess || !can)
-                    return fail(c, MC_EHIP, "mc_shard_attach: GPU %d cannot read GPU %d's memory (no peer access)", c->cfg.device, x.device);
-                const hipError_t e = hipDeviceEnablePeerAccess(x.device, 0);
-                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail(c, MC_EHIP, "mc_shard_attach: hipDeviceEnablePeerAccess: %s", hipGetErrorString(e));
-                (void)hipGetLastError();
-            }
-        } else {
-            if (!x.has_ipc) { shard_detach_locked(c); return fail(c, MC_EHIP, "mc_shard_attach: shard %u comes from another process without an IPC handle", i); }
-            void *p = nullptr;
-            for (auto &m : c->ipc_opened)  // (the same table as last time: its mapping is still there)
-                if (!m.in_use && memcmp(&m.h, &x.ipc, sizeof x.ipc) == 0 && m.addr == x.addr && m.bytes == x.bytes) { p = m.p; m.in_use = true; break; }
-            if (!p) {
-                const hipError_t e = hipIpcOpenMemHandle(&p, x.ipc, hipIpcMemLazyEnablePeerAccess);
-                if (e != hipSuccess) { shard_detach_locked(c); return fail(c, MC_EHIP, "mc_shard_attach: hipIpcOpenMemHandle (shard %u): %s", i, hipGetErrorString(e)); }
-                c->ipc_opened.push_back(mc_ctx::IpcMap{x.ipc, p, true, x.addr, x.bytes});
-            }
-            slots = static_cast<Slot *>(p);
-        }
-        refs[i].slots = slots; refs[i].shift = x.shift; refs[i].rmask = x.rmask; refs[i].n_regions = x.n_regions; refs[i].mm_k = x.mm_k;
-        refs[i].empty = x.empty;
-    }
-    if (hipMalloc(reinterpret_cast<void **>(&c->d_shards), n * sizeof(ShardRef)) != hipSuccess) { shard_detach_locked(c); return fail(c, MC_ENOMEM, "mc_shard_attach: out of device memory"); }
-    if (hipMemcpy(c->d_shards, refs.data(), n * sizeof(ShardRef), hipMemcpyHostToDevice) != hipSuccess) { shard_detach_locked(c); return fail(c, MC_EHIP, "mc_shard_attach: upload failed"); }
-    // Mappings nobody asked for this time are closed at once (kept until twice as many had gathered, a peer's table
-    // that had been replaced -- grown, or given back to the driver -- stayed pinned through its mapping, up to 137 GB each).
-    {
-        std::vector<mc_ctx::IpcMap> keep;
-        for (auto &m : c->ipc_opened) { if (m.in_use) keep.push_back(m); else (void)hipIpcCloseMemHandle(m.p); }
-        c->ipc_opened.swap(keep);
-    }
-    c->h_shards = refs;
-    c->shard_self = self;
-    c->shard_owner_mm_k = by_minimizer ? c->cfg.k : 0;
-    return MC_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int mc_shard_export(mc_ctx *c, mc_shard_handle *out)
-{
-    if (!c) return MC_EINVAL;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!out) return fail(c, MC_EINVAL, "mc_shard_export: out is null");
-    ShardWire w;
-    const int rc = shard_describe(c, &w, true);
-    if (rc) return rc;
-    memset(out, 0, sizeof *out);
-    memcpy(out, &w, sizeof w);
-    return MC_OK;
-}
-
-int mc_shard_attach(mc_ctx *c, const mc_shard_handle *shards, uint32_t n_shards, uint32_t self, int by_minimizer)
-{
-    if (!c) return MC_EINVAL;
-    std::lock_guard<std::mutex> g(c->mu);
-    if (!shards) return fail(c, MC_EINVAL, "mc_shard_attach: shards is null");
-    if (n_shards == 0 || n_shards > 512) return fail(c, MC_EINVAL, "mc_shard_attach: bad number of shards / own index");  // (before anything is sized by it)
-    std::vector<ShardWire> w(n_shards);
-    for (uint32_t i = 0; i < n_shards; i++) memcpy(&w[i], &shards[i], sizeof(ShardWire));
-    return shard_attach_locked(c, w.data(), n_shards, self, by_minimizer);
-}
-
-int mc_shard_detach(mc_ctx *c)
-{
-    if (!c) return MC_EINVAL;
-    std::lock_guard<std::mutex> g(c->mu);
-    shard_detach_locked(c);
-    c->shards_dropped = false;
-    return MC_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------ several GPUs as one table
-// mc_group: the native counterpart of metacherchant_amd/distributed.py, for a host that is one
-// process: a context per device, one host thread per device for the work, and the exchange as peer-to-peer copies --
-// every (source, destination) pair at once, so that all xGMI links of a GPU are busy together, which is what an
-// all-to-all over RCCL's grouped send / recv does too.  Reads are dealt to the devices in equal contiguous shares, every
-// device turns its share into super-k-mer records (keys for k < 23 / hash keys) bucketed by owner, the buckets travel,
-// every device counts what it owns (disjoint key sets).  For the BFS the shards' k-mers at or above the threshold are
-// gathered on the first device into a BFS-only context that borrows that device's read store (read pointers refer to the
-// first device's reads: the others keep none).  What the reference does instead: P threads over one shared map
-// (src/io/IOUtils.java:283-315, src/io/ReadsDispatcher.java:34-53).
-
-// RCCL, loaded when a group asks for it (MC_GROUP_TRANSPORT=rccl / MC_FLAG_GROUP_RCCL): the library is large and a process
-// that counts on one GPU, or moves its buckets with peer copies, never needs it.  Types and constants from <rccl/rccl.h>.
-struct RcclApi {
-    void *lib = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t *, int, const int *) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    ncclResult_t (*Send)(const void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Recv)(void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-    bool load(std::string *why)
-    {
-        if (lib) return true;
-        for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-            if (lib) break;
-        }
-        if (!lib) { *why = std::string("librccl.so.1 cannot be loaded: ") + dlerror(); return false; }
-#define RCCL_SYM(field, sym) field = reinterpret_cast<decltype(field)>(dlsym(lib, sym)); if (!field) { *why = std::string("librccl has no ") + sym; return false; }
-        RCCL_SYM(CommInitAll, "ncclCommInitAll") RCCL_SYM(CommDestroy, "ncclCommDestroy") RCCL_SYM(GroupStart, "ncclGroupStart")
-        RCCL_SYM(GroupEnd, "ncclGroupEnd") RCCL_SYM(Send, "ncclSend") RCCL_SYM(Recv, "ncclRecv") RCCL_SYM(GetErrorString, "ncclGetErrorString")
-#undef RCCL_SYM
-        return true;
-    }
-};
-static RcclApi g_rccl;
-
-struct mc_group {
-    std::vector<mc_ctx *> ctx;  // one per device, in the order given
-    mc_ctx *solid = nullptr;    // BFS-only context on the first device (n > 1)
-    int solid_cov = -1;
-    bool dirty = true;          // counts changed since the shards were gathered
-    mc_config cfg{};
-    std::string err;
-    std::mutex mu;
-    // how the buckets travel between the devices: peer-to-peer copies (every pair at once), or RCCL -- one communicator per
-    // device in this process (ncclCommInitAll), the exchange as grouped ncclSend / ncclRecv, which is what an all-to-all is
-    bool use_rccl = false;
-    std::vector<ncclComm_t> comm;
-    bool peer_all = true;       // every pair of distinct devices has peer access (else HIP stages those copies through the host)
-    bool gather_reads = false;  // every device's reads are brought to the first device's store, and every record carries a pointer into it
-    mc_switches sw;             // the environment switches, read by mc_group_create (switches.h)
-};
-
-namespace {
-
-int gfail(mc_group *g, int code, const std::string &msg)
-{
-    if (g) g->err = msg;
-    return code;
-}
-
-// runs f(rank) on one thread per rank; returns the first non-zero result
-template <typename F>
-int per_rank(size_t n, F &&f)
-{
-    std::vector<int> rc(n, 0);
-    std::vector<std::thread> th;
-    auto guarded = [&](size_t r) {  // (an exception must not leave a thread: std::terminate)
-        try { rc[r] = f(r); } catch (const std::bad_alloc &) { rc[r] = MC_ENOMEM; } catch (...) { rc[r] = MC_EINVAL; }
-    };
-    for (size_t r = 1; r < n; r++) th.emplace_back([&, r] { guarded(r); });
-    guarded(0);
-    for (auto &t : th) t.join();
-    for (int x : rc) if (x) return x;
-    return MC_OK;
-}
-
-// bytes from a buffer of src's device to one of dst's (the same device: a plain device copy)
-hipError_t peer_copy(void *d, const mc_ctx *dst, const void *s, const mc_ctx *src, size_t bytes, hipStream_t st)
-{
-    if (bytes == 0) return hipSuccess;
-    if (dst->cfg.device == src->cfg.device) return hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, st);
-    return hipMemcpyPeerAsync(d, dst->cfg.device, s, src->cfg.device, bytes, st);
-}
-
-}  // namespace
-
-extern "C" {
-
-const char *mc_group_last_error(const mc_group *g) { return g ? g->err.c_str() : g_create_err.c_str(); }
-
-void mc_group_destroy(mc_group *g)
-{
-    if (!g) return;
-    for (ncclComm_t cm : g->comm) if (cm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(cm);
-    if (g->solid) mc_destroy(g->solid);
-    for (mc_ctx *c : g->ctx) mc_destroy(c);
-    delete g;
-}
-
-int mc_group_create(const mc_config *cfg, const int32_t *devices, uint32_t n_devices, mc_group **out)
-{
-    if (!cfg || !devices || !out || n_devices == 0 || n_devices > 64) return fail(nullptr, MC_EINVAL, "mc_group_create: bad argument");
-    *out = nullptr;
-    mc_group *g = new (std::nothrow) mc_group;
-    if (!g) return fail(nullptr, MC_ENOMEM, "mc_group_create: out of host memory");
-    g->cfg = *cfg;
-    g->sw = read_switches();
-    for (uint32_t r = 0; r < n_devices; r++) {
-        mc_config c = *cfg;
-        c.device = devices[r];
-        c.capacity_hint = cfg->capacity_hint ? cfg->capacity_hint / n_devices + (1u << 20) : 0;  // owners hold equal shares of the keys
-        if (n_devices > 1) c.flags |= MC_FLAG_SOLID_LIST;                                           // its solid k-mers will be exported
-        mc_ctx *x = nullptr;
-        const int rc = mc_create(&c, &x);
-        if (rc) { mc_group_destroy(g); return rc; }
-        g->ctx.push_back(x);
-        // The BFS device reads its look-ahead from ITS store: the other devices' reads are brought there (group_import_reads; a file's
-        // reads are tokenised there in the first place) and every device works its pointers out as if its reads sat in that store
-        // -- a walk that had only the first device's reads to follow took 20 times as long at 8 devices (include/mcgpu.h
-        // mc_set_read_pointers).  MC_EXCHANGE_GATHER_READS=0: the other devices' records carry no pointers.
-        g->gather_reads = g->sw.group_gather_reads && n_devices > 1;
-        if (n_devices > 1) (void)mc_set_read_pointers(x, g->gather_reads ? ((r == 0 ? 1 : 2) | MC_PTRS_ON_EVERY_RECORD) : (r == 0 ? 1 : 0));
-    }
-    // peer access between every pair of different devices (already enabled: fine).  A pair without it still works -- HIP
-    // stages such copies through the host -- but at a fraction of the xGMI rate: say so once.
-    for (uint32_t a = 0; a < n_devices; a++)
-        for (uint32_t b = 0; b < n_devices; b++) {
-            if (devices[a] == devices[b]) continue;
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, devices[a], devices[b]) != hipSuccess) can = 0;
-            bool ok = false;
-            if (can && hipSetDevice(devices[a]) == hipSuccess) {
-                const hipError_t e = hipDeviceEnablePeerAccess(devices[b], 0);
-                ok = e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled;
-            }
-            (void)hipGetLastError();
-            if (!ok && g->peer_all) {
-                g->peer_all = false;
-                fprintf(stderr, "WARN: no peer access from GPU %d to GPU %d: the exchange between them is staged through the host\n", devices[a], devices[b]);
-            }
-        }
-    {   // transport of the exchange
-        g->use_rccl = ((cfg->flags & MC_FLAG_GROUP_RCCL) != 0 || g->sw.group_transport == 1) && g->sw.group_transport != 2;
-        if (g->use_rccl && n_devices > 1) {
-            for (uint32_t a = 0; a < n_devices; a++)
-                for (uint32_t b = a + 1; b < n_devices; b++)
-                    if (devices[a] == devices[b]) { mc_group_destroy(g); return fail(nullptr, MC_EINVAL, "mc_group_create: RCCL wants every rank on a GPU of its own (GPU %d is named twice); use the peer-copy transport for shares of one GPU", devices[a]); }
-            std::string why;
-            if (!g_rccl.load(&why)) { mc_group_destroy(g); return fail(nullptr, MC_EINVAL, "mc_group_create: %s", why.c_str()); }
-            g->comm.assign(n_devices, nullptr);
-            std::vector<int> devs(devices, devices + n_devices);
-            const ncclResult_t r = g_rccl.CommInitAll(g->comm.data(), (int)n_devices, devs.data());
-            if (r != ncclSuccess) { mc_group_destroy(g); return fail(nullptr, MC_EHIP, "mc_group_create: ncclCommInitAll: %s", g_rccl.GetErrorString(r)); }
-        } else {
-            g->use_rccl = false;
-        }
-    }
-    if (n_devices > 1) {
-        mc_config c = *cfg;
-        c.device = devices[0];
-        c.capacity_hint = 1u << 20;
-        c.flags = 0;
-        const int rc = mc_create(&c, &g->solid);
-        if (rc) { mc_group_destroy(g); return rc; }
-    }
-    *out = g;
-    return MC_OK;
-}
-
-int mc_group_set_coverage_hint(mc_group *g, int min_cov)
-{
-    if (!g) return MC_EINVAL;
-    for (mc_ctx *c : g->ctx) {
-        const int rc = mc_set_coverage_hint(c, min_cov);
-        if (rc) return gfail(g, rc, mc_last_error(c));
-    }
-    return MC_OK;
-}
-
-namespace {
-// what one device brings to an exchange: its share of the reads (device pointers) and, filled on the way, what it sends and receives
-struct GroupRank {
-    DevBuf<uint64_t> dw, doff, send, recv;   // reads uploaded here (host batches); what goes out (records: 2 words each, or keys) and what came in
-    DevBuf<uint32_t> send_p, recv_p;         // the read pointers that travel with them
-    DevBuf<uint32_t> fc, recv_fc;            // binned records: a row of fine-bucket counts for every owner; the rows every source sent me
-    std::vector<uint64_t> owner_off;         // owner o's piece of `send` = [owner_off[o], owner_off[o + 1])
-    std::vector<uint64_t> owner_win;         // binned records: the windows of owner o's piece
-    uint64_t n_recv = 0;
-    const uint64_t *d_words = nullptr, *d_off = nullptr;  // the share: d_off[0 .. n_reads] index bases of d_words
-    uint64_t n_reads = 0, n_bases = 0, windows = 0;       // n_bases = d_off[n_reads]; windows: k-mer occurrences, or an upper bound
-    int64_t in_store = -1;                                // >= 0: the share sits in this device's read store from that word on
-};
-
-// n_words packed words of device `from`'s reads to word `at_word` of the first device's read store (where that device's pointers lead)
-int group_import_reads(mc_group *g, size_t from, const uint64_t *src, uint64_t n_words, uint64_t at_word)
-{
-    mc_ctx *c0 = g->ctx[0];
-    std::lock_guard<std::mutex> g0(c0->mu);
-    if (hipSetDevice(c0->cfg.device) != hipSuccess) return MC_EHIP;
-    if (at_word + n_words + 1 > c0->rs_cap_words) {
-        const uint64_t fill = c0->rs_bases / 32;
-        int rc = rs_reserve(c0, at_word + n_words + 1 > fill ? at_word + n_words + 1 - fill : 0);
-        if (rc) return rc;
-    }
-    if (peer_copy(c0->rs_words + at_word, c0, src, g->ctx[from], n_words * 8, c0->stream) != hipSuccess || hipStreamSynchronize(c0->stream) != hipSuccess) return MC_EHIP;
-    c0->rs_hi_bases = std::max(c0->rs_hi_bases, (at_word + n_words) * 32);
-    return MC_OK;
-}
-
-// every device: its share -> records (keys) bucketed by owner; the exchange; every device counts what it owns
-int group_exchange_count(mc_group *g, std::vector<GroupRank> &R)
-{
-    const size_t W = g->ctx.size();
-    const bool sk = g->ctx[0]->sk_form;
-    bool sk_batch = sk;  // this batch travels as super-k-mer records (false: as keys)
-    // the binned form of the record exchange (include/mcgpu.h mc_extract_superkmers_binned_dev) where every device's table is laid
-    // out for the same level-1 buckets: the sender orders an owner's records by them, and the owner's run starts at its second level
-    uint32_t fine = 0;
-    if (sk) {
-        fine = mc_superkmer_fine_buckets(g->ctx[0], (uint32_t)W);
-        for (size_t r = 1; r < W && fine; r++) if (mc_superkmer_fine_buckets(g->ctx[r], (uint32_t)W) != fine) fine = 0;
-    }
-    auto extract = [&](size_t r, bool as_records) -> int {
-        mc_ctx *c = g->ctx[r];
-        GroupRank &X = R[r];
-        X.owner_off.assign(W + 1, 0);
-        X.owner_win.assign(W, 0);
-        if (hipSetDevice(c->cfg.device) != hipSuccess) return MC_EHIP;
-        if (as_records && fine && X.fc.alloc((uint64_t)W * fine) != hipSuccess) return MC_ENOMEM;
-        if (X.n_reads == 0 || X.windows == 0) {  // (a rank without reads still sends its rows: zeros)
-            if (as_records && fine && (hipMemsetAsync(X.fc.p, 0, (uint64_t)W * fine * 4, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) return MC_EHIP;
-            return MC_OK;
-        }
-        X.send.reset();
-        X.send_p.reset();
-        c->extract_in_store = X.in_store;
-        if (as_records) {
-            const uint64_t cap = mc_superkmer_capacity(c, X.windows, X.n_reads);
-            if (X.send.alloc(cap * 2) != hipSuccess || X.send_p.alloc(cap) != hipSuccess) return MC_ENOMEM;
-            if (fine)
-                return mc_extract_superkmers_binned_dev(c, X.d_words, X.d_off, X.n_reads, X.n_bases, (uint32_t)W, fine, X.send.p, X.send_p.p, cap, X.fc.p,
-                                                        X.owner_off.data(), X.owner_win.data());
-            return mc_extract_superkmers_dev(c, X.d_words, X.d_off, X.n_reads, X.n_bases, (uint32_t)W, X.send.p, X.send_p.p, cap, X.owner_off.data());
-        }
-        if (X.send.alloc(X.windows) != hipSuccess || X.send_p.alloc(X.windows) != hipSuccess) return MC_ENOMEM;
-        // A group that deals super-k-mer records deals by minimizer (sk_owner), and the owner of a k-mer must not depend on the
-        // form a batch travels in: one batch as keys dealt by the key's own hash would split a k-mer's count over two shards
-        // -- each under the threshold, perhaps, and the k-mer gone from the graph.
-        c->extract_by_minimizer = sk;
-        return mc_extract_keys_dev(c, X.d_words, X.d_off, X.n_reads, X.n_bases, (uint32_t)W, reinterpret_cast<int64_t *>(X.send.p), X.send_p.p, X.windows,
-                                   X.owner_off.data());
-    };
-    std::vector<uint64_t> fill(W, 0);  // (where every device's reads go, or are deemed to go, in the shared store: a second extraction starts there again)
-    if (g->gather_reads) for (size_t r = 0; r < W; r++) fill[r] = mc_read_store_tell(g->ctx[r]);
-    int rc = per_rank(W, [&](size_t r) -> int { return extract(r, sk); });
-    if (rc == MC_EOVERFLOW && sk) {
-        if (g->gather_reads) for (size_t r = 0; r < W; r++) (void)mc_read_store_seek(g->ctx[r], fill[r], 0);
-        // an owner's piece overflowed (reads of low complexity share one minimizer, hence one owner): this batch travels as
-        // keys instead, on every rank alike -- one record per window, counted per owner first and then packed (no piece to
-        // overflow), and dealt to the SAME owners: those of the keys' minimizers
-        sk_batch = false;
-        for (mc_ctx *c : g->ctx) c->err.clear();
-        if (g->sw.ingest_debug) fprintf(stderr, "[ingest] group: an owner's piece of the record form overflowed; this batch travels as keys, dealt by minimizer\n");
-        rc = per_rank(W, [&](size_t r) -> int { return extract(r, false); });
-    }
-    if (rc) {
-        for (mc_ctx *c : g->ctx) if (!c->err.empty()) return gfail(g, rc, c->err);
-        return gfail(g, rc, "mc_group_add_reads_packed: extraction failed");
-    }
-    // ---- the exchange: owner d receives its piece of every rank's output, all pairs at once
-    const size_t unit = sk_batch ? 16 : 8;
-    const bool binned = sk_batch && fine != 0;
-    if (g->use_rccl) {
-        // RCCL: every device's receive buffer first, then ONE group of sends and receives over all pairs (what an all-to-all
-        // with per-pair counts is), each communicator's calls on its own context's stream
-        rc = per_rank(W, [&](size_t d) -> int {
-            mc_ctx *c = g->ctx[d];
-            if (hipSetDevice(c->cfg.device) != hipSuccess) return MC_EHIP;
-            uint64_t total = 0;
-            for (size_t r = 0; r < W; r++) total += R[r].owner_off[d + 1] - R[r].owner_off[d];
-            R[d].n_recv = total;
-            if (binned && R[d].recv_fc.alloc((uint64_t)W * fine) != hipSuccess) return MC_ENOMEM;
-            if (total == 0) return MC_OK;
-            return R[d].recv.alloc(total * (sk_batch ? 2 : 1)) == hipSuccess && R[d].recv_p.alloc(total) == hipSuccess ? MC_OK : MC_ENOMEM;
-        });
-        if (rc) return gfail(g, rc, "mc_group_add_reads_packed: no room for the received buckets");
-        struct Zero { size_t d; uint64_t at, m; };
-        std::vector<Zero> ptr_zero;
-        ncclResult_t nr = g_rccl.GroupStart();
-        std::vector<uint64_t> at(W, 0);
-        for (size_t r = 0; r < W && nr == ncclSuccess; r++)       // source
-            for (size_t d = 0; d < W && nr == ncclSuccess; d++) {  // owner
-                const uint64_t o0 = R[r].owner_off[d], m = R[r].owner_off[d + 1] - o0;
-                if (binned) {  // source r's row of counts for owner d
-                    nr = g_rccl.Send(R[r].fc.p + d * fine, (size_t)fine * 4, ncclUint8, (int)d, g->comm[r], g->ctx[r]->stream);
-                    if (nr == ncclSuccess) nr = g_rccl.Recv(R[d].recv_fc.p + r * fine, (size_t)fine * 4, ncclUint8, (int)r, g->comm[d], g->ctx[d]->stream);
-                    if (nr != ncclSuccess) break;
-                }
-                if (m == 0) continue;
-                nr = g_rccl.Send(reinterpret_cast<const char *>(R[r].send.p) + o0 * unit, m * unit, ncclUint8, (int)d, g->comm[r], g->ctx[r]->stream);
-                if (nr == ncclSuccess) nr = g_rccl.Recv(reinterpret_cast<char *>(R[d].recv.p) + at[d] * unit, m * unit, ncclUint8, (int)r, g->comm[d], g->ctx[d]->stream);
-                // (read pointers lead into the FIRST device's read store, the one the walk reads: the other devices keep none, and the
-                // zeros they used to send -- a fifth of their bytes -- are filled in where they arrive)
-                if (r == 0 || g->gather_reads) {  // (gather_reads: every device's reads are in that store, every record brings its pointer)
-                    if (nr == ncclSuccess) nr = g_rccl.Send(R[r].send_p.p + o0, m * 4, ncclUint8, (int)d, g->comm[r], g->ctx[r]->stream);
-                    if (nr == ncclSuccess) nr = g_rccl.Recv(R[d].recv_p.p + at[d], m * 4, ncclUint8, (int)r, g->comm[d], g->ctx[d]->stream);
-                } else {
-                    ptr_zero.push_back({d, at[d], m});
-                }
-                at[d] += m;
-            }
-        const ncclResult_t ne = g_rccl.GroupEnd();
-        if (nr == ncclSuccess) nr = ne;
-        for (const Zero &z : ptr_zero) {
-            if (hipSetDevice(g->ctx[z.d]->cfg.device) != hipSuccess || hipMemsetAsync(R[z.d].recv_p.p + z.at, 0, z.m * 4, g->ctx[z.d]->stream) != hipSuccess)
-                return gfail(g, MC_EHIP, "mc_group_add_reads_packed: clearing the pointers of pointer-less records failed");
-        }
-        if (nr != ncclSuccess) return gfail(g, MC_EHIP, std::string("mc_group_add_reads_packed: RCCL exchange: ") + g_rccl.GetErrorString(nr));
-        rc = per_rank(W, [&](size_t d) -> int {
-            mc_ctx *c = g->ctx[d];
-            if (hipSetDevice(c->cfg.device) != hipSuccess) return MC_EHIP;
-            return hipStreamSynchronize(c->stream) == hipSuccess ? MC_OK : MC_EHIP;
-        });
-        if (rc) return gfail(g, rc, "mc_group_add_reads_packed: the RCCL exchange failed");
-    } else
-    rc = per_rank(W, [&](size_t d) -> int {
-        mc_ctx *c = g->ctx[d];
-        if (hipSetDevice(c->cfg.device) != hipSuccess) return MC_EHIP;
-        uint64_t total = 0;
-        for (size_t r = 0; r < W; r++) total += R[r].owner_off[d + 1] - R[r].owner_off[d];
-        R[d].n_recv = total;
-        if (total == 0) return MC_OK;
-        if (R[d].recv.alloc(total * (sk_batch ? 2 : 1)) != hipSuccess || R[d].recv_p.alloc(total) != hipSuccess) return MC_ENOMEM;
-        if (binned && R[d].recv_fc.alloc((uint64_t)W * fine) != hipSuccess) return MC_ENOMEM;
-        uint64_t at = 0;
-        for (size_t r = 0; r < W; r++) {
-            const uint64_t o0 = R[r].owner_off[d], m = R[r].owner_off[d + 1] - o0;
-            if (binned && peer_copy(R[d].recv_fc.p + r * fine, c, R[r].fc.p + d * fine, g->ctx[r], (size_t)fine * 4, c->stream) != hipSuccess) return MC_EHIP;
-            // (pointers: from the first device only -- they lead into its read store; the others' would be zeros)
-            if (peer_copy(reinterpret_cast<char *>(R[d].recv.p) + at * unit, c, reinterpret_cast<const char *>(R[r].send.p) + o0 * unit, g->ctx[r], m * unit, c->stream) != hipSuccess ||
-                (r == 0 || g->gather_reads ? peer_copy(R[d].recv_p.p + at, c, R[r].send_p.p + o0, g->ctx[r], m * 4, c->stream)
-                        : (m ? hipMemsetAsync(R[d].recv_p.p + at, 0, m * 4, c->stream) : hipSuccess)) != hipSuccess)
-                return MC_EHIP;
-            at += m;
-        }
-        return hipStreamSynchronize(c->stream) == hipSuccess ? MC_OK : MC_EHIP;
-    });
-    if (rc) return gfail(g, rc, "mc_group_add_reads_packed: the exchange between the devices failed");
-    // ---- every device counts what it owns
-    rc = per_rank(W, [&](size_t d) -> int {
-        if (R[d].n_recv == 0) return MC_OK;
-        if (binned) {  // every source's piece is a part, in the order the pieces were received
-            std::vector<uint64_t> part_off(W + 1, 0);
-            uint64_t windows = 0;
-            for (size_t r = 0; r < W; r++) {
-                part_off[r + 1] = part_off[r] + (R[r].owner_off[d + 1] - R[r].owner_off[d]);
-                windows += R[r].owner_win[d];
-            }
-            return mc_add_superkmers_binned_dev(g->ctx[d], R[d].recv.p, R[d].recv_p.p, R[d].n_recv, windows, fine, (uint32_t)W, part_off.data(), R[d].recv_fc.p);
-        }
-        return sk_batch ? mc_add_superkmers_dev(g->ctx[d], R[d].recv.p, R[d].recv_p.p, R[d].n_recv)
-                  : mc_add_keys_dev(g->ctx[d], reinterpret_cast<const int64_t *>(R[d].recv.p), R[d].recv_p.p, R[d].n_recv);
-    });
-    if (rc) {
-        for (mc_ctx *c : g->ctx) if (!c->err.empty()) return gfail(g, rc, c->err);
-        return gfail(g, rc, "mc_group_add_reads_packed: counting failed");
-    }
-    return MC_OK;
-}
-}  // namespace
-
-namespace {
-// a batch of packed reads in host memory: shares up to the devices, exchange, count (the caller holds the group's lock)
-int group_add_host_batch(mc_group *g, const uint64_t *words, const uint64_t *off, uint64_t n_reads)
-{
-    const size_t W = g->ctx.size();
-    const int k = g->cfg.k;
-    std::vector<GroupRank> R(W);
-    int rc = per_rank(W, [&](size_t r) -> int {
-        mc_ctx *c = g->ctx[r];
-        const uint64_t a = n_reads * r / W, b = n_reads * (r + 1) / W;
-        if (a == b) return MC_OK;
-        if (hipSetDevice(c->cfg.device) != hipSuccess) return MC_EHIP;
-        const uint64_t w0 = off[a] / 32, w1 = (off[b] + 31) / 32 + 1, nb = off[b] - w0 * 32;
-        std::vector<uint64_t> rel(off + a, off + b + 1);
-        uint64_t windows = 0;
-        for (uint64_t i = 0; i < b - a; i++) {
-            const uint64_t len = rel[i + 1] - rel[i];
-            if (len >= (uint64_t)k) windows += len - (uint64_t)k + 1;
-        }
-        for (auto &x : rel) x -= w0 * 32;
-        if (R[r].dw.alloc(w1 - w0) != hipSuccess || R[r].doff.alloc(b - a + 1) != hipSuccess) return MC_ENOMEM;
-        // (through the context's pinned staging buffers: a pageable copy runs at a third of the link's rate)
-        if (h2d_fast(c, R[r].dw.p, words + w0, (w1 - w0) * 8) != MC_OK || h2d_fast(c, R[r].doff.p, rel.data(), (b - a + 1) * 8) != MC_OK) return MC_EHIP;
-        R[r].d_words = R[r].dw.p; R[r].d_off = R[r].doff.p;
-        R[r].n_reads = b - a; R[r].n_bases = nb; R[r].windows = windows;
-        return MC_OK;
-    });
-    if (rc) {
-        for (mc_ctx *c : g->ctx) if (!c->err.empty()) return gfail(g, rc, c->err);
-        return gfail(g, rc, "mc_group_add_reads_packed: the reads did not reach the devices");
-    }
-    uint64_t end_word = 0;
-    if (g->gather_reads) {
-        // the shares one behind the other in the first device's store: its own where its extraction will append it, the others'
-        // copied there from their devices; every other device is told where its share sits (its pointers lead there)
-        mc_ctx *c0 = g->ctx[0];
-        uint64_t at = 0;
-        {
-            std::lock_guard<std::mutex> g0(c0->mu);
-            at = c0->rs_end() / 32;
-        }
-        std::vector<uint64_t> pos(W + 1, at);
-        for (size_t r = 0; r < W; r++) pos[r + 1] = pos[r] + (R[r].n_reads ? (R[r].n_bases + 31) / 32 + 1 : 0);
-        end_word = pos[W];
-        if ((rc = mc_read_store_seek(c0, pos[0] * 32, end_word * 32 + 64)) != MC_OK) return gfail(g, rc, c0->err);
-        rc = per_rank(W, [&](size_t r) -> int {
-            if (r == 0 || R[r].n_reads == 0) return MC_OK;
-            int x = group_import_reads(g, r, R[r].dw.p, (R[r].n_bases + 31) / 32 + 1, pos[r]);
-            return x ? x : mc_read_store_seek(g->ctx[r], pos[r] * 32, 0);
-        });
-        if (rc) {
-            for (mc_ctx *c : g->ctx) if (!c->err.empty()) return gfail(g, rc, c->err);
-            return gfail(g, rc, "mc_group_add_reads_packed: the reads did not reach the first device's store");
-        }
-    }
-    rc = group_exchange_count(g, R);
-    if (g->gather_reads && rc == MC_OK && (rc = mc_read_store_seek(g->ctx[0], end_word * 32, 0)) != MC_OK) return gfail(g, rc, g->ctx[0]->err);  // (the next batch goes behind all of them)
-    return rc;
-}
-}  // namespace
-
-int mc_group_add_reads_packed(mc_group *g, const uint64_t *words, const uint64_t *off, uint64_t n_reads)
-{
-    if (!g) return MC_EINVAL;
-    std::lock_guard<std::mutex> lk(g->mu);
-    if ((!words || !off) && n_reads) return gfail(g, MC_EINVAL, "mc_group_add_reads_packed: null pointer");
-    if (n_reads == 0) return MC_OK;
-    g->dirty = true;
-    if (g->ctx.size() == 1) {
-        const int rc = mc_add_reads_packed(g->ctx[0], words, off, n_reads);
-        return rc ? gfail(g, rc, mc_last_error(g->ctx[0])) : MC_OK;
-    }
-    return group_add_host_batch(g, words, off, n_reads);
-}
-
-int mc_group_add_reads_file(mc_group *g, const char *path, uint64_t *n_reads)
-{
-    if (!g) return MC_EINVAL;
-    if (n_reads) *n_reads = 0;
-    if (!path) return gfail(g, MC_EINVAL, "mc_group_add_reads_file: null path");
-    if (g->ctx.size() == 1) {
-        const int rc = mc_add_reads_file(g->ctx[0], path, n_reads);
-        return rc ? gfail(g, rc, mc_last_error(g->ctx[0])) : MC_OK;
-    }
-    try {
-        // Batches of 2^24 reads per device (2.5 G bases of 150-base reads: 0.6 GB of host memory per device): every batch is
-        // one exchange and one counting run on every device, and a counting run rewrites the device's whole table -- with
-        // 2^20 reads a batch, as before, a billion reads meant 119 rewrites of a 100 GB-class table per device.
-        const uint64_t per_dev = g->sw.group_batch_reads;
-        int rc = MC_OK;
-        // Uncompressed FASTA / FASTQ: tokenised on the FIRST device (csrc/tokenizer.h, chunk i + 1 crossing PCIe while chunk i
-        // is tokenised), into its read store -- the one the walk reads --; when W x per_dev reads have gathered, or the file
-        // ends, the other devices fetch their shares of the packed reads from it (device to device) and the batch is exchanged
-        // and counted.  A chunk the device declines goes through the host reader like any other file.
-        mch::PlainReadsFile f;
-        if (!g->sw.tokenizer_host && g->ctx[0]->rs_enabled && mch::map_plain_reads(path, &f)) {
-            std::lock_guard<std::mutex> lk(g->mu);
-            g->dirty = true;
-            mc_ctx *c0 = g->ctx[0];
-            const size_t W = g->ctx.size();
-            const uint64_t chunk = g->sw.tokenizer_chunk_bytes;
-            std::vector<std::pair<const char *, const char *>> cuts;
-            for (const char *b = f.p, *end = f.p + f.n; b < end;) {
-                const char *e = (uint64_t)(end - b) <= chunk + chunk / 4 ? end : mch::plain_record_start(f, b + chunk);
-                cuts.emplace_back(b, e);
-                b = e;
-            }
-            {
-                std::lock_guard<std::mutex> g0(c0->mu);
-                HIPCHK(c0, hipSetDevice(c0->cfg.device));
-                const int r = rs_reserve(c0, (f.fastq ? f.n / 2 : f.n) / 32 + 2 * cuts.size() + 2);
-                if (r) return gfail(g, r, c0->err);
-            }
-            std::unique_ptr<TokPending> pend(new TokPending);
-            auto drop_pend = [&] { std::lock_guard<std::mutex> g0(c0->mu); pend.reset(); };
-            uint64_t total = 0, n_flushes = 0;
-            // the reads gathered in `pend` so far: shares to the devices, exchange, count; the store then ends behind them
-            auto flush = [&]() -> int {
-                if (pend->reads == 0) { pend->base_word = -1; pend->bases = 0; return MC_OK; }
-                n_flushes++;
-                const uint64_t n = pend->reads, base_word = (uint64_t)pend->base_word;
-                std::vector<uint64_t> cut_off(W + 1, 0);  // base offset (relative to the batch) of every share's first read
-                {
-                    std::lock_guard<std::mutex> g0(c0->mu);
-                    if (hipSetDevice(c0->cfg.device) != hipSuccess) return gfail(g, MC_EHIP, "mc_group_add_reads_file: hipSetDevice");
-                    for (size_t r = 0; r <= W; r++)
-                        if (hipMemcpyAsync(&cut_off[r], pend->off.p + n * r / W, 8, hipMemcpyDeviceToHost, c0->stream) != hipSuccess) return gfail(g, MC_EHIP, "mc_group_add_reads_file: copy failed");
-                    if (hipStreamSynchronize(c0->stream) != hipSuccess) return gfail(g, MC_EHIP, "mc_group_add_reads_file: copy failed");
-                }
-                std::vector<GroupRank> R(W);
-                int frc = per_rank(W, [&](size_t r) -> int {
-                    mc_ctx *c = g->ctx[r];
-                    const uint64_t a = n * r / W, b = n * (r + 1) / W;
-                    if (a == b) return MC_OK;
-                    GroupRank &X = R[r];
-                    X.n_reads = b - a;
-                    X.n_bases = cut_off[r + 1];
-                    X.windows = cut_off[r + 1] - cut_off[r];  // (an upper bound: a window per base)
-                    if (r == 0) {  // in place: the share is where the walk will read it
-                        X.d_words = c0->rs_words + base_word;
-                        X.d_off = pend->off.p;
-                        X.in_store = (int64_t)base_word;
-                        return MC_OK;
-                    }
-                    // the words [w0, w1] of the share and its offsets come over; d_words is handed on as if it held the batch from
-                    // its first word (the offsets stay relative to the batch: nothing below w0 is looked at)
-                    if (hipSetDevice(c->cfg.device) != hipSuccess) return MC_EHIP;
-                    // (with 512 words before the share's first: the extract kernels load whole tiles, up to 8191 bases ahead of it)
-                    const uint64_t w0 = std::max<uint64_t>(cut_off[r] / 32, 512) - 512, w1 = (cut_off[r + 1] + 31) / 32 + 1;
-                    if (X.dw.alloc(w1 - w0) != hipSuccess || X.doff.alloc(b - a + 1) != hipSuccess) return MC_ENOMEM;
-                    if (peer_copy(X.dw.p, c, c0->rs_words + base_word + w0, c0, (w1 - w0) * 8, c->stream) != hipSuccess ||
-                        peer_copy(X.doff.p, c, pend->off.p + a, c0, (b - a + 1) * 8, c->stream) != hipSuccess ||
-                        hipStreamSynchronize(c->stream) != hipSuccess)
-                        return MC_EHIP;
-                    X.d_words = X.dw.p - w0;
-                    X.d_off = X.doff.p;
-                    // (the share sits in the first device's store: batch position p is store position base_word * 32 + p, which is
-                    // what this device's pointers come to when its -- deemed -- fill stands at the share's first word)
-                    if (g->gather_reads) return mc_read_store_seek(c, (base_word + cut_off[r] / 32) * 32, 0);
-                    return MC_OK;
-                });
-                if (frc) return gfail(g, frc, "mc_group_add_reads_file: the shares did not reach the devices");
-                frc = group_exchange_count(g, R);
-                {   // the batch's reads stay in the first device's store, whoever counted them
-                    std::lock_guard<std::mutex> g0(c0->mu);
-                    c0->rs_bases = std::max<uint64_t>(c0->rs_bases, (base_word + (pend->bases + 31) / 32) * 32);
-                }
-                pend->reads = pend->bases = 0;
-                pend->base_word = -1;
-                return frc;
-            };
-            struct Upload {
-                PoolBuf<uint8_t> text;
-                std::thread th;
-                bool ok = true;
-            };
-            std::unique_ptr<Upload> cur, nxt;
-            auto start_upload = [&](size_t i, std::unique_ptr<Upload> &u) -> int {
-                u.reset(new Upload);
-                const uint64_t n = (uint64_t)(cuts[i].second - cuts[i].first);
-                {
-                    std::lock_guard<std::mutex> g0(c0->mu);
-                    HIPCHK(c0, hipSetDevice(c0->cfg.device));
-                    HIPCHK(c0, u->text.alloc(&c0->tok_pool, (n + tok::T_TILE - 1) / tok::T_TILE * tok::T_TILE));
-                }
-                Upload *up = u.get();
-                const char *b = cuts[i].first;
-                up->th = std::thread([c0, up, b, n, &f] { up->ok = h2d_pinned(c0, up->text.p, b, n, f.fd, (uint64_t)(b - f.p)); });
-                return MC_OK;
-            };
-            auto finish = [&](std::unique_ptr<Upload> &u) {
-                if (!u) return;
-                if (u->th.joinable()) u->th.join();
-                std::lock_guard<std::mutex> g0(c0->mu);
-                u.reset();
-            };
-            rc = cuts.empty() ? MC_OK : start_upload(0, cur);
-            if (rc) rc = gfail(g, rc, c0->err);
-            for (size_t i = 0; i < cuts.size() && rc == MC_OK; i++) {
-                cur->th.join();
-                if (!cur->ok) { rc = gfail(g, MC_EHIP, "mc_group_add_reads_file: host-to-device copy failed"); break; }
-                if (i + 1 < cuts.size()) {
-                    rc = start_upload(i + 1, nxt);
-                    if (rc) { rc = gfail(g, rc, c0->err); break; }
-                }
-                uint64_t got = 0;
-                bool declined = false;
-                {
-                    std::lock_guard<std::mutex> g0(c0->mu);
-                    rc = tokenize_chunk_locked(c0, f, cuts[i].first, cuts[i].second, cur->text.p, &got, &declined, pend.get());
-                    if (rc) rc = gfail(g, rc, c0->err);
-                }
-                if (rc != MC_OK) break;
-                if (declined) {  // (what was gathered goes first: the host's batches are appended behind it)
-                    rc = flush();
-                    if (rc != MC_OK) break;
-                    int hrc = MC_OK;
-                    try {
-                        got = mch::parse_plain_range(f, cuts[i].first, cuts[i].second, W * per_dev, [&](mch::PackedBatch &b) {
-                            if (hrc == MC_OK && b.n_reads()) hrc = group_add_host_batch(g, b.words.data(), b.offsets.data(), b.n_reads());
-                        });
-                    } catch (...) {
-                        finish(cur);
-                        finish(nxt);
-                        drop_pend();
-                        throw;
-                    }
-                    rc = hrc;
-                    if (rc != MC_OK) break;
-                }
-                total += got;
-                if (pend->reads >= W * per_dev) {
-                    rc = flush();
-                    if (rc != MC_OK) break;
-                }
-                finish(cur);
-                cur = std::move(nxt);
-            }
-            finish(cur);
-            finish(nxt);
-            if (rc == MC_OK) rc = flush();
-            drop_pend();
-            if (rc != MC_OK) return rc;
-            if (g->sw.ingest_debug)
-                fprintf(stderr, "[ingest] group: %zu chunk(s) tokenised on device %d, %llu reads in %llu exchange(s) over %zu devices\n", cuts.size(), c0->cfg.device,
-                        (unsigned long long)total, (unsigned long long)n_flushes, W);
-            if (n_reads) *n_reads = total;
-            return MC_OK;
-        }
-        const uint64_t n = mch::load_reads_file(path, g->ctx.size() * per_dev, [&](mch::PackedBatch &b) {
-            if (rc == MC_OK) rc = mc_group_add_reads_packed(g, b.words.data(), b.offsets.data(), b.n_reads());
-        });
-        if (rc != MC_OK) return rc;
-        if (n_reads) *n_reads = n;
-        return MC_OK;
-    } catch (const mch::Error &e) {
-        return gfail(g, MC_EINVAL, e.what());
-    } catch (const std::bad_alloc &) {
-        return gfail(g, MC_ENOMEM, "mc_group_add_reads_file: out of host memory");
-    }
-}
-
-int mc_group_finalize_counts(mc_group *g, uint64_t *n_distinct)
-{
-    if (!g) return MC_EINVAL;
-    uint64_t total = 0;
-    for (mc_ctx *c : g->ctx) {
-        uint64_t n = 0;
-        const int rc = mc_finalize_counts(c, &n);
-        if (rc) return gfail(g, rc, mc_last_error(c));
-        total += n;  // owners are disjoint
-    }
-    if (n_distinct) *n_distinct = total;
-    return MC_OK;
-}
-
-int mc_group_get_stats(mc_group *g, mc_stats *out)
-{
-    if (!g || !out) return MC_EINVAL;
-    mc_stats t{};
-    for (mc_ctx *c : g->ctx) {
-        mc_stats s{};
-        const int rc = mc_get_stats(c, &s);
-        if (rc) return gfail(g, rc, mc_last_error(c));
-        t.windows += s.windows; t.count_launches += s.count_launches; t.table_slots += s.table_slots; t.table_bytes += s.table_bytes;
-        t.grows += s.grows; t.spill_keys += s.spill_keys; t.solid_kmers += s.solid_kmers; t.solid_sweeps += s.solid_sweeps;
-        t.solid_list_builds += s.solid_list_builds;
-        t.long_runs += s.long_runs;
-        t.binned_runs += s.binned_runs;
-        t.dup_keys += s.dup_keys; t.dup_checks += s.dup_checks; t.dup_ms = std::max(t.dup_ms, s.dup_ms); t.dup_unchecked |= s.dup_unchecked;
-        t.left_bins = std::max(t.left_bins, s.left_bins);
-        t.count_ms = std::max(t.count_ms, s.count_ms); t.count_total_ms = std::max(t.count_total_ms, s.count_total_ms);
-        t.p1_ms = std::max(t.p1_ms, s.p1_ms); t.p2_ms = std::max(t.p2_ms, s.p2_ms); t.p3_ms = std::max(t.p3_ms, s.p3_ms);
-    }
-    *out = t;
-    return MC_OK;
-}
-
-int mc_group_bfs_batch(mc_group *g, const mc_bfs_job *jobs, uint32_t n_jobs, int min_cov, int64_t max_kmers, int64_t max_radius,
-                       mc_bfs_result *out)
-{
-    if (!g) return MC_EINVAL;
-    std::lock_guard<std::mutex> lk(g->mu);
-    const size_t W = g->ctx.size();
-    if (W == 1) {
-        const int rc = mc_bfs_batch(g->ctx[0], jobs, n_jobs, min_cov, max_kmers, max_radius, out);
-        return rc ? gfail(g, rc, mc_last_error(g->ctx[0])) : MC_OK;
-    }
-    // ---- the walk reads every device's counting table where it is (round 4): the first context gets the other tables' addresses
-    // (peer access; the same device for shares of one GPU) and looks a k-mer up in its owner's table.  No export, no copy of
-    // the solid k-mers, no second table -- and what made configs[3] impossible: 5 G gathered solid k-mers do not fit beside
-    // rank 0's counting table.  MC_GROUP_WALK=gather keeps round 3's way (and a group without peer
-    // access between all its devices has no other).
-    if (!g->sw.group_walk_gather && g->peer_all) {
-        mc_ctx *c0 = g->ctx[0];
-        const bool dbg = g->sw.ingest_debug;
-        const auto t_0 = std::chrono::steady_clock::now();
-        if (g->dirty || !c0->d_shards) {
-            std::vector<ShardWire> w(W);
-            int grc = per_rank(W, [&](size_t r) -> int {
-                std::lock_guard<std::mutex> cl(g->ctx[r]->mu);
-                return shard_describe(g->ctx[r], &w[r], false);
-            });
-            if (grc) {
-                for (mc_ctx *c : g->ctx) if (!c->err.empty()) return gfail(g, grc, c->err);
-                return gfail(g, grc, "mc_group_bfs_batch: a device's table could not be shared");
-            }
-            std::lock_guard<std::mutex> cl(c0->mu);
-            grc = shard_attach_locked(c0, w.data(), (uint32_t)W, 0, c0->sk_form ? 1 : 0);
-            if (grc) return gfail(g, grc, c0->err);
-            g->dirty = false;
-            g->solid_cov = -1;
-        }
-        const auto t_1 = std::chrono::steady_clock::now();
-        const int rc = mc_bfs_batch(c0, jobs, n_jobs, min_cov, max_kmers, max_radius, out);
-        if (dbg) fprintf(stderr, "[walk] group: tables described and attached in %.2f ms, %u walk(s) in %.2f ms\n", std::chrono::duration<double, std::milli>(t_1 - t_0).count(),
-                         n_jobs, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_1).count());
-        return rc ? gfail(g, rc, mc_last_error(c0)) : MC_OK;
-    }
-    if (g->dirty || g->solid_cov != min_cov) {
-        // ---- gather: every shard's (key, count, pointer) with count >= min_cov, side by side on the first device.  The
-        // shards are exported on all devices at once; the copies are then issued on the first device's stream with that
-        // device current, and waited for once.
-        std::vector<uint64_t> n(W, 0);
-        struct Shard { DevBuf<int64_t> k; DevBuf<int16_t> c; DevBuf<uint32_t> p; uint64_t got = 0; };
-        std::vector<Shard> sh(W);
-        int grc = per_rank(W, [&](size_t r) -> int {
-            mc_ctx *c = g->ctx[r];
-            if (hipSetDevice(c->cfg.device) != hipSuccess) return MC_EHIP;
-            int rc = mc_export_dev(c, min_cov, nullptr, nullptr, nullptr, 0, &n[r]);
-            if (rc || n[r] == 0) return rc;
-            if (sh[r].k.alloc(n[r]) != hipSuccess || sh[r].c.alloc(n[r]) != hipSuccess || sh[r].p.alloc(n[r]) != hipSuccess) return MC_ENOMEM;
-            return mc_export_dev(c, min_cov, sh[r].k.p, sh[r].c.p, sh[r].p.p, n[r], &sh[r].got);
-        });
-        if (grc) {
-            for (mc_ctx *c : g->ctx) if (!c->err.empty()) return gfail(g, grc, c->err);
-            return gfail(g, grc, "mc_group_bfs_batch: exporting the shards failed");
-        }
-        uint64_t total = 0;
-        for (size_t r = 0; r < W; r++) total += sh[r].got;
-        mc_ctx *c0 = g->ctx[0];
-        if (hipSetDevice(c0->cfg.device) != hipSuccess) return gfail(g, MC_EHIP, "hipSetDevice failed");
-        DevBuf<int64_t> all_k;
-        DevBuf<int16_t> all_c;
-        DevBuf<uint32_t> all_p;
-        if (all_k.alloc(total) != hipSuccess || all_c.alloc(total) != hipSuccess || all_p.alloc(total) != hipSuccess)
-            return gfail(g, MC_ENOMEM, "mc_group_bfs_batch: no room for the gathered shards");
-        uint64_t at = 0;
-        for (size_t r = 0; r < W; r++) {
-            const uint64_t got = sh[r].got;
-            if (got == 0) continue;
-            if (peer_copy(all_k.p + at, c0, sh[r].k.p, g->ctx[r], got * 8, c0->stream) != hipSuccess || peer_copy(all_c.p + at, c0, sh[r].c.p, g->ctx[r], got * 2, c0->stream) != hipSuccess ||
-                peer_copy(all_p.p + at, c0, sh[r].p.p, g->ctx[r], got * 4, c0->stream) != hipSuccess)
-                return gfail(g, MC_EHIP, "mc_group_bfs_batch: gathering the shards failed (peer copy)");
-            at += got;
-        }
-        if (hipStreamSynchronize(c0->stream) != hipSuccess) return gfail(g, MC_EHIP, "mc_group_bfs_batch: gathering the shards failed (peer copy)");
-        if (hipSetDevice(c0->cfg.device) != hipSuccess) return gfail(g, MC_EHIP, "hipSetDevice failed");
-        int rc = mc_clear(g->solid);
-        if (!rc) rc = mc_share_read_store(g->solid, c0);
-        uint64_t kept = 0;
-        if (!rc) rc = mc_solid_from_pairs_dev(g->solid, all_k.p, all_c.p, all_p.p, at, min_cov, &kept);
-        if (rc) return gfail(g, rc, mc_last_error(g->solid));
-        g->solid_cov = min_cov;
-        g->dirty = false;
-    }
-    const int rc = mc_bfs_batch(g->solid, jobs, n_jobs, min_cov, max_kmers, max_radius, out);
-    return rc ? gfail(g, rc, mc_last_error(g->solid)) : MC_OK;
-}
-
-}  // extern "C"

@@ -1,6 +1,6 @@
 // The library's environment switches (INTEGRATION.md lists them), read in one place.
 //
-// read_switches() fills an mc_switches from the environment: mc_create stores one in mc_ctx::sw, mc_group_create one in
+// read_switches() fills an mc_switches from the environment: mc_create stores one in mc_ctx::sw, mc_group_create (group.hip) one in
 // mc_group::sw (the group's own switches: MC_GROUP_*, MC_EXCHANGE_GATHER_READS).  A switch set after a context was created
 // changes nothing for that context.  Two exceptions read elsewhere: the pools' switches, once per process
 // (read_pool_switches: the pools outlive every context), and MC_DUP_CHECK, on every call (mcgpu.hip dup_check_on).
@@ -75,7 +75,7 @@ inline mc_switches read_switches()
     return s;
 }
 
-// The process-wide pools of table and scratch memory (mcgpu.hip TablePool, ScratchPool) read theirs once per process, when
+// The process-wide pools of table and scratch memory (context.h TablePool, ScratchPool) read theirs once per process, when
 // the library is loaded.
 struct mc_pool_switches {
     bool table_pool = true;          // MC_TABLE_POOL=0: tables go back to the driver

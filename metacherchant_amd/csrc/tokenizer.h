@@ -15,14 +15,11 @@
 // the CALLER reads the file with the host parser instead, which reproduces the reference's behaviour (and messages) in
 // those cases.  Nothing here decides a result differently from the host reader: tests compare the tables.
 #pragma once
-#include "kmer_device.h"
+#include "device_types.h"
 
 namespace mc {
 namespace tok {
 
-constexpr int T_THREADS = 256;
-constexpr uint32_t T_BYTES = 32;                        // bytes per thread of the newline passes
-constexpr uint32_t T_TILE = T_THREADS * T_BYTES;        // 8192 bytes per workgroup
 constexpr uint32_t SCAN_TILE = 4096;                    // elements per workgroup of the generic scan
 enum { TOK_BAD_CHAR = 1, TOK_BAD_STRUCTURE = 2, TOK_BAD_QUALITY = 4 };
 

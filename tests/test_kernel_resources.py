@@ -4,7 +4,6 @@ kernel arguments into scratch for the whole of k_bfs, every t.slots / t.reads be
 to 10.7 ms before anyone looked at `private_segment_fixed_size`."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
@@ -13,23 +12,31 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def _kernel_notes(tmp_path):
+    """Resources of every kernel of the library, gathered from every unit's code object; a kernel defined in two of them fails."""
     from metacherchant_amd import build
     lib = build.build_lib()
     tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
     if not all(os.path.exists(t) for t in tools):
         pytest.skip("ROCm's llvm tools are not here")
-    fat, co = str(tmp_path / "fatbin"), str(tmp_path / "k.co")
-    subprocess.check_call([tools[0], "--dump-section", ".hip_fatbin=" + fat, lib, str(tmp_path / "stripped.so")])
-    subprocess.check_call([tools[1], "--unbundle", "--type=o", "--input=" + fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    text = subprocess.check_output([tools[2], "--notes", co], text=True)
     kernels = {}
-    for block in text.split("- .agpr_count")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        kernels[name] = {k: int(v) for k, v in re.findall(r"\.(private_segment_fixed_size|vgpr_count|group_segment_fixed_size|vgpr_spill_count):\s+(\d+)", block)}
+    for co in build.code_objects(lib, str(tmp_path)):
+        text = subprocess.check_output([tools[2], "--notes", co], text=True)
+        for block in text.split("- .agpr_count")[1:]:
+            name = re.search(r"\.name:\s+(\S+)", block).group(1)
+            assert name not in kernels, "%s is in two code objects" % name
+            kernels[name] = {k: int(v) for k, v in re.findall(r"\.(private_segment_fixed_size|vgpr_count|group_segment_fixed_size|vgpr_spill_count):\s+(\d+)", block)}
     return kernels
 
 
-def test_the_walk_and_the_merge_kernel_use_no_scratch_memory(tmp_path):
+def test_every_unit_has_its_kernels_in_the_library(tmp_path):
+    """One kernel of each unit that has kernels: the table (mcgpu.hip), the counting pipeline and the key join it includes, the
+    tokeniser (reads_file.hip) and the walk (walk.hip) -- a reader that saw only the first code object would miss some."""
+    kernels = _kernel_notes(tmp_path)
+    for part in ("k_fill_empty", "k_p3_dedup", "k_dup_scatter", "k_scan_sums", "k_fa_pack", "k_bfs_reset", "k_bfs_pack", "k_bfsILi"):
+        assert any(part in n for n in kernels), (part, sorted(kernels))
+
+
+def test_the_walk_and_the_merge_kernel_use_no_scratch_memory_in_any_unit(tmp_path):
     kernels = _kernel_notes(tmp_path)
     walk = {n: r for n, r in kernels.items() if "k_bfsILi" in n or "k_bfs_scoutILi" in n}
     assert len(walk) == 12  # the walk and its scouts' kernel: three key modes x (one table, several ranks' tables) each
