@@ -351,9 +351,41 @@ int mc_save_kmers(mc_ctx *ctx, const char *bin_path, const char *stat_path, int 
                   uint64_t *n_written);
 int mc_load_kmers(mc_ctx *ctx, const char *path, int freq_threshold, uint64_t *n_records, uint64_t *n_added);
 
+/* ---- reads-classifier: per-read k-mer coverage of a second read set in this table (src/tools/ReadsClassifier.java:154-200,
+ * src/algo/PairFinder.java:32-57, src/algo/ReadsFinderInGraph.java:37-161).
+ * Reads come in the packed layout above, but whole: the caller turns N / n / . into base code 0 (A) -- what
+ * itmo!/dna/DnaQBuilder.java:45 does -- and does not split them.  For every read of length L >= k, with
+ * cov[i] = getWithZero(key of window i) (the count saturated at 32767, 0 when absent; ReadsFinderInGraph.java:63-88):
+ *   sum = sum of cov[i] (a Java int: it wraps), covered = #{i : cov[i] > 0}, last = cov[L - k];
+ *   found = findRead (:37-49,95-103): !(width < found_pct / 100.0) && (width == 1 || (width != 0 && |width - theory| <= std))
+ *           with cov_mean = (sum + last (k - 1)) / L, width = (covered + [last > 0] (k - 1)) / L, theory = 1 - e^-cov_mean,
+ *           std = z sqrt(e^-cov_mean (1 - e^-cov_mean) / L), all in double.
+ * A read shorter than k is not found and its numbers are 0.
+ * flags & MC_CLASSIFY_CORRECTION: findReadWithCorrection (:121-161).  d_bad_pos[r] is the only position of read r whose phred is
+ * below 10, -1 when there is none, -2 when there are several (d_bad_pos may be NULL: no read has one).  A read with exactly one
+ * such position p is found when one of the four reads with base p set to 0..3 passes findRead with the threshold 0.9 -- a
+ * constant in the reference, whatever found_pct says; only the <= k windows that cover p are looked up again.  sum / covered /
+ * last stay those of the read as given.
+ * The table is read as mc_get reads it: call after mc_finalize_counts.  A table of hash keys still in minimizer bins (mc_get
+ * above) is moved to hash-prefix regions first, once and for good (the cost of one table rebuild); nothing is ever swept per call.
+ * Errors: MC_ESTATE before mc_finalize_counts; MC_EINVAL for null pointers or found_pct outside 0 .. 100.
+ * mc_classify_reads takes host pointers (words: ceil(n_bases / 32) + 1 entries as above), mc_classify_reads_dev device ones. */
+typedef struct {
+    int32_t sum;     /* sum of the windows' coverages (int32 wrap-around, as the reference's int) */
+    int32_t covered; /* windows with coverage > 0 */
+    int16_t last;    /* coverage of the last window */
+    uint8_t found;   /* the verdict (with the correction when asked for) */
+    uint8_t pad;
+} mc_read_cov;
+#define MC_CLASSIFY_CORRECTION 1
+int mc_classify_reads_dev(mc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_read_offsets, uint64_t n_reads,
+                          const int32_t *d_bad_pos, int found_pct, double z, int flags, mc_read_cov *d_out);
+int mc_classify_reads(mc_ctx *ctx, const uint64_t *words, const uint64_t *read_offsets, uint64_t n_reads,
+                      const int32_t *bad_pos, int found_pct, double z, int flags, mc_read_cov *out);
+
 /* ---- measurement */
 typedef struct {
-    uint64_t windows;        /* k-mer occurrences counted so far */
+    uint64_t windows;       /* k-mer occurrences counted so far */
     uint64_t count_launches; /* counting passes: launches of the direct kernel, or runs of the partitioned pipeline */
     double count_ms;         /* their summed device time (HIP events on the context's stream) */
     double count_total_ms;   /* device time of all counting-phase kernels */

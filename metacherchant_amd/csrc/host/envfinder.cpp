@@ -18,6 +18,7 @@
 #include <cmath>
 #include <functional>
 #include <limits>
+#include <memory>
 #include <set>
 #include <sstream>
 #include <thread>
@@ -1247,6 +1248,149 @@ uint64_t load_reads_file(const std::string &path, size_t max_reads, const std::f
         sink(batch);
     }
     return delivered;
+}
+
+// ------------------------------------------------------------------------------------------ whole reads with qualities
+
+struct DnaQReader::Impl {
+    std::string path;
+    Compression comp = COMP_NONE;
+    bool fastq = false;
+    int offset = 64;
+    std::unique_ptr<LineSource> src;
+    bool done = false;
+    std::string line, data, qual;
+    // FastqReader.readNextDataLine: empty lines skipped, a line starting with '@' or '+', then the content line
+    bool fastq_line(std::string &out)
+    {
+        for (;;) {
+            if (!src->getline(line)) return false;
+            if (!line.empty()) break;
+        }
+        if (line[0] != '@' && line[0] != '+') throw Error("Unknown structure of fastq file! Waiting \"@ID\" or \"+ID\" string");
+        if (!src->getline(out)) throw Error("Unexpected end of file. File is corrupted/Format mismatch.");
+        return true;
+    }
+    bool fastq_record()
+    {
+        if (!fastq_line(data)) return false;
+        if (!fastq_line(qual)) throw Error("Unexpected end of file. File is corrupted/Format mismatch.");
+        if (data.size() != qual.size()) throw Error("Bad DnaQ record: length of chars and quality is not the same.");
+        return true;
+    }
+    // FastaWithNsReader.readNextDataLine
+    bool fasta_record()
+    {
+        data.clear();
+        while (src->getline(line)) {
+            if (!line.empty() && (line[0] == '>' || line[0] == ';')) {
+                if (!data.empty()) return true;
+            } else {
+                data += line;
+            }
+        }
+        return !data.empty();
+    }
+};
+
+static bool unknown_base(char c) { return c == 'N' || c == 'n' || c == '.'; }
+
+DnaQReader::DnaQReader(const std::string &path) : impl_(new Impl)
+{
+    Impl &I = *impl_;
+    I.path = path;
+    const size_t slash = path.find_last_of('/');
+    std::string name = lower(slash == std::string::npos ? path : path.substr(slash + 1));
+    if (ends_with(name, ".gz")) { I.comp = COMP_GZ; name.resize(name.size() - 3); }
+    if (ends_with(name, ".bz2")) { I.comp = COMP_BZ2; name.resize(name.size() - 4); }
+    bool binq, fasta;
+    reads_format_of(name, &binq, &I.fastq, &fasta);
+    if (binq) { delete impl_; throw Error("Illegal format binq: the reads-classifier reads FASTA and FASTQ files"); }
+    if (!I.fastq && !fasta) { delete impl_; throw Error("Can't detect file format for file '" + name + "'"); }
+    try {
+        if (I.fastq) {  // ReadersUtils.determineQualityFormat: a pass over the first 1000 records with Illumina
+            I.src.reset(new LineSource(path, I.comp));
+            bool sanger = false;
+            for (int r = 0; r < 1000 && !sanger && I.fastq_record(); r++)
+                for (size_t i = 0; i < I.data.size(); i++)
+                    if (!unknown_base(I.data[i]) && ((unsigned char)I.qual[i] < 64 || (unsigned char)I.qual[i] > 126)) { sanger = true; break; }
+            I.offset = sanger ? 33 : 64;
+        }
+        I.src.reset(new LineSource(path, I.comp));
+    } catch (...) {
+        delete impl_;
+        throw;
+    }
+}
+
+DnaQReader::~DnaQReader() { delete impl_; }
+
+size_t DnaQReader::read(DnaQBatch &b, size_t max_reads)
+{
+    Impl &I = *impl_;
+    if (b.offsets.empty()) b.offsets.assign(1, 0);
+    size_t got = 0;
+    while (!I.done && got < max_reads) {
+        if (!(I.fastq ? I.fastq_record() : I.fasta_record())) { I.done = true; break; }
+        const size_t n = I.data.size();
+        for (size_t i = 0; i < n; i++) {
+            const char c = I.data[i];
+            if (unknown_base(c)) {  // DnaQBuilder.unsafeAppendUnknown: base 0, phred 0
+                b.codes.push_back(0);
+                b.phred.push_back(0);
+                continue;
+            }
+            const int code = code_of(c);
+            if (code < 0)
+                throw Error(std::string("read contains the character '") + c +
+                            "': IUPAC codes other than N are replaced at random by the reference "
+                            "(itmo!/dna/DnaTools.java:66-117), which has no defined result; rejecting the input");
+            int ph = 20;  // ReadersUtils.DEFAULT_PHRED_FOR_FASTA
+            if (I.fastq) {
+                const int qc = (unsigned char)I.qual[i];
+                if (qc < I.offset || qc > 126) throw Error("Invalid quality code char: \"" + std::string(1, (char)qc) + "\" char code = " + std::to_string(qc));
+                ph = (qc - I.offset) & 63;  // (DnaQ keeps the phred in 6 bits of a byte: DnaQ.phredAt)
+            }
+            b.codes.push_back((uint8_t)code);
+            b.phred.push_back((uint8_t)ph);
+        }
+        b.offsets.push_back(b.codes.size());
+        got++;
+    }
+    return got;
+}
+
+std::string java_format_2f(double x)
+{
+    if (x != x) return "NaN";
+    if (std::isinf(x)) return x > 0 ? "Infinity" : "-Infinity";
+    // the shortest decimal that reads back as x (Double.toString's digits), then HALF_UP to two places
+    char buf[64];
+    for (int prec = 1; prec <= 17; prec++) {
+        snprintf(buf, sizeof buf, "%.*e", prec - 1, x < 0 ? -x : x);
+        if (strtod(buf, nullptr) == (x < 0 ? -x : x)) break;
+    }
+    std::string m = buf;  // d.ddddde[+-]XX
+    const size_t e = m.find('e');
+    const int exp10 = atoi(m.c_str() + e + 1);
+    std::string digits;
+    for (size_t i = 0; i < e; i++)
+        if (m[i] != '.') digits.push_back(m[i]);
+    // value = 0.digits x 10^(exp10 + 1): integer part and two decimals, the third decides
+    const int point = exp10 + 1;  // digits before the decimal point
+    std::string ip, fp;
+    if (point <= 0) { ip = "0"; fp = std::string((size_t)-point, '0') + digits; }
+    else if ((size_t)point >= digits.size()) { ip = digits + std::string((size_t)point - digits.size(), '0'); }
+    else { ip = digits.substr(0, (size_t)point); fp = digits.substr((size_t)point); }
+    while (fp.size() < 3) fp.push_back('0');
+    std::string out = ip + fp.substr(0, 2);
+    if (fp[2] >= '5') {
+        int i = (int)out.size() - 1;
+        while (i >= 0 && out[(size_t)i] == '9') out[(size_t)i--] = '0';
+        if (i >= 0) out[(size_t)i]++; else out.insert(out.begin(), '1');
+    }
+    std::string body = out.substr(0, out.size() - 2) + "." + out.substr(out.size() - 2);
+    return std::signbit(x) ? "-" + body : body;
 }
 
 // ------------------------------------------------------------------------------------------ Environment

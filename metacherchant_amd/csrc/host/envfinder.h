@@ -133,6 +133,35 @@ const char *plain_record_start(const PlainReadsFile &f, const char *q);
 // the serial parser over [b, e), which must begin at a record start; returns the reads delivered
 uint64_t parse_plain_range(const PlainReadsFile &f, const char *b, const char *e, size_t max_reads, const std::function<void(PackedBatch &)> &sink);
 
+// ---- whole reads with their qualities, the reads-classifier's -r files: itmo!/io/ReadersUtils.java:185-215 readDnaQLazy.
+// FASTQ (itmo!/io/readers/FastqReader.java:70-80): N / n / . become base 0 (A) with phred 0 (itmo!/dna/DnaQBuilder.java:45),
+// other bases take the phred of their quality char -- Illumina (+64) unless one of the first 1000 records has a char that is
+// not (ReadersUtils.java:63-77), else Sanger (+33) -- kept as DnaQ.phredAt reads it back: in 6 bits.  FASTA (FastaWithNsReader):
+// the lines between two '>' / ';' lines joined, empty records skipped, N / n / . as above, phred 20 for every other base.
+// Reads are neither split nor dropped.  Plain, .gz or .bz2.
+struct DnaQBatch {
+    std::vector<uint8_t> codes;     // base codes A0 G1 C2 T3 (N -> 0)
+    std::vector<uint8_t> phred;     // 0 .. 63
+    std::vector<uint64_t> offsets;  // n_reads + 1
+    uint64_t n_reads() const { return offsets.empty() ? 0 : offsets.size() - 1; }
+    void clear() { codes.clear(); phred.clear(); offsets.assign(1, 0); }
+};
+class DnaQReader {
+public:
+    explicit DnaQReader(const std::string &path);  // throws Error on a file it cannot read or whose format it cannot tell
+    ~DnaQReader();
+    DnaQReader(const DnaQReader &) = delete;
+    DnaQReader &operator=(const DnaQReader &) = delete;
+    // appends up to max_reads records to b; returns how many (0: the file is done)
+    size_t read(DnaQBatch &b, size_t max_reads);
+
+private:
+    struct Impl;
+    Impl *impl_;
+};
+// String.format("%.2f", x) for a double: HALF_UP on the shortest decimal that reads back as x (Java's FormattedFloatingDecimal)
+std::string java_format_2f(double x);
+
 // ---- 2-bit packed k-mers (k <= 63): base i of the string is bits 2(k-1-i)+1..2(k-1-i), codes A0 G1 C2 T3,
 // the layout of mc_bfs_result's hi/lo words (include/mcgpu.h)
 typedef unsigned __int128 kmer_t;

@@ -13,6 +13,7 @@
 #include <ctime>
 #include <functional>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -66,9 +67,15 @@ struct Options {
     bool bothdirs = false, forcehash = false, trim = false, merge = false, cont = false, force = false, help = false;
     unsigned long long capacity_hint = 0;
     std::vector<int> devices;  // --devices 0,1,...: several GPUs as one table (mc_group_*); empty: --device alone
+    // --tool reads-classifier (src/tools/ReadsClassifier.java:42-95)
+    std::vector<std::string> input_files, read_files;
+    bool correction = false, interval95 = false;
+    long long found_threshold = 90;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
+// Every tool has its own parameters (itmo!/utils/tool/Tool.java: a tool's addParameter calls plus the launch options), and a
+// short option may mean something else in another tool: -o is --output here and --output-dir in reads-classifier.
 const OptSpec SPECS[] = {
     {"k", "k", 0}, {"reads", "i", 2}, {"seq", nullptr, 0}, {"hicseq", nullptr, 0}, {"output", "o", 0},
     {"maxkmers", nullptr, 0}, {"maxradius", nullptr, 0}, {"coverage", nullptr, 0}, {"bothdirs", nullptr, 1},
@@ -78,9 +85,34 @@ const OptSpec SPECS[] = {
     {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"output-dir", nullptr, 0}, {"env", "e", 2}, {"geneid", "g", 0},
 };
 
-const OptSpec *find_spec(const std::string &tok)
+// --tool reads-classifier: its parameters (ReadsClassifier.java:42-95) and the launch options
+const OptSpec CLASSIFIER_SPECS[] = {
+    {"k", "k", 0}, {"input-files", "i", 2}, {"read-files", "r", 2}, {"output-dir", "o", 0}, {"correction", "corr", 1},
+    {"hash", nullptr, 0}, {"interval95", nullptr, 1}, {"found-threshold", "found", 0},
+    {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
+};
+
+struct SpecTable {
+    const OptSpec *b, *e;
+};
+
+// the tool a command line names (the last -t / --tool wins, as every option's last value does): it decides the parameter table
+std::string tool_of(int argc, char **argv)
 {
-    for (const OptSpec &s : SPECS) {
+    std::string tool = "environment-finder";
+    for (int i = 1; i < argc; i++) {
+        const std::string tok = argv[i];
+        if ((tok == "-t" || tok == "--tool") && i + 1 < argc) tool = argv[++i];
+        else if (tok.rfind("--tool=", 0) == 0) tool = tok.substr(7);
+    }
+    return tool;
+}
+
+const OptSpec *find_spec(SpecTable t, const std::string &tok)
+{
+    for (const OptSpec *p = t.b; p != t.e; p++) {
+        const OptSpec &s = *p;
         if (tok == std::string("--") + s.name) return &s;
         if (s.shortopt && tok == std::string("-") + s.shortopt) return &s;
     }
@@ -103,6 +135,8 @@ long long parse_int(const std::string &name, const std::string &v)
 
 Options parse_args(int argc, char **argv)
 {
+    const SpecTable specs = tool_of(argc, argv) == "reads-classifier" ? SpecTable{std::begin(CLASSIFIER_SPECS), std::end(CLASSIFIER_SPECS)}
+                                                                      : SpecTable{std::begin(SPECS), std::end(SPECS)};
     std::map<std::string, std::vector<std::string>> got;
     for (int i = 1; i < argc; i++) {
         std::string tok = argv[i], inline_val;
@@ -113,14 +147,14 @@ Options parse_args(int argc, char **argv)
             tok = tok.substr(0, eq);
             has_inline = true;
         }
-        const OptSpec *s = find_spec(tok);
+        const OptSpec *s = find_spec(specs, tok);
         if (!s) throw Error("Cannot parse command line: Unrecognized option: " + tok);
         auto &vals = got[s->name];
         vals.clear();
         if (has_inline) {
             vals.push_back(inline_val);
         } else if (s->kind == 2) {
-            while (i + 1 < argc && !find_spec(argv[i + 1]) && argv[i + 1][0] != '-') vals.push_back(argv[++i]);
+            while (i + 1 < argc && !find_spec(specs, argv[i + 1]) && argv[i + 1][0] != '-') vals.push_back(argv[++i]);
         } else if (s->kind == 1) {
             if (i + 1 < argc && argv[i + 1][0] != '-') vals.push_back(argv[++i]);
             else vals.push_back("true");  // option without an argument, itmo!/utils/tool/Tool.java:650-652
@@ -144,6 +178,11 @@ Options parse_args(int argc, char **argv)
     };
     multi("reads", o.reads);
     multi("env", o.env);
+    multi("input-files", o.input_files);
+    multi("read-files", o.read_files);
+    if (auto v = val("correction")) o.correction = java_bool(*v);
+    if (auto v = val("interval95")) o.interval95 = java_bool(*v);
+    if (auto v = val("found-threshold")) o.found_threshold = parse_int("found-threshold", *v);
     if (auto v = val("seq")) o.seq = *v;
     if (auto v = val("hicseq")) o.hicseq = *v;
     if (auto v = val("output")) o.output = *v;
@@ -208,6 +247,15 @@ void usage()
     puts("      --merge [<arg>]      draw single environment for multiple input sequences? (default false)");
     puts("Input parameters of --tool environment-finder-multi (CPU only): -e/--env <graph.txt files>, --seq, -o/--output, -g/--geneid (default 1)");
     puts("Input parameters of --tool kmer-counter: -k, -i/--reads, --hash, --output-dir <dir> (default <work-dir>/kmers)");
+    puts("Input parameters of --tool reads-classifier (splits the reads of -r into found / not found in the graph of -i):");
+    puts("  -k, --k <arg>                  k-mer size (MANDATORY)");
+    puts("  -i, --input-files <args>       reads for the de Bruijn graph, or its <name>.kmers.bin from kmer-counter (MANDATORY)");
+    puts("  -r, --read-files <args>        one FASTQ / FASTA file of reads to classify, or two of paired reads (MANDATORY)");
+    puts("  -o, --output-dir <arg>         directory of found_{1,2,s}.fastq, not_found_{1,2,s}.fastq (default <work-dir>/reads_classifier)");
+    puts("  -corr, --correction [<arg>]    try the four bases at a read's one low-quality position (default false)");
+    puts("      --hash <arg>               hash function to use for k > 31: poly or fnv1a (default poly)");
+    puts("      --interval95 [<arg>]       set the interval width to probability 0.95 (default false)");
+    puts("  -found, --found-threshold <arg>  minimum coverage breadth for class `found`, 0 - 100 % (default 90)");
     puts("Launch options: -w/--work-dir <dir> (default workDir), -c/--continue, --force, -v/--verbose, -h/--help,");
     puts("                -t/--tool <name>, -p/--available-processors <n> and -m/--memory <arg> (accepted, unused),");
     puts("                --device <n> (GPU ordinal), --devices <a,b,...|a-b> (several GPUs as one table: reads dealt to them,");
@@ -277,9 +325,9 @@ struct Engine {
 };
 
 // the reads of all --reads files into the table; returns hm.size()
-uint64_t load_reads(const Options &o, Engine &e)
+uint64_t load_reads(const std::vector<std::string> &files, Engine &e)
 {
-    for (const std::string &path : o.reads) {
+    for (const std::string &path : files) {
         const size_t slash = path.find_last_of('/');
         info("Loading file " + (slash == std::string::npos ? path : path.substr(slash + 1)) + "...");
         uint64_t n = 0;
@@ -316,7 +364,7 @@ int run_kmer_counter(const Options &o)
     Engine E;
     E.open(cfg, {});
     mc_ctx *ctx = E.c;
-    const uint64_t size = load_reads(o, E);
+    const uint64_t size = load_reads(o.reads, E);
     // ReadersUtils.readDnaLazy(file).name(): the first file's name without its format extension
     std::string name = o.reads[0];
     const size_t slash = name.find_last_of('/');
@@ -368,12 +416,213 @@ int run_multi(const Options &o)
     return 0;
 }
 
+// --tool reads-classifier (src/tools/ReadsClassifier.java:154-200, src/algo/PairFinder.java:32-57): the reads of -r split by how
+// well their k-mers are covered in the graph of -i (mc_classify_reads), written to six FASTQ files.  The reference fills its four
+// lists from a thread pool, so their order is only defined at -p 1; here it is that order: input order within every list.
+
+// WritersUtils.writeDnaQsToFastqFile (itmo!/io/writers/FastqDedicatedWriter.java:39-60): "@<n>" counting from 1 (DataCounter), the
+// bases with N printed as A (the DnaQ holds base 0 there), "+", the qualities as Illumina (phred + 64, Illumina.getPhredChar)
+struct FastqOut {
+    FILE *f = nullptr;
+    unsigned long long n = 0;
+    std::string path, rec;
+    explicit FastqOut(const std::string &p) : path(p)
+    {
+        f = fopen(p.c_str(), "wb");
+        if (!f) throw Error("Failed to write to file " + p);
+        setvbuf(f, nullptr, _IOFBF, 1 << 20);
+    }
+    ~FastqOut() { if (f) fclose(f); }
+    void close()
+    {
+        if (f && (fclose(f) != 0)) { f = nullptr; throw Error("Failed to write to file " + path); }
+        f = nullptr;
+    }
+    void put(const uint8_t *codes, const uint8_t *phred, size_t len)
+    {
+        if (len == 0) throw Error("Empty DnaQ!");
+        rec = "@" + std::to_string(++n) + "\n";
+        const size_t at = rec.size();
+        rec.resize(at + 2 * len + 4);
+        char *b = &rec[at], *q = b + len + 3;
+        for (size_t i = 0; i < len; i++) {
+            b[i] = "AGCT"[codes[i] & 3];
+            if (phred[i] > 62) throw Error("Invalid quality code byte: " + std::to_string(phred[i]));
+            q[i] = (char)(phred[i] + 64);
+        }
+        b[len] = '\n'; b[len + 1] = '+'; b[len + 2] = '\n'; q[len] = '\n';
+        if (fwrite(rec.data(), 1, rec.size(), f) != rec.size()) throw Error("Failed to write to file " + path);
+    }
+};
+
+// records kept aside (bases and phreds, length first) and appended to a FastqOut later: the "second only" halves of the _s files
+struct SideList {
+    FILE *f = tmpfile();
+    SideList() { if (!f) throw Error("Failed to create a temporary file"); }
+    ~SideList() { if (f) fclose(f); }
+    void put(const uint8_t *codes, const uint8_t *phred, size_t len)
+    {
+        const uint64_t n = len;
+        if (fwrite(&n, 8, 1, f) != 1 || fwrite(codes, 1, len, f) != len || fwrite(phred, 1, len, f) != len) throw Error("Failed to write a temporary file");
+    }
+    void append_to(FastqOut &out)
+    {
+        rewind(f);
+        std::vector<uint8_t> c, q;
+        uint64_t n = 0;
+        while (fread(&n, 8, 1, f) == 1) {
+            c.resize(n);
+            q.resize(n);
+            if (fread(c.data(), 1, n, f) != n || fread(q.data(), 1, n, f) != n) throw Error("Failed to read a temporary file");
+            out.put(c.data(), q.data(), n);
+        }
+    }
+};
+
+// one batch of whole reads through mc_classify_reads: N is base 0 already (DnaQReader), bad_pos as findReadWithCorrection counts
+std::vector<mc_read_cov> classify_batch(mc_ctx *ctx, const DnaQBatch &b, size_t n, const Options &o)
+{
+    std::vector<mc_read_cov> out(n);
+    if (n == 0) return out;
+    const uint64_t n_bases = b.offsets[n];
+    std::vector<uint64_t> words((n_bases + 31) / 32 + 1, 0);
+    for (uint64_t i = 0; i < n_bases; i++) words[i >> 5] |= (uint64_t)(b.codes[i] & 3) << (62 - 2 * (i & 31));
+    std::vector<int32_t> bad;
+    if (o.correction) {
+        bad.assign(n, -1);
+        for (size_t r = 0; r < n; r++)
+            for (uint64_t i = b.offsets[r]; i < b.offsets[r + 1]; i++)
+                if (b.phred[i] < 10) {
+                    if (bad[r] != -1) { bad[r] = -2; break; }
+                    bad[r] = (int32_t)(i - b.offsets[r]);
+                }
+    }
+    MC_CHECK(ctx, mc_classify_reads(ctx, words.data(), b.offsets.data(), n, o.correction ? bad.data() : nullptr, (int)o.found_threshold,
+                                    o.interval95 ? 1.96 : 1.0, o.correction ? MC_CLASSIFY_CORRECTION : 0, out.data()));
+    return out;
+}
+
+int run_reads_classifier(const Options &o)
+{
+    // (every parameter is checked before a device is opened)
+    if (o.k < 0) throw Error("Parameter 'k' is mandatory");
+    if (o.input_files.empty()) throw Error("Parameter 'input-files' is mandatory");
+    if (o.read_files.empty()) throw Error("Parameter 'read-files' is mandatory");
+    if (o.k < 1 || o.k > 63)
+        throw Error("k = " + std::to_string(o.k) + " is not supported: this build handles k <= 31 (packed keys) and 32 <= k <= 63 (hash keys)");
+    if (o.found_threshold < 0 || o.found_threshold > 100) throw Error("--found-threshold must be within 0 .. 100 (a percentage of the read)");
+    if (!open_work_dir(o, "k=" + std::to_string(o.k) + "\n")) return 0;
+    const std::string out_dir = o.output_dir.empty() ? o.work_dir + "/reads_classifier" : o.output_dir;
+    write_file(out_dir + "/.keep", "");  // outputDir.mkdirs()
+    remove((out_dir + "/.keep").c_str());
+
+    // loadGraph (ReadsClassifier.java:98-118)
+    int mode = MC_KEY_PACKED;
+    if (o.k > 31) {  // determineHashFunction (:121-132)
+        std::string h = o.hash;
+        for (char &c : h) c = (char)tolower((unsigned char)c);
+        if (h == "fnv1a") { info("Using FNV1a hash function"); mode = MC_KEY_FNV1A; }
+        else { info("Using default polynomial hash function"); mode = MC_KEY_POLY; }
+    }
+    std::string first = o.input_files[0];
+    const size_t slash = first.find_last_of('/');
+    if (slash != std::string::npos) first = first.substr(slash + 1);
+    for (char &c : first) c = (char)tolower((unsigned char)c);
+    const bool kmers_bin = first.size() >= 9 && first.compare(first.size() - 9, 9, "kmers.bin") == 0;
+    mc_config cfg{};
+    cfg.k = o.k;
+    cfg.key_mode = mode;
+    cfg.device = o.device;
+    cfg.capacity_hint = o.capacity_hint;
+    Engine E;
+    E.open(cfg, {});
+    mc_ctx *ctx = E.c;
+    uint64_t n_distinct = 0;
+    if (kmers_bin) {  // IOUtils.loadKmers(files, 0, ...)
+        for (const std::string &path : o.input_files) MC_CHECK(ctx, mc_load_kmers(ctx, path.c_str(), 0, nullptr, nullptr));
+        E.finalize(&n_distinct);
+        info("Hashtable size: " + std::to_string(n_distinct) + " kmers");
+    } else {
+        if (o.k > 31) info("Reading hashes of k-mers instead");
+        n_distinct = load_reads(o.input_files, E);
+    }
+
+    info("Loading reads...");
+    const bool paired = o.read_files.size() == 2;
+    DnaQReader r1(o.read_files[0]);
+    std::unique_ptr<DnaQReader> r2(paired ? new DnaQReader(o.read_files[1]) : nullptr);
+    info(o.correction ? "Searching for corrected reads in graph..." : "Searching for reads in graph...");
+    FastqOut found1(out_dir + "/found_1.fastq"), found2(out_dir + "/found_2.fastq"), nf1(out_dir + "/not_found_1.fastq"),
+        nf2(out_dir + "/not_found_2.fastq"), found_s(out_dir + "/found_s.fastq"), nf_s(out_dir + "/not_found_s.fastq");
+    SideList found_s_tail, nf_s_tail;
+    long long both = 0, first_only = 0, second_only = 0, neither = 0;
+    constexpr size_t BATCH = 1u << 20;
+    DnaQBatch b1, b2;
+    for (;;) {
+        b1.clear();
+        b2.clear();
+        size_t n = r1.read(b1, BATCH);
+        if (paired) n = r2->read(b2, n);  // PairSource (itmo!/io/sources/PairSource.java:35-45): pairs end with the shorter file
+        if (n == 0) break;
+        const std::vector<mc_read_cov> c1 = classify_batch(ctx, b1, n, o);
+        const std::vector<mc_read_cov> c2 = paired ? classify_batch(ctx, b2, n, o) : std::vector<mc_read_cov>(n);
+        for (size_t i = 0; i < n; i++) {
+            const uint8_t *s1 = b1.codes.data() + b1.offsets[i], *q1 = b1.phred.data() + b1.offsets[i];
+            const size_t l1 = b1.offsets[i + 1] - b1.offsets[i];
+            const uint8_t *s2 = paired ? b2.codes.data() + b2.offsets[i] : nullptr, *q2 = paired ? b2.phred.data() + b2.offsets[i] : nullptr;
+            const size_t l2 = paired ? b2.offsets[i + 1] - b2.offsets[i] : 0;
+            const bool f1 = c1[i].found != 0;
+            const bool f2 = l2 == 0 ? !f1 : c2[i].found != 0;  // (a single-end read is paired with an empty one)
+            if (f1 && f2) {
+                both++;
+                found1.put(s1, q1, l1);
+                found2.put(s2, q2, l2);
+            } else if (f1) {
+                first_only++;
+                if (l1) found_s.put(s1, q1, l1);
+                if (l2) nf_s.put(s2, q2, l2);
+            } else if (f2) {
+                second_only++;
+                if (l2) found_s_tail.put(s2, q2, l2);
+                if (l1) nf_s_tail.put(s1, q1, l1);
+            } else {
+                neither++;
+                nf1.put(s1, q1, l1);
+                nf2.put(s2, q2, l2);
+            }
+        }
+        if (paired && n < BATCH) break;  // (one of the files is done)
+    }
+
+    // FoundStats (ReadsClassifier.java:203-260): Java ints, String.format("%.2f")
+    const long long total = 2 * (both + first_only + second_only + neither), found = 2 * both + first_only + second_only,
+                    not_found = 2 * neither + first_only + second_only, pairs = 2 * (both + neither);
+    info("|\tTotal: " + std::to_string(total) + " reads");
+    info("|\tPaired: " + std::to_string(pairs) + " reads");
+    info("|\tTotal quality: " + java_format_2f(100 * (double)pairs / (double)total) + " %");
+    info("|\tFound: " + std::to_string(found) + " reads");
+    info("|\tPercent of found reads: " + java_format_2f(100 * (double)found / (double)total) + " %");
+    info("|\tQuality of found bin: " + java_format_2f((double)both * 2 / (double)(both * 2 + first_only + second_only) * 100) + " %");
+    info("|\tNot found: " + std::to_string(not_found) + " reads");
+    info("|\tPercent of not found reads: " + java_format_2f(100 * (double)not_found / (double)total) + " %");
+    info("|\tQuality of not found bin: " + java_format_2f((double)neither * 2 / (double)(neither * 2 + first_only + second_only) * 100) + " %");
+    info("Writing classified reads...");
+    found_s_tail.append_to(found_s);
+    nf_s_tail.append_to(nf_s);
+    for (FastqOut *f : {&found1, &found2, &nf1, &nf2, &found_s, &nf_s}) f->close();
+    info("Reads have been written. Finishing...");
+    write_file(o.work_dir + "/SUCCESS", "");
+    return 0;
+}
+
 int run(const Options &o)
 {
     if (o.tool == "kmer-counter") return run_kmer_counter(o);
     if (o.tool == "environment-finder-multi") return run_multi(o);
+    if (o.tool == "reads-classifier") return run_reads_classifier(o);
     if (o.tool != "environment-finder")
-        throw Error("Tool '" + o.tool + "' is not part of this build: only environment-finder, kmer-counter and environment-finder-multi are");
+        throw Error("Tool '" + o.tool + "' is not part of this build: only environment-finder, kmer-counter, environment-finder-multi and "
+                    "reads-classifier are");
     if (o.k < 0) throw Error("Parameter 'k' is mandatory");
     if (o.seq.empty()) throw Error("Parameter 'seq' is mandatory");
     if (o.output.empty()) throw Error("Parameter 'output' is mandatory");
@@ -409,7 +658,7 @@ int run(const Options &o)
     E.set_coverage_hint(o.coverage);
 
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t n_distinct = load_reads(o, E);
+    const uint64_t n_distinct = load_reads(o.reads, E);
     logline("DEBUG", "k-mers HM size = " + group_digits(n_distinct));
     const auto t1 = std::chrono::steady_clock::now();
 

@@ -60,6 +60,15 @@ class Stats(C.Structure):
                 ("binned_runs", C.c_uint64)]
 
 
+class ReadCov(C.Structure):
+    """mc_read_cov: one read's coverage in the table (include/mcgpu.h mc_classify_reads)"""
+    _fields_ = [("sum", C.c_int32), ("covered", C.c_int32), ("last", C.c_int16), ("found", C.c_uint8), ("pad", C.c_uint8)]
+
+
+READ_COV_DTYPE = np.dtype([("sum", np.int32), ("covered", np.int32), ("last", np.int16), ("found", np.uint8), ("pad", np.uint8)])
+CLASSIFY_CORRECTION = 1  # mc_classify_reads flags: findReadWithCorrection
+
+
 # every symbol include/mcgpu.h declares; tests check that the library exports all of them
 EXPORTS = [
     "mc_abi_version", "mc_create", "mc_destroy", "mc_clear", "mc_set_coverage_hint", "mc_set_read_pointers", "mc_share_read_store", "mc_last_error", "mc_set_stream", "mc_add_reads_packed",
@@ -69,7 +78,7 @@ EXPORTS = [
     "mc_group_finalize_counts", "mc_group_bfs_batch", "mc_group_get_stats", "mc_add_keys_dev", "mc_superkmer_capacity", "mc_extract_superkmers_dev", "mc_add_superkmers_dev",
     "mc_superkmer_fine_buckets", "mc_extract_superkmers_binned_dev", "mc_add_superkmers_binned_dev",
     "mc_read_store_seek", "mc_read_store_tell", "mc_read_store_import_dev", "mc_get_stats", "mc_reset_stats", "mc_trim", "mc_synth_reads_dev", "mc_synth_genome",
-    "mc_shard_export", "mc_shard_attach", "mc_shard_detach",
+    "mc_shard_export", "mc_shard_attach", "mc_shard_detach", "mc_classify_reads", "mc_classify_reads_dev",
 ]
 
 _LIB = None
@@ -147,6 +156,9 @@ def load():
     L.mc_trim.argtypes = [vp]
     L.mc_synth_reads_dev.argtypes = [vp, u64, u64, u64, u64, u64, u64, C.c_uint32, C.c_uint32, vp, vp]
     L.mc_synth_genome.argtypes = [u64, u64, u64, C.POINTER(C.c_uint8)]
+    if hasattr(L, "mc_classify_reads"):  # (a tuning build of an older revision, MC_LIB)
+        L.mc_classify_reads.argtypes = [vp, u64p, u64p, u64, C.POINTER(C.c_int32), i32, C.c_double, i32, C.POINTER(ReadCov)]
+        L.mc_classify_reads_dev.argtypes = [vp, vp, vp, u64, vp, i32, C.c_double, i32, vp]
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -280,6 +292,42 @@ class Context:
         self._chk(self._L.mc_kmer_keys(self._h, _p(hi, C.c_uint64) if hi is not None else None,
                                        _p(lo, C.c_uint64), len(lo), _p(out, C.c_int64)))
         return out
+
+    # ---- reads-classifier
+    def classify_reads(self, codes_or_words, offsets, bad_pos=None, found=90, z=1.0, correction=False, packed=None):
+        """Per-read coverage of a read set in this table (mc_classify_reads): returns numpy arrays sum, covered, last, found.
+        codes_or_words: base codes 0..3 (uint8, one a base; N already turned into 0) or the packed words with their pad word
+        (uint64; packed=None tells them apart by dtype); offsets: n_reads + 1 base offsets.  bad_pos: per read the only position
+        with phred < 10, -1 for none, -2 for several (None: none anywhere).  found: the breadth threshold in percent; z: 1 or 1.96."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        a = np.asarray(codes_or_words)
+        if packed is None:
+            packed = a.dtype == np.uint64
+        if packed:
+            words = np.ascontiguousarray(a, dtype=np.uint64)
+        else:
+            codes = np.ascontiguousarray(a, dtype=np.uint8)
+            words = np.zeros((len(codes) + 31) // 32 + 1, dtype=np.uint64)
+            if len(codes):
+                pad = (-len(codes)) % 32
+                c = np.concatenate([codes & 3, np.zeros(pad, dtype=np.uint8)]).reshape(-1, 32).astype(np.uint64)
+                words[:len(c)] = np.bitwise_or.reduce(c << (np.uint64(62) - np.uint64(2) * np.arange(32, dtype=np.uint64)), axis=1)
+        if n > 0 and len(words) < (int(offsets[-1]) + 31) // 32 + 1:
+            raise ValueError("words[] must hold ceil(n_bases/32) + 1 entries")
+        bp = None if bad_pos is None else np.ascontiguousarray(bad_pos, dtype=np.int32)
+        if bp is not None and len(bp) != n:
+            raise ValueError("bad_pos needs one entry a read")
+        out = np.zeros(max(n, 0), dtype=READ_COV_DTYPE)
+        self._chk(self._L.mc_classify_reads(self._h, _p(words, C.c_uint64), _p(offsets, C.c_uint64), max(n, 0),
+                                            _p(bp, C.c_int32) if bp is not None else None, int(found), float(z),
+                                            CLASSIFY_CORRECTION if correction else 0, out.ctypes.data_as(C.POINTER(ReadCov))))
+        return out["sum"].copy(), out["covered"].copy(), out["last"].copy(), out["found"].astype(bool)
+
+    def classify_reads_dev(self, d_words, d_offsets, n_reads, d_out, d_bad_pos=None, found=90, z=1.0, correction=False):
+        """mc_classify_reads_dev: d_out holds 12 bytes a read (mc_read_cov)"""
+        self._chk(self._L.mc_classify_reads_dev(self._h, _dptr(d_words), _dptr(d_offsets), int(n_reads), _dptr(d_bad_pos), int(found),
+                                                float(z), CLASSIFY_CORRECTION if correction else 0, _dptr(d_out)))
 
     # ---- BFS
     def bfs_batch(self, jobs, min_cov, max_kmers=-1, max_radius=-1):
