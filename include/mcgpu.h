@@ -383,6 +383,45 @@ int mc_classify_reads_dev(mc_ctx *ctx, const uint64_t *d_words, const uint64_t *
 int mc_classify_reads(mc_ctx *ctx, const uint64_t *words, const uint64_t *read_offsets, uint64_t n_reads,
                       const int32_t *bad_pos, int found_pct, double z, int flags, mc_read_cov *out);
 
+/* ---- triple-reads-classifier: found / half-found / not found with two k (src/tools/TripleReadsClassifier.java:164-270,
+ * src/algo/TripleFinder.java:32-67, src/algo/TripleFinder2.java:45-110).
+ * The reference keeps pass 1's class of a read in a map keyed by the read's bases (read.toString(): N printed as A, no qualities;
+ * one map a mate) and looks every read up by its bases in pass 2: a read's pass-1 class is that of the LAST read of its side with
+ * the same bases.  It runs pairs on a thread pool, so "last" is only defined at -p 1; here it is the greatest input index.
+ *
+ * mc_reads_last_copy: for every read r, last[r] = the greatest index j of a read with exactly the same bases (same length, same
+ * codes); j >= r.  Reads in the layout of mc_classify_reads (N is code 0: exactly the reference's key).  Needs no table (any
+ * context, before or after mc_finalize_counts).  A 64-bit fingerprint a read, a stable radix sort of (fingerprint, index), then
+ * every read is compared base for base with the last member of its run of equal fingerprints: the result never rests on a
+ * fingerprint alone.  flags & MC_LAST_COPY_WEAK_FP (tests only): the first round keeps 4 bits of the fingerprint, so distinct reads
+ * share one and the collision path runs.  Errors: MC_EINVAL for null pointers or n_reads >= 2^31 (one sort).
+ * mc_reads_last_copy takes host pointers, mc_reads_last_copy_dev device ones. */
+#define MC_LAST_COPY_WEAK_FP 1
+int mc_reads_last_copy_dev(mc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_read_offsets, uint64_t n_reads,
+                           int flags, uint32_t *d_last);
+int mc_reads_last_copy(mc_ctx *ctx, const uint64_t *words, const uint64_t *read_offsets, uint64_t n_reads,
+                       int flags, uint32_t *last);
+
+/* mc_triple_classes: the classes of n_pairs pairs at this context's k, one byte a read, from the two mates' mc_read_cov (what
+ * mc_classify_reads gave at this k, with or without the correction) and their lengths (offsets1 / offsets2: n_pairs + 1 each).
+ * found_i = cov_i.found, except found_2 = !found_1 when mate 2 is empty (TripleFinder.java:44-46);
+ * width = (covered + [last > 0] (k - 1)) / len, 0 when len < k (getWidth, :70-76: the read as given, without the correction);
+ * half = half_pct / 100.0.
+ *   Pass 1 (prev1 == prev2 == NULL): FOUND if found, else HALF_FOUND if width >= half, else NOT_FOUND (TripleFinder.java:48-61).
+ *   Pass 2 (prev_s: pass 1's classes of side s, last_s: mc_reads_last_copy of side s): c1 = prev_s[last_s[i]];
+ *     FOUND if found && c1 == FOUND, else HALF_FOUND if found || c1 == FOUND || (width >= half && c1 == HALF_FOUND), else NOT_FOUND
+ *     (TripleFinder2.java:58-76).
+ * Needs no table.  Errors: MC_EINVAL for null pointers, half_pct outside 0 .. 100, or only some of the pass-2 arrays. */
+#define MC_CLASS_NOT_FOUND 0
+#define MC_CLASS_HALF_FOUND 1
+#define MC_CLASS_FOUND 2
+int mc_triple_classes_dev(mc_ctx *ctx, const mc_read_cov *d_cov1, const mc_read_cov *d_cov2, const uint64_t *d_offsets1,
+                          const uint64_t *d_offsets2, uint64_t n_pairs, int half_pct, const uint8_t *d_prev1, const uint8_t *d_prev2,
+                          const uint32_t *d_last1, const uint32_t *d_last2, uint8_t *d_class1, uint8_t *d_class2);
+int mc_triple_classes(mc_ctx *ctx, const mc_read_cov *cov1, const mc_read_cov *cov2, const uint64_t *offsets1, const uint64_t *offsets2,
+                      uint64_t n_pairs, int half_pct, const uint8_t *prev1, const uint8_t *prev2, const uint32_t *last1,
+                      const uint32_t *last2, uint8_t *class1, uint8_t *class2);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

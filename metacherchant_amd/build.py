@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libmcgpu.so")
 CLI = os.path.join(LIBDIR, "metacherchant")
 
 # the library's units (csrc/context.h says what each holds), and the host reader the read-file entry point uses
-HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", os.path.join("host", "envfinder.cpp")]
+HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", os.path.join("host", "envfinder.cpp")]
 # every header under csrc/ makes every object stale (a stale library would travel to the GPU box unnoticed)
 HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "envfinder.h"), os.path.join("test", "bfs_old_race.h"),
                                                                       os.path.join(ROOT, "include", "mcgpu.h")]
@@ -107,8 +107,11 @@ def build_host(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     if os.path.exists(LIB) and (force or _stale(CLI, common + hdrs + [os.path.join(hdir, "main.cpp"), LIB])):
-        cmd = ["g++"] + flags + ["-o", CLI, os.path.join(hdir, "main.cpp")] + common + [
-            "-L", LIBDIR, "-lmcgpu", "-Wl,-rpath,$ORIGIN", "-lpthread", "-lz", "-ldl"]
+        # (the CLI keeps the triple-reads-classifier's reads on the device itself: HIP's host API, no device code)
+        rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
+        cmd = ["g++"] + flags + ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"), "-o", CLI, os.path.join(hdir, "main.cpp")] + common + [
+            "-L", LIBDIR, "-lmcgpu", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib"),
+            "-lpthread", "-lz", "-ldl"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

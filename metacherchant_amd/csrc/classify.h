@@ -1,6 +1,6 @@
 // The verdict of the reads-classifier on one read (src/algo/ReadsFinderInGraph.java:37-49,95-103), from the three numbers
-// the kernel reduces a read to.  One function for the kernel (csrc/classify.hip) and for host code: it compiles as HIP and as
-// plain C++.
+// the kernel reduces a read to, and the triple-reads-classifier's width and class rules.  One copy for the kernels
+// (csrc/classify.hip) and for host code: it compiles as HIP and as plain C++.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -25,6 +25,30 @@ MC_CLASSIFY_HD inline bool classify_verdict(int32_t sum, int32_t covered, int32_
     const double theory_width = 1.0 - exp(-cov_mean);
     const double std_dev = z * sqrt(exp(-cov_mean) * (1 - exp(-cov_mean)) / len);
     return !(width < thr) && (width == 1 || (width != 0 && -std_dev <= width - theory_width && width - theory_width <= std_dev));
+}
+
+// the classes of the triple-reads-classifier (include/mcgpu.h MC_CLASS_*: TripleReadsClassifier.FindResult)
+enum : uint8_t { CLASS_NOT_FOUND = 0, CLASS_HALF_FOUND = 1, CLASS_FOUND = 2 };
+
+// getWidth (src/algo/TripleFinder.java:70-76, TripleFinder2.java:113-119): the breadth of the read as given, 0 when len < k
+MC_CLASSIFY_HD inline double triple_width(int32_t covered, int32_t last, int32_t len, int k)
+{
+    if (len < k) return 0;
+    return (double)(int32_t)((uint32_t)covered + (last > 0 ? (uint32_t)(k - 1) : 0u)) / len;
+}
+
+// pass 1 (TripleFinder.java:48-61): found, else half found when the width reaches half (half_threshold / 100)
+MC_CLASSIFY_HD inline uint8_t triple_class_pass1(bool found, double width, double half)
+{
+    return found ? CLASS_FOUND : width >= half ? CLASS_HALF_FOUND : CLASS_NOT_FOUND;
+}
+
+// pass 2 (TripleFinder2.java:58-76): f the verdict at k2, c1 the pass-1 class of the read's bases
+MC_CLASSIFY_HD inline uint8_t triple_class_pass2(bool f, uint8_t c1, double width, double half)
+{
+    if (f && c1 == CLASS_FOUND) return CLASS_FOUND;
+    if (f || c1 == CLASS_FOUND || (width >= half && c1 == CLASS_HALF_FOUND)) return CLASS_HALF_FOUND;
+    return CLASS_NOT_FOUND;
 }
 
 }  // namespace mc

@@ -5,6 +5,8 @@
 // (kmer_device.h key_of) and looks it up (table_get), then the wave sums the coverages with cross-lane shuffles.  A probe
 // is one 16-byte slot read at a random place in the table: the kernel is bound by how many of them HBM serves, and a wave
 // has up to 64 of them in flight.  DESIGN.md "Reads-classifier" has the roofline.
+//
+// k_triple_classes, the triple-reads-classifier's classes (mc_triple_classes*): one thread a pair, the rules of classify.h.
 #include "context.h"
 #include "classify.h"
 
@@ -96,7 +98,102 @@ __global__ void __launch_bounds__(CL_THREADS) k_classify(const uint64_t *__restr
     }
 }
 
+constexpr int TC_THREADS = 256;
+
+// one thread a pair: the two mates' classes at this pass (prev1 == NULL: pass 1; else pass 2 with the pass-1 classes of the mates' last
+// copies).  (A last index out of range -- the caller's mistake -- reads as NOT_FOUND rather than outside the array.)
+__global__ void __launch_bounds__(TC_THREADS) k_triple_classes(const mc_read_cov *__restrict__ cov1, const mc_read_cov *__restrict__ cov2,
+                                                               const uint64_t *__restrict__ off1, const uint64_t *__restrict__ off2, uint64_t n,
+                                                               int k, double half, const uint8_t *__restrict__ prev1,
+                                                               const uint8_t *__restrict__ prev2, const uint32_t *__restrict__ last1,
+                                                               const uint32_t *__restrict__ last2, uint8_t *__restrict__ cls1,
+                                                               uint8_t *__restrict__ cls2)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int32_t len1 = (int32_t)(off1[i + 1] - off1[i]), len2 = (int32_t)(off2[i + 1] - off2[i]);
+        const mc_read_cov a = cov1[i], b = cov2[i];
+        const bool f1 = a.found != 0;
+        const bool f2 = len2 == 0 ? !f1 : b.found != 0;  // TripleFinder.java:44-46, TripleFinder2.java:54-56
+        const double w1 = triple_width(a.covered, a.last, len1, k), w2 = triple_width(b.covered, b.last, len2, k);
+        if (!prev1) {
+            cls1[i] = triple_class_pass1(f1, w1, half);
+            cls2[i] = triple_class_pass1(f2, w2, half);
+        } else {
+            const uint32_t j1 = last1[i], j2 = last2[i];
+            cls1[i] = triple_class_pass2(f1, j1 < n ? prev1[j1] : (uint8_t)CLASS_NOT_FOUND, w1, half);
+            cls2[i] = triple_class_pass2(f2, j2 < n ? prev2[j2] : (uint8_t)CLASS_NOT_FOUND, w2, half);
+        }
+    }
+}
+
 }  // namespace
+
+int mc_triple_classes_dev(mc_ctx *c, const mc_read_cov *d_cov1, const mc_read_cov *d_cov2, const uint64_t *d_offsets1, const uint64_t *d_offsets2,
+                          uint64_t n_pairs, int half_pct, const uint8_t *d_prev1, const uint8_t *d_prev2, const uint32_t *d_last1,
+                          const uint32_t *d_last2, uint8_t *d_class1, uint8_t *d_class2)
+{
+    if (!c) return MC_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (half_pct < 0 || half_pct > 100) return fail(c, MC_EINVAL, "mc_triple_classes: half_pct %d is outside 0 .. 100", half_pct);
+    const int n_prev = !!d_prev1 + !!d_prev2 + !!d_last1 + !!d_last2;
+    if (n_prev != 0 && n_prev != 4) return fail(c, MC_EINVAL, "mc_triple_classes: pass 2 needs both sides' classes and last copies");
+    if (n_pairs && (!d_cov1 || !d_cov2 || !d_offsets1 || !d_offsets2 || !d_class1 || !d_class2))
+        return fail(c, MC_EINVAL, "mc_triple_classes: null pointer");
+    if (n_pairs == 0) return MC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const double half = (double)half_pct / 100;  // TripleReadsClassifier.java:203,229
+    hipLaunchKernelGGL(k_triple_classes, dim3(grid_for(n_pairs, TC_THREADS, 1 << 16)), dim3(TC_THREADS), 0, c->stream, d_cov1, d_cov2, d_offsets1,
+                       d_offsets2, n_pairs, c->cfg.k, half, d_prev1, d_prev2, d_last1, d_last2, d_class1, d_class2);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MC_OK;
+}
+
+int mc_triple_classes(mc_ctx *c, const mc_read_cov *cov1, const mc_read_cov *cov2, const uint64_t *offsets1, const uint64_t *offsets2, uint64_t n_pairs,
+                      int half_pct, const uint8_t *prev1, const uint8_t *prev2, const uint32_t *last1, const uint32_t *last2, uint8_t *class1,
+                      uint8_t *class2)
+{
+    if (!c) return MC_EINVAL;
+    const bool pass2 = prev1 || prev2 || last1 || last2;
+    if (n_pairs && (!cov1 || !cov2 || !offsets1 || !offsets2 || !class1 || !class2 || (pass2 && !(prev1 && prev2 && last1 && last2))))
+        return fail(c, MC_EINVAL, "mc_triple_classes: null pointer");
+    if (n_pairs == 0) return mc_triple_classes_dev(c, nullptr, nullptr, nullptr, nullptr, 0, half_pct, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    DevBuf<mc_read_cov> dc1, dc2;
+    DevBuf<uint64_t> do1, do2;
+    DevBuf<uint8_t> dp1, dp2, dk1, dk2;
+    DevBuf<uint32_t> dl1, dl2;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        HIPCHK(c, dc1.alloc(n_pairs));
+        HIPCHK(c, dc2.alloc(n_pairs));
+        HIPCHK(c, do1.alloc(n_pairs + 1));
+        HIPCHK(c, do2.alloc(n_pairs + 1));
+        HIPCHK(c, dk1.alloc(n_pairs));
+        HIPCHK(c, dk2.alloc(n_pairs));
+        HIPCHK(c, hipMemcpy(dc1.p, cov1, n_pairs * sizeof(mc_read_cov), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(dc2.p, cov2, n_pairs * sizeof(mc_read_cov), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(do1.p, offsets1, (n_pairs + 1) * 8, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(do2.p, offsets2, (n_pairs + 1) * 8, hipMemcpyHostToDevice));
+        if (pass2) {
+            HIPCHK(c, dp1.alloc(n_pairs));
+            HIPCHK(c, dp2.alloc(n_pairs));
+            HIPCHK(c, dl1.alloc(n_pairs));
+            HIPCHK(c, dl2.alloc(n_pairs));
+            HIPCHK(c, hipMemcpy(dp1.p, prev1, n_pairs, hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(dp2.p, prev2, n_pairs, hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(dl1.p, last1, n_pairs * 4, hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(dl2.p, last2, n_pairs * 4, hipMemcpyHostToDevice));
+        }
+    }
+    int rc = mc_triple_classes_dev(c, dc1.p, dc2.p, do1.p, do2.p, n_pairs, half_pct, dp1.p, dp2.p, dl1.p, dl2.p, dk1.p, dk2.p);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipMemcpy(class1, dk1.p, n_pairs, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(class2, dk2.p, n_pairs, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
 
 int mc_classify_reads_dev(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_read_offsets, uint64_t n_reads, const int32_t *d_bad_pos,
                           int found_pct, double z, int flags, mc_read_cov *d_out)

@@ -17,6 +17,8 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "envfinder.h"
 #include "mcgpu.h"
 
@@ -71,6 +73,10 @@ struct Options {
     std::vector<std::string> input_files, read_files;
     bool correction = false, interval95 = false;
     long long found_threshold = 90;
+    // --tool triple-reads-classifier (src/tools/TripleReadsClassifier.java:40-105)
+    int k2 = -1;
+    std::vector<std::string> input_kmers_1, input_kmers_2;
+    long long half_threshold = 40;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -89,6 +95,15 @@ const OptSpec SPECS[] = {
 const OptSpec CLASSIFIER_SPECS[] = {
     {"k", "k", 0}, {"input-files", "i", 2}, {"read-files", "r", 2}, {"output-dir", "o", 0}, {"correction", "corr", 1},
     {"hash", nullptr, 0}, {"interval95", nullptr, 1}, {"found-threshold", "found", 0},
+    {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
+};
+
+// --tool triple-reads-classifier: its parameters (TripleReadsClassifier.java:40-105) and the launch options
+const OptSpec TRIPLE_SPECS[] = {
+    {"k", "k", 0}, {"k2", "k2", 0}, {"input-files", "i", 2}, {"input-kmers-1", "ik1", 2}, {"input-kmers-2", "ik2", 2}, {"read-files", "r", 2},
+    {"output-dir", "o", 0}, {"hash", nullptr, 0}, {"correction", "corr", 1}, {"interval95", nullptr, 1}, {"found-threshold", "found", 0},
+    {"half-threshold", "half", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
 };
@@ -135,8 +150,10 @@ long long parse_int(const std::string &name, const std::string &v)
 
 Options parse_args(int argc, char **argv)
 {
-    const SpecTable specs = tool_of(argc, argv) == "reads-classifier" ? SpecTable{std::begin(CLASSIFIER_SPECS), std::end(CLASSIFIER_SPECS)}
-                                                                      : SpecTable{std::begin(SPECS), std::end(SPECS)};
+    const std::string tool = tool_of(argc, argv);
+    const SpecTable specs = tool == "reads-classifier"          ? SpecTable{std::begin(CLASSIFIER_SPECS), std::end(CLASSIFIER_SPECS)}
+                            : tool == "triple-reads-classifier" ? SpecTable{std::begin(TRIPLE_SPECS), std::end(TRIPLE_SPECS)}
+                                                                : SpecTable{std::begin(SPECS), std::end(SPECS)};
     std::map<std::string, std::vector<std::string>> got;
     for (int i = 1; i < argc; i++) {
         std::string tok = argv[i], inline_val;
@@ -183,6 +200,10 @@ Options parse_args(int argc, char **argv)
     if (auto v = val("correction")) o.correction = java_bool(*v);
     if (auto v = val("interval95")) o.interval95 = java_bool(*v);
     if (auto v = val("found-threshold")) o.found_threshold = parse_int("found-threshold", *v);
+    multi("input-kmers-1", o.input_kmers_1);
+    multi("input-kmers-2", o.input_kmers_2);
+    if (auto v = val("k2")) o.k2 = (int)parse_int("k2", *v);
+    if (auto v = val("half-threshold")) o.half_threshold = parse_int("half-threshold", *v);
     if (auto v = val("seq")) o.seq = *v;
     if (auto v = val("hicseq")) o.hicseq = *v;
     if (auto v = val("output")) o.output = *v;
@@ -256,6 +277,19 @@ void usage()
     puts("      --hash <arg>               hash function to use for k > 31: poly or fnv1a (default poly)");
     puts("      --interval95 [<arg>]       set the interval width to probability 0.95 (default false)");
     puts("  -found, --found-threshold <arg>  minimum coverage breadth for class `found`, 0 - 100 % (default 90)");
+    puts("Input parameters of --tool triple-reads-classifier (splits the pairs of -r into found / half found / not found with two k):");
+    puts("  -k, --k <arg>                  k-mer size of the first graph (MANDATORY)");
+    puts("  -k2, --k2 <arg>                k-mer size of the second graph, k2 > k (MANDATORY)");
+    puts("  -i, --input-files <args>       reads for both de Bruijn graphs (unless -ik1 / -ik2 give them)");
+    puts("  -ik1, --input-kmers-1 <args>   the first graph as <name>.kmers.bin from kmer-counter at k");
+    puts("  -ik2, --input-kmers-2 <args>   the second graph as <name>.kmers.bin from kmer-counter at k2");
+    puts("  -r, --read-files <args>        two FASTQ / FASTA files of paired reads to classify (MANDATORY)");
+    puts("  -o, --output-dir <arg>         directory of the nine {found,half_found,not_found}_{1,2,s}.fastq (default <work-dir>/reads_classifier)");
+    puts("  -corr, --correction [<arg>]    try the four bases at a read's one low-quality position (default false)");
+    puts("      --hash <arg>               hash function to use for k > 31: poly or fnv1a (default poly)");
+    puts("      --interval95 [<arg>]       set the interval width to probability 0.95 (default false)");
+    puts("  -found, --found-threshold <arg>  minimum coverage breadth for class `found`, 0 - 100 % (default 90)");
+    puts("  -half, --half-threshold <arg>  minimum coverage breadth for class `half-found`, 0 - 100 % (default 40)");
     puts("Launch options: -w/--work-dir <dir> (default workDir), -c/--continue, --force, -v/--verbose, -h/--help,");
     puts("                -t/--tool <name>, -p/--available-processors <n> and -m/--memory <arg> (accepted, unused),");
     puts("                --device <n> (GPU ordinal), --devices <a,b,...|a-b> (several GPUs as one table: reads dealt to them,");
@@ -479,6 +513,19 @@ struct SideList {
     }
 };
 
+// findReadWithCorrection's one low-quality position of each of the first n reads: -1 for none, -2 for several (mc_classify_reads)
+std::vector<int32_t> bad_positions(const DnaQBatch &b, size_t n)
+{
+    std::vector<int32_t> bad(n, -1);
+    for (size_t r = 0; r < n; r++)
+        for (uint64_t i = b.offsets[r]; i < b.offsets[r + 1]; i++)
+            if (b.phred[i] < 10) {
+                if (bad[r] != -1) { bad[r] = -2; break; }
+                bad[r] = (int32_t)(i - b.offsets[r]);
+            }
+    return bad;
+}
+
 // one batch of whole reads through mc_classify_reads: N is base 0 already (DnaQReader), bad_pos as findReadWithCorrection counts
 std::vector<mc_read_cov> classify_batch(mc_ctx *ctx, const DnaQBatch &b, size_t n, const Options &o)
 {
@@ -487,19 +534,50 @@ std::vector<mc_read_cov> classify_batch(mc_ctx *ctx, const DnaQBatch &b, size_t 
     const uint64_t n_bases = b.offsets[n];
     std::vector<uint64_t> words((n_bases + 31) / 32 + 1, 0);
     for (uint64_t i = 0; i < n_bases; i++) words[i >> 5] |= (uint64_t)(b.codes[i] & 3) << (62 - 2 * (i & 31));
-    std::vector<int32_t> bad;
-    if (o.correction) {
-        bad.assign(n, -1);
-        for (size_t r = 0; r < n; r++)
-            for (uint64_t i = b.offsets[r]; i < b.offsets[r + 1]; i++)
-                if (b.phred[i] < 10) {
-                    if (bad[r] != -1) { bad[r] = -2; break; }
-                    bad[r] = (int32_t)(i - b.offsets[r]);
-                }
-    }
+    const std::vector<int32_t> bad = o.correction ? bad_positions(b, n) : std::vector<int32_t>();
     MC_CHECK(ctx, mc_classify_reads(ctx, words.data(), b.offsets.data(), n, o.correction ? bad.data() : nullptr, (int)o.found_threshold,
                                     o.interval95 ? 1.96 : 1.0, o.correction ? MC_CLASSIFY_CORRECTION : 0, out.data()));
     return out;
+}
+
+// file.getName().toLowerCase().endsWith("kmers.bin"): loadGraph reads such a file as kmer-counter's output
+bool names_kmers_bin(const std::string &path)
+{
+    std::string first = path;
+    const size_t slash = first.find_last_of('/');
+    if (slash != std::string::npos) first = first.substr(slash + 1);
+    for (char &c : first) c = (char)tolower((unsigned char)c);
+    return first.size() >= 9 && first.compare(first.size() - 9, 9, "kmers.bin") == 0;
+}
+
+// loadGraph (ReadsClassifier.java:98-132, TripleReadsClassifier.java:127-160): the hash-function line for k > 31, then the table at k
+// from kmer_files when the first one's name ends in kmers.bin (IOUtils.loadKmers), else counted from the reads of --input-files
+void load_graph(const Options &o, int k, const std::vector<std::string> &kmer_files, Engine &E)
+{
+    int mode = MC_KEY_PACKED;
+    if (k > 31) {  // determineHashFunction
+        std::string h = o.hash;
+        for (char &c : h) c = (char)tolower((unsigned char)c);
+        if (h == "fnv1a") { info("Using FNV1a hash function"); mode = MC_KEY_FNV1A; }
+        else { info("Using default polynomial hash function"); mode = MC_KEY_POLY; }
+    }
+    const bool kmers_bin = !kmer_files.empty() && names_kmers_bin(kmer_files[0]);
+    mc_config cfg{};
+    cfg.k = k;
+    cfg.key_mode = mode;
+    cfg.device = o.device;
+    cfg.capacity_hint = o.capacity_hint;
+    E.open(cfg, {});
+    mc_ctx *ctx = E.c;
+    uint64_t n_distinct = 0;
+    if (kmers_bin) {  // IOUtils.loadKmers(files, 0, ...)
+        for (const std::string &path : kmer_files) MC_CHECK(ctx, mc_load_kmers(ctx, path.c_str(), 0, nullptr, nullptr));
+        E.finalize(&n_distinct);
+        info("Hashtable size: " + std::to_string(n_distinct) + " kmers");
+    } else {
+        if (k > 31) info("Reading hashes of k-mers instead");
+        load_reads(o.input_files, E);
+    }
 }
 
 int run_reads_classifier(const Options &o)
@@ -516,36 +594,9 @@ int run_reads_classifier(const Options &o)
     write_file(out_dir + "/.keep", "");  // outputDir.mkdirs()
     remove((out_dir + "/.keep").c_str());
 
-    // loadGraph (ReadsClassifier.java:98-118)
-    int mode = MC_KEY_PACKED;
-    if (o.k > 31) {  // determineHashFunction (:121-132)
-        std::string h = o.hash;
-        for (char &c : h) c = (char)tolower((unsigned char)c);
-        if (h == "fnv1a") { info("Using FNV1a hash function"); mode = MC_KEY_FNV1A; }
-        else { info("Using default polynomial hash function"); mode = MC_KEY_POLY; }
-    }
-    std::string first = o.input_files[0];
-    const size_t slash = first.find_last_of('/');
-    if (slash != std::string::npos) first = first.substr(slash + 1);
-    for (char &c : first) c = (char)tolower((unsigned char)c);
-    const bool kmers_bin = first.size() >= 9 && first.compare(first.size() - 9, 9, "kmers.bin") == 0;
-    mc_config cfg{};
-    cfg.k = o.k;
-    cfg.key_mode = mode;
-    cfg.device = o.device;
-    cfg.capacity_hint = o.capacity_hint;
     Engine E;
-    E.open(cfg, {});
+    load_graph(o, o.k, o.input_files, E);
     mc_ctx *ctx = E.c;
-    uint64_t n_distinct = 0;
-    if (kmers_bin) {  // IOUtils.loadKmers(files, 0, ...)
-        for (const std::string &path : o.input_files) MC_CHECK(ctx, mc_load_kmers(ctx, path.c_str(), 0, nullptr, nullptr));
-        E.finalize(&n_distinct);
-        info("Hashtable size: " + std::to_string(n_distinct) + " kmers");
-    } else {
-        if (o.k > 31) info("Reading hashes of k-mers instead");
-        n_distinct = load_reads(o.input_files, E);
-    }
 
     info("Loading reads...");
     const bool paired = o.read_files.size() == 2;
@@ -615,14 +666,233 @@ int run_reads_classifier(const Options &o)
     return 0;
 }
 
+// --tool triple-reads-classifier (src/tools/TripleReadsClassifier.java:164-270, src/algo/TripleFinder.java, src/algo/TripleFinder2.java):
+// the pairs of -r classed found / half found / not found by their k-mers in the graph at k, then at k2, written to nine FASTQ files.
+// Both sides' reads stay on the device for both passes.  A read's pass-1 class is that of the last read of its side with the same bases
+// (the reference's maps keyed by bases: mc_reads_last_copy).  The reference runs pairs on a thread pool, so its lists' order and its
+// maps' last writer are only defined at -p 1; here they are that: input order in every file, "last" = the greatest input index.
+
+void hip_check(hipError_t e, const char *what)
+{
+    if (e != hipSuccess) throw Error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// device memory of the tool's own, grown by doubling
+struct DevArray {
+    char *p = nullptr;
+    size_t cap = 0, size = 0;
+    DevArray() = default;
+    DevArray(const DevArray &) = delete;
+    DevArray &operator=(const DevArray &) = delete;
+    ~DevArray() { if (p) (void)hipFree(p); }
+    void reserve(size_t bytes)
+    {
+        if (bytes <= cap) return;
+        const size_t nc = std::max(bytes, 2 * cap);
+        char *q = nullptr;
+        hip_check(hipMalloc(reinterpret_cast<void **>(&q), nc), "hipMalloc");
+        if (size) hip_check(hipMemcpy(q, p, size, hipMemcpyDeviceToDevice), "hipMemcpy");
+        if (p) (void)hipFree(p);
+        p = q;
+        cap = nc;
+    }
+    void put(size_t at, const void *h, size_t bytes)  // host bytes to [at, at + bytes)
+    {
+        reserve(at + bytes);
+        if (bytes) hip_check(hipMemcpy(p + at, h, bytes, hipMemcpyHostToDevice), "hipMemcpy");
+        size = std::max(size, at + bytes);
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = size = 0;
+    }
+    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// one side of the pairs on the device, in mc_classify_reads' layout: words (the pad word included), offsets, bad positions
+struct SideStore {
+    DevArray words, offsets, bad;
+    uint64_t n_reads = 0, n_bases = 0, carry = 0;  // carry: the partly filled last word, written again with the next batch
+    void add(const DnaQBatch &b, size_t n, bool correction)
+    {
+        if (n_reads == 0) {
+            const uint64_t z = 0;
+            offsets.put(0, &z, 8);
+        }
+        const uint64_t nb = b.offsets[n], end = n_bases + nb, w0 = n_bases / 32;
+        std::vector<uint64_t> w((end + 31) / 32 - w0 + 1, 0);
+        w[0] = carry;
+        for (uint64_t i = 0; i < nb; i++) {
+            const uint64_t g = n_bases + i;
+            w[g / 32 - w0] |= (uint64_t)(b.codes[i] & 3) << (62 - 2 * (g & 31));
+        }
+        words.put(w0 * 8, w.data(), w.size() * 8);
+        carry = end % 32 ? w[end / 32 - w0] : 0;
+        std::vector<uint64_t> off(n);
+        for (size_t i = 0; i < n; i++) off[i] = n_bases + b.offsets[i + 1];
+        offsets.put((n_reads + 1) * 8, off.data(), n * 8);
+        if (correction) {
+            const std::vector<int32_t> bp = bad_positions(b, n);
+            bad.put(n_reads * 4, bp.data(), n * 4);
+        }
+        n_reads += n;
+        n_bases = end;
+    }
+};
+
+// the pairs of two DnaQ readers, batch by batch: PairSource (itmo!/io/sources/PairSource.java:35-45) ends them with the shorter file
+template <typename F>
+void for_each_pair_batch(const Options &o, F &&f)
+{
+    DnaQReader r1(o.read_files[0]), r2(o.read_files[1]);
+    constexpr size_t BATCH = 1u << 20;
+    DnaQBatch b1, b2;
+    for (;;) {
+        b1.clear();
+        b2.clear();
+        size_t n = r1.read(b1, BATCH);
+        n = r2.read(b2, n);
+        if (n == 0) break;
+        f(b1, b2, n);
+        if (n < BATCH) break;  // (one of the files is done)
+    }
+}
+
+int run_triple_reads_classifier(const Options &o)
+{
+    // (every parameter is checked before a device is opened)
+    if (o.k < 0) throw Error("Parameter 'k' is mandatory");
+    if (o.k2 < 0) throw Error("Parameter 'k2' is mandatory");
+    if (o.read_files.empty()) throw Error("Parameter 'read-files' is mandatory");
+    if (o.k >= o.k2) throw Error("k2 should be greater than k, given: " + std::to_string(o.k) + " " + std::to_string(o.k2));
+    if (o.read_files.size() < 2)  // (the reference takes sources.get(1); files after the second are ignored, as there)
+        throw Error("--read-files needs two files of paired reads, given: " + std::to_string(o.read_files.size()));
+    const std::vector<std::string> *kmers[2] = {&o.input_kmers_1, &o.input_kmers_2};
+    for (int pass = 0; pass < 2; pass++)
+        if (o.input_files.empty() && (kmers[pass]->empty() || !names_kmers_bin((*kmers[pass])[0])))
+            throw Error("No graph for k = " + std::to_string(pass ? o.k2 : o.k) + ": give --input-files, or --input-kmers-" +
+                        std::to_string(pass + 1) + " with a <name>.kmers.bin from kmer-counter");
+    for (int kk : {o.k, o.k2})
+        if (kk < 1 || kk > 63)
+            throw Error("k = " + std::to_string(kk) + " is not supported: this build handles k <= 31 (packed keys) and 32 <= k <= 63 (hash keys)");
+    if (o.found_threshold < 0 || o.found_threshold > 100) throw Error("--found-threshold must be within 0 .. 100 (a percentage of the read)");
+    if (o.half_threshold < 0 || o.half_threshold > 100) throw Error("--half-threshold must be within 0 .. 100 (a percentage of the read)");
+    if (!open_work_dir(o, "k=" + std::to_string(o.k) + "\nk2=" + std::to_string(o.k2) + "\n")) return 0;
+    const std::string out_dir = o.output_dir.empty() ? o.work_dir + "/reads_classifier" : o.output_dir;
+    write_file(out_dir + "/.keep", "");  // outputDir.mkdirs()
+    remove((out_dir + "/.keep").c_str());
+
+    info("Loading reads...");
+    hip_check(hipSetDevice(o.device), "hipSetDevice");
+    SideStore side[2];
+    for_each_pair_batch(o, [&](const DnaQBatch &b1, const DnaQBatch &b2, size_t n) {
+        side[0].add(b1, n, o.correction);
+        side[1].add(b2, n, o.correction);
+    });
+    const uint64_t n = side[0].n_reads;
+
+    // the two passes: each side's coverage at k (mc_classify_reads), then its classes (mc_triple_classes); pass 2 reads pass 1's
+    // class of every read's last copy
+    DevArray cov[2], cls1[2], cls2[2], last[2];
+    for (int s = 0; s < 2; s++) {
+        cov[s].reserve(n * sizeof(mc_read_cov));
+        cls1[s].reserve(n);
+        cls2[s].reserve(n);
+        last[s].reserve(n * 4);
+    }
+    const double z = o.interval95 ? 1.96 : 1.0;
+    for (int pass = 0; pass < 2; pass++) {
+        const int k = pass ? o.k2 : o.k;
+        info("Building graph with k = " + std::to_string(k) + " ...");
+        Engine E;  // (one graph at a time: cleanImpl frees the first before the second is built)
+        load_graph(o, k, *kmers[pass], E);
+        mc_ctx *ctx = E.c;
+        info(o.correction ? "Searching for corrected reads in graph..." : "Searching for reads in graph...");
+        for (int s = 0; s < 2; s++)
+            MC_CHECK(ctx, mc_classify_reads_dev(ctx, side[s].words.as<uint64_t>(), side[s].offsets.as<uint64_t>(), n,
+                                                o.correction ? side[s].bad.as<int32_t>() : nullptr, (int)o.found_threshold, z,
+                                                o.correction ? MC_CLASSIFY_CORRECTION : 0, cov[s].as<mc_read_cov>()));
+        DevArray *out = pass ? cls2 : cls1;
+        MC_CHECK(ctx, mc_triple_classes_dev(ctx, cov[0].as<mc_read_cov>(), cov[1].as<mc_read_cov>(), side[0].offsets.as<uint64_t>(),
+                                            side[1].offsets.as<uint64_t>(), n, (int)o.half_threshold, pass ? cls1[0].as<uint8_t>() : nullptr,
+                                            pass ? cls1[1].as<uint8_t>() : nullptr, pass ? last[0].as<uint32_t>() : nullptr,
+                                            pass ? last[1].as<uint32_t>() : nullptr, out[0].as<uint8_t>(), out[1].as<uint8_t>()));
+        if (pass == 0)
+            for (int s = 0; s < 2; s++)
+                MC_CHECK(ctx, mc_reads_last_copy_dev(ctx, side[s].words.as<uint64_t>(), side[s].offsets.as<uint64_t>(), n, 0, last[s].as<uint32_t>()));
+    }
+    std::vector<uint8_t> c1(n), c2(n);
+    if (n) {
+        hip_check(hipMemcpy(c1.data(), cls2[0].p, n, hipMemcpyDeviceToHost), "hipMemcpy");
+        hip_check(hipMemcpy(c2.data(), cls2[1].p, n, hipMemcpyDeviceToHost), "hipMemcpy");
+    }
+    for (int s = 0; s < 2; s++)  // (the reads are read again from the files below)
+        for (DevArray *a : {&side[s].words, &side[s].offsets, &side[s].bad, &cov[s], &cls1[s], &cls2[s], &last[s]}) a->release();
+
+    // FoundStats (TripleReadsClassifier.java:225-242,276-333): Java ints, String.format("%.2f")
+    long long both[3] = {0, 0, 0}, single[3] = {0, 0, 0};  // by class: both mates in it, one mate of a mixed pair in it
+    for (uint64_t i = 0; i < n; i++) {
+        if (c1[i] == c2[i]) both[c1[i]]++;
+        else { single[c1[i]]++; single[c2[i]]++; }
+    }
+    const long long bf = both[MC_CLASS_FOUND], bh = both[MC_CLASS_HALF_FOUND], bn = both[MC_CLASS_NOT_FOUND];
+    const long long total = 2 * (bn + bf + bh) + single[0] + single[1] + single[2], paired = 2 * (bf + bn + bh);
+    const long long found = 2 * bf + single[MC_CLASS_FOUND], not_found = 2 * bn + single[MC_CLASS_NOT_FOUND],
+                    half_found = 2 * bh + single[MC_CLASS_HALF_FOUND];
+    info("|\tTotal: " + std::to_string(total) + " reads");
+    info("|\tPaired: " + std::to_string(paired) + " reads");
+    info("|\tTotal quality: " + java_format_2f(100 * (double)paired / (double)total) + " %");
+    info("|\tFound: " + std::to_string(found) + " reads");
+    info("|\tPercent of found reads: " + java_format_2f(100 * (double)found / (double)total) + " %");
+    info("|\tQuality of found bin: " + java_format_2f((double)bf * 2 / (double)found * 100) + " %");
+    info("|\tNot found: " + std::to_string(not_found) + " reads");
+    info("|\tPercent of not found reads: " + java_format_2f(100 * (double)not_found / (double)total) + " %");
+    info("|\tQuality of not found bin: " + java_format_2f((double)bn * 2 / (double)not_found * 100) + " %");
+    info("|\tHalf found: " + std::to_string(half_found) + " reads");
+    info("|\tPercent of half found reads: " + java_format_2f(100 * (double)half_found / (double)total) + " %");
+    info("|\tQuality of half found bin: " + java_format_2f((double)bh * 2 / (double)half_found * 100) + " %");
+
+    // the nine files, streamed from a second read of -r in input order: found_{1,2} take every read (an empty one fails the writer,
+    // "Empty DnaQ!"), the others only reads of length > 0
+    info("Writing classified reads...");
+    FastqOut found1(out_dir + "/found_1.fastq"), found2(out_dir + "/found_2.fastq"), half1(out_dir + "/half_found_1.fastq"),
+        half2(out_dir + "/half_found_2.fastq"), nf1(out_dir + "/not_found_1.fastq"), nf2(out_dir + "/not_found_2.fastq"),
+        found_s(out_dir + "/found_s.fastq"), half_s(out_dir + "/half_found_s.fastq"), nf_s(out_dir + "/not_found_s.fastq");
+    FastqOut *pair_out[3][2] = {{&nf1, &nf2}, {&half1, &half2}, {&found1, &found2}}, *single_out[3] = {&nf_s, &half_s, &found_s};
+    uint64_t at = 0;
+    for_each_pair_batch(o, [&](const DnaQBatch &b1, const DnaQBatch &b2, size_t m) {
+        if (at + m > n) throw Error("The read files changed while they were being classified");
+        for (size_t i = 0; i < m; i++, at++) {
+            const DnaQBatch *b[2] = {&b1, &b2};
+            const uint8_t cls[2] = {c1[at], c2[at]};
+            for (int s = 0; s < 2; s++) {
+                const uint64_t o0 = b[s]->offsets[i], len = b[s]->offsets[i + 1] - o0;
+                const uint8_t *codes = b[s]->codes.data() + o0, *phred = b[s]->phred.data() + o0;
+                if (cls[0] == cls[1]) {
+                    if (len || cls[0] == MC_CLASS_FOUND) pair_out[cls[0]][s]->put(codes, phred, len);
+                } else if (len) {
+                    single_out[cls[s]]->put(codes, phred, len);
+                }
+            }
+        }
+    });
+    for (FastqOut *f : {&found1, &found2, &half1, &half2, &nf1, &nf2, &found_s, &half_s, &nf_s}) f->close();
+    info("Reads have been written. Finishing...");
+    write_file(o.work_dir + "/SUCCESS", "");
+    return 0;
+}
+
 int run(const Options &o)
 {
     if (o.tool == "kmer-counter") return run_kmer_counter(o);
     if (o.tool == "environment-finder-multi") return run_multi(o);
     if (o.tool == "reads-classifier") return run_reads_classifier(o);
+    if (o.tool == "triple-reads-classifier") return run_triple_reads_classifier(o);
     if (o.tool != "environment-finder")
-        throw Error("Tool '" + o.tool + "' is not part of this build: only environment-finder, kmer-counter, environment-finder-multi and "
-                    "reads-classifier are");
+        throw Error("Tool '" + o.tool + "' is not part of this build: only environment-finder, kmer-counter, environment-finder-multi, "
+                    "reads-classifier and triple-reads-classifier are");
     if (o.k < 0) throw Error("Parameter 'k' is mandatory");
     if (o.seq.empty()) throw Error("Parameter 'seq' is mandatory");
     if (o.output.empty()) throw Error("Parameter 'output' is mandatory");

@@ -67,6 +67,8 @@ class ReadCov(C.Structure):
 
 READ_COV_DTYPE = np.dtype([("sum", np.int32), ("covered", np.int32), ("last", np.int16), ("found", np.uint8), ("pad", np.uint8)])
 CLASSIFY_CORRECTION = 1  # mc_classify_reads flags: findReadWithCorrection
+LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fingerprint, so distinct reads share one
+CLASS_NOT_FOUND, CLASS_HALF_FOUND, CLASS_FOUND = 0, 1, 2  # mc_triple_classes
 
 
 # every symbol include/mcgpu.h declares; tests check that the library exports all of them
@@ -79,6 +81,7 @@ EXPORTS = [
     "mc_superkmer_fine_buckets", "mc_extract_superkmers_binned_dev", "mc_add_superkmers_binned_dev",
     "mc_read_store_seek", "mc_read_store_tell", "mc_read_store_import_dev", "mc_get_stats", "mc_reset_stats", "mc_trim", "mc_synth_reads_dev", "mc_synth_genome",
     "mc_shard_export", "mc_shard_attach", "mc_shard_detach", "mc_classify_reads", "mc_classify_reads_dev",
+    "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev",
 ]
 
 _LIB = None
@@ -159,6 +162,12 @@ def load():
     if hasattr(L, "mc_classify_reads"):  # (a tuning build of an older revision, MC_LIB)
         L.mc_classify_reads.argtypes = [vp, u64p, u64p, u64, C.POINTER(C.c_int32), i32, C.c_double, i32, C.POINTER(ReadCov)]
         L.mc_classify_reads_dev.argtypes = [vp, vp, vp, u64, vp, i32, C.c_double, i32, vp]
+    if hasattr(L, "mc_reads_last_copy"):
+        u8p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+        L.mc_reads_last_copy.argtypes = [vp, u64p, u64p, u64, i32, u32p]
+        L.mc_reads_last_copy_dev.argtypes = [vp, vp, vp, u64, i32, vp]
+        L.mc_triple_classes.argtypes = [vp, C.POINTER(ReadCov), C.POINTER(ReadCov), u64p, u64p, u64, i32, u8p, u8p, u32p, u32p, u8p, u8p]
+        L.mc_triple_classes_dev.argtypes = [vp] + [vp] * 4 + [u64, i32] + [vp] * 6
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -294,13 +303,9 @@ class Context:
         return out
 
     # ---- reads-classifier
-    def classify_reads(self, codes_or_words, offsets, bad_pos=None, found=90, z=1.0, correction=False, packed=None):
-        """Per-read coverage of a read set in this table (mc_classify_reads): returns numpy arrays sum, covered, last, found.
-        codes_or_words: base codes 0..3 (uint8, one a base; N already turned into 0) or the packed words with their pad word
-        (uint64; packed=None tells them apart by dtype); offsets: n_reads + 1 base offsets.  bad_pos: per read the only position
-        with phred < 10, -1 for none, -2 for several (None: none anywhere).  found: the breadth threshold in percent; z: 1 or 1.96."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = len(offsets) - 1
+    @staticmethod
+    def _words(codes_or_words, offsets, packed):
+        """the packed words (with their pad word) of base codes 0..3 (uint8) or of words already packed (uint64)"""
         a = np.asarray(codes_or_words)
         if packed is None:
             packed = a.dtype == np.uint64
@@ -313,8 +318,18 @@ class Context:
                 pad = (-len(codes)) % 32
                 c = np.concatenate([codes & 3, np.zeros(pad, dtype=np.uint8)]).reshape(-1, 32).astype(np.uint64)
                 words[:len(c)] = np.bitwise_or.reduce(c << (np.uint64(62) - np.uint64(2) * np.arange(32, dtype=np.uint64)), axis=1)
-        if n > 0 and len(words) < (int(offsets[-1]) + 31) // 32 + 1:
+        if len(offsets) > 1 and len(words) < (int(offsets[-1]) + 31) // 32 + 1:
             raise ValueError("words[] must hold ceil(n_bases/32) + 1 entries")
+        return words
+
+    def classify_reads(self, codes_or_words, offsets, bad_pos=None, found=90, z=1.0, correction=False, packed=None):
+        """Per-read coverage of a read set in this table (mc_classify_reads): returns numpy arrays sum, covered, last, found.
+        codes_or_words: base codes 0..3 (uint8, one a base; N already turned into 0) or the packed words with their pad word
+        (uint64; packed=None tells them apart by dtype); offsets: n_reads + 1 base offsets.  bad_pos: per read the only position
+        with phred < 10, -1 for none, -2 for several (None: none anywhere).  found: the breadth threshold in percent; z: 1 or 1.96."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        words = self._words(codes_or_words, offsets, packed)
         bp = None if bad_pos is None else np.ascontiguousarray(bad_pos, dtype=np.int32)
         if bp is not None and len(bp) != n:
             raise ValueError("bad_pos needs one entry a read")
@@ -328,6 +343,63 @@ class Context:
         """mc_classify_reads_dev: d_out holds 12 bytes a read (mc_read_cov)"""
         self._chk(self._L.mc_classify_reads_dev(self._h, _dptr(d_words), _dptr(d_offsets), int(n_reads), _dptr(d_bad_pos), int(found),
                                                 float(z), CLASSIFY_CORRECTION if correction else 0, _dptr(d_out)))
+
+    # ---- triple-reads-classifier
+    def reads_last_copy(self, codes_or_words, offsets, weak=False, packed=None):
+        """mc_reads_last_copy: for every read, the greatest index of a read with the same bases (uint32 array).  Reads as in
+        classify_reads.  weak: the tests' 4-bit first fingerprint (the result is the same)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(len(offsets) - 1, 0)
+        words = self._words(codes_or_words, offsets, packed)
+        out = np.zeros(n, dtype=np.uint32)
+        self._chk(self._L.mc_reads_last_copy(self._h, _p(words, C.c_uint64), _p(offsets, C.c_uint64), n, LAST_COPY_WEAK_FP if weak else 0,
+                                             _p(out, C.c_uint32)))
+        return out
+
+    def reads_last_copy_dev(self, d_words, d_offsets, n_reads, d_last, weak=False):
+        """mc_reads_last_copy_dev: d_last holds 4 bytes a read"""
+        self._chk(self._L.mc_reads_last_copy_dev(self._h, _dptr(d_words), _dptr(d_offsets), int(n_reads), LAST_COPY_WEAK_FP if weak else 0,
+                                                 _dptr(d_last)))
+
+    @staticmethod
+    def _covs(cov):
+        """mc_read_cov records from a READ_COV_DTYPE array or from classify_reads' (sum, covered, last, found)"""
+        if isinstance(cov, np.ndarray) and cov.dtype == READ_COV_DTYPE:
+            return np.ascontiguousarray(cov)
+        s, c, last, f = cov
+        out = np.zeros(len(s), dtype=READ_COV_DTYPE)
+        out["sum"], out["covered"], out["last"], out["found"] = s, c, last, np.asarray(f).astype(np.uint8)
+        return out
+
+    def triple_classes(self, cov1, cov2, offsets1, offsets2, half=40, prev=None, last=None):
+        """mc_triple_classes at this context's k: the classes (uint8 arrays, CLASS_*) of both mates of every pair.  cov1 / cov2: what
+        classify_reads returned for each side (or READ_COV_DTYPE arrays); offsets1 / offsets2: each side's n_pairs + 1 offsets.  Pass 2:
+        prev = (pass-1 classes of side 1, of side 2), last = (reads_last_copy of side 1, of side 2)."""
+        c1, c2 = self._covs(cov1), self._covs(cov2)
+        o1, o2 = (np.ascontiguousarray(o, dtype=np.uint64) for o in (offsets1, offsets2))
+        n = len(c1)
+        if len(c2) != n or len(o1) != n + 1 or len(o2) != n + 1:
+            raise ValueError("both sides need one record a pair and n_pairs + 1 offsets")
+        p1 = p2 = l1 = l2 = None
+        if prev is not None:
+            p1, p2 = (np.ascontiguousarray(p, dtype=np.uint8) for p in prev)
+            l1, l2 = (np.ascontiguousarray(x, dtype=np.uint32) for x in last)
+            if not all(len(x) == n for x in (p1, p2, l1, l2)):
+                raise ValueError("pass 2 needs one class and one last copy a read")
+        k1, k2 = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        cp = lambda a: a.ctypes.data_as(C.POINTER(ReadCov))  # noqa: E731
+        opt = lambda a, t: _p(a, t) if a is not None else None  # noqa: E731
+        self._chk(self._L.mc_triple_classes(self._h, cp(c1), cp(c2), _p(o1, C.c_uint64), _p(o2, C.c_uint64), n, int(half),
+                                            opt(p1, C.c_uint8), opt(p2, C.c_uint8), opt(l1, C.c_uint32), opt(l2, C.c_uint32),
+                                            _p(k1, C.c_uint8), _p(k2, C.c_uint8)))
+        return k1, k2
+
+    def triple_classes_dev(self, d_cov1, d_cov2, d_offsets1, d_offsets2, n_pairs, d_class1, d_class2, half=40, d_prev1=None, d_prev2=None,
+                           d_last1=None, d_last2=None):
+        """mc_triple_classes_dev: d_cov* hold 12 bytes a read (mc_read_cov), d_class* one byte"""
+        self._chk(self._L.mc_triple_classes_dev(self._h, _dptr(d_cov1), _dptr(d_cov2), _dptr(d_offsets1), _dptr(d_offsets2), int(n_pairs),
+                                                int(half), _dptr(d_prev1), _dptr(d_prev2), _dptr(d_last1), _dptr(d_last2), _dptr(d_class1),
+                                                _dptr(d_class2)))
 
     # ---- BFS
     def bfs_batch(self, jobs, min_cov, max_kmers=-1, max_radius=-1):
