@@ -422,6 +422,29 @@ int mc_triple_classes(mc_ctx *ctx, const mc_read_cov *cov1, const mc_read_cov *c
                       uint64_t n_pairs, int half_pct, const uint8_t *prev1, const uint8_t *prev2, const uint32_t *last1,
                       const uint32_t *last2, uint8_t *class1, uint8_t *class2);
 
+/* ---- seq-cov: depth and breadth of every sequence's k-mers in up to four tables at once (src/tools/SequenceCoverage.java:162-185).
+ * Sequences come in the layout of mc_classify_reads (whole, N as code 0, the pad word); they may be reads, genes or contigs of any
+ * length: the work is cut by base positions, not by sequences.  For sequence s of length L and table t, with
+ * cov[i] = getWithZero(key of window i) as mc_classify_reads defines it (the saturated count, 0 when absent; the contexts' key mode):
+ *   out[s * n_tables + t].depth = sum of cov[i] (64 bits: it does not wrap), .breadth = #{i : cov[i] > 0}, over i = 0 .. L - k;
+ * both 0 when L < k.  (No "last window" extension: that is findRead's.)  A window is keyed once and looked up in all n_tables tables.
+ * tables: n_tables contexts (1 .. MC_SEQ_COV_MAX_TABLES) with the same k, key mode and device, each after mc_finalize_counts; the
+ * same context may be named more than once.  A table of hash keys still in minimizer bins is moved to hash-prefix regions first, as
+ * mc_classify_reads does.  The kernel runs on tables[0]'s stream, and messages go to tables[0]'s last error.
+ * Errors: MC_EINVAL for null pointers, n_tables of 0 or above MC_SEQ_COV_MAX_TABLES, or contexts that differ in k, key mode or
+ * device; MC_ESTATE when a context is not finalized.  n_seqs == 0 is MC_OK after these checks.  out is not written on an error.
+ * mc_seq_coverage takes host pointers (words: ceil(n_bases / 32) + 1 entries), mc_seq_coverage_dev device ones (d_out: n_seqs *
+ * n_tables entries, zeroed by the call). */
+typedef struct {
+    uint64_t depth;   /* sum of the windows' coverages */
+    uint64_t breadth; /* windows with coverage > 0 */
+} mc_seq_cov;
+#define MC_SEQ_COV_MAX_TABLES 4
+int mc_seq_coverage_dev(mc_ctx *const *tables, uint32_t n_tables, const uint64_t *d_words, const uint64_t *d_seq_offsets,
+                        uint64_t n_seqs, mc_seq_cov *d_out);
+int mc_seq_coverage(mc_ctx *const *tables, uint32_t n_tables, const uint64_t *words, const uint64_t *seq_offsets, uint64_t n_seqs,
+                    mc_seq_cov *out);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

@@ -4,6 +4,6 @@ The product is libmcgpu.so (hand-written HIP for gfx950 behind the C ABI of incl
 the C++ host tool; this package only binds it for tests, benchmarks and multi-GPU orchestration.
 """
 from . import native  # noqa: F401
-from .native import KEY_FNV1A, KEY_PACKED, KEY_POLY, Context, McError  # noqa: F401
+from .native import KEY_FNV1A, KEY_PACKED, KEY_POLY, Context, McError, seq_coverage, seq_coverage_dev  # noqa: F401
 
-__all__ = ["native", "Context", "McError", "KEY_PACKED", "KEY_POLY", "KEY_FNV1A"]
+__all__ = ["native", "Context", "McError", "KEY_PACKED", "KEY_POLY", "KEY_FNV1A", "seq_coverage", "seq_coverage_dev"]

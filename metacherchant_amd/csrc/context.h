@@ -1,6 +1,6 @@
 // The library's context and what more than one unit of it needs (host side; private to libmcgpu.so, not include/mcgpu.h).
 //
-// The library is six units, each defining and launching its own kernels:
+// The library is seven units, each defining and launching its own kernels:
 //   mcgpu.hip       the table, the key join, the counting pipeline, the context ABI, and the table work of the walk (solid table,
 //                   the check of its "absent" look-ups)
 //   reads_file.hip  the device tokeniser's driver and mc_add_reads_file
@@ -8,6 +8,7 @@
 //   group.hip       mc_group_* (no kernels)
 //   classify.hip    mc_classify_reads*: the reads-classifier's per-read coverage (classify.h: its verdict), and mc_triple_classes*
 //   last_copy.hip   mc_reads_last_copy*: the last read with the same bases, for the triple-reads-classifier (hipCUB's radix sort)
+//   seq_cov.hip     mc_seq_coverage*: depth and breadth of sequences of any length in up to four tables at once, cut by positions
 // A function below the "across units" line is what one unit lends another; everything else stays static in its unit.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1393,6 +1393,35 @@ std::string java_format_2f(double x)
     return std::signbit(x) ? "-" + body : body;
 }
 
+std::string java_double_to_string(double x)
+{
+    if (x != x) return "NaN";
+    if (std::isinf(x)) return x > 0 ? "Infinity" : "-Infinity";
+    const std::string sign = std::signbit(x) ? "-" : "";
+    if (x == 0) return sign + "0.0";
+    const double a = x < 0 ? -x : x;
+    // the shortest decimal that reads back as x, as in java_format_2f
+    char buf[64];
+    for (int prec = 1; prec <= 17; prec++) {
+        snprintf(buf, sizeof buf, "%.*e", prec - 1, a);
+        if (strtod(buf, nullptr) == a) break;
+    }
+    const std::string m = buf;  // d.ddddde[+-]XX
+    const size_t e = m.find('e');
+    const int exp10 = atoi(m.c_str() + e + 1);  // value = d.ddd x 10^exp10
+    std::string digits;
+    for (size_t i = 0; i < e; i++)
+        if (m[i] != '.') digits.push_back(m[i]);
+    while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
+    if (a >= 1e-3 && a < 1e7) {  // plain notation, at least one digit on either side of the point
+        const int point = exp10 + 1;  // digits before the point
+        if (point <= 0) return sign + "0." + std::string((size_t)-point, '0') + digits;
+        if ((size_t)point >= digits.size()) return sign + digits + std::string((size_t)point - digits.size(), '0') + ".0";
+        return sign + digits.substr(0, (size_t)point) + "." + digits.substr((size_t)point);
+    }
+    return sign + digits.substr(0, 1) + "." + (digits.size() > 1 ? digits.substr(1) : "0") + "E" + std::to_string(exp10);
+}
+
 // ------------------------------------------------------------------------------------------ Environment
 
 // ---- packed k-mers

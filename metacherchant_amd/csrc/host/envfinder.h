@@ -161,6 +161,9 @@ private:
 };
 // String.format("%.2f", x) for a double: HALF_UP on the shortest decimal that reads back as x (Java's FormattedFloatingDecimal)
 std::string java_format_2f(double x);
+// Double.toString as JDK 19 and later document it: the shortest decimal that reads back as x, at least one digit after the point,
+// plain notation for 10^-3 <= |x| < 10^7 and d.dddE[-]n outside it (seq-cov's columns, src/tools/SequenceCoverage.java:184)
+std::string java_double_to_string(double x);
 
 // ---- 2-bit packed k-mers (k <= 63): base i of the string is bits 2(k-1-i)+1..2(k-1-i), codes A0 G1 C2 T3,
 // the layout of mc_bfs_result's hi/lo words (include/mcgpu.h)

@@ -4,8 +4,9 @@
 //
 // dump format (text): k chunk_length trim n_genes / gene strings / n_passes / per pass: dir n /
 // n lines "kmer dist cov last".  Also: `mc_hosttest seeds <fasta>` and `mc_hosttest reads <file>`
-// print what the seed reader / read ingest deliver.
+// print what the seed reader / read ingest deliver; `fmt` and `dtoa` print Java's number formats.
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <functional>
 #include <iostream>
@@ -40,6 +41,21 @@ int main(int argc, char **argv)
             fputs(java_format_6_2f(strtof(argv[2], nullptr)).c_str(), stdout);
             return 0;
         }
+        if (argc == 3 && std::string(argv[1]) == "dtoa") {  // Double.toString of every double of the file (hex bit patterns, one a line)
+            std::ifstream f(argv[2]);
+            if (!f) throw Error("cannot open the file of doubles");
+            std::string out;
+            for (std::string line; std::getline(f, line);) {
+                if (line.empty()) continue;
+                const uint64_t bits = strtoull(line.c_str(), nullptr, 16);
+                double x;
+                memcpy(&x, &bits, 8);
+                out += java_double_to_string(x);
+                out.push_back('\n');
+            }
+            fwrite(out.data(), 1, out.size(), stdout);
+            return 0;
+        }
         if (argc == 3 && std::string(argv[1]) == "hashmap") {  // put every k-mer string of the file ("-kmer": remove it as an iterator does, "~kmer": as HashMap.remove does), print both maps' orders
             std::ifstream f(argv[2]);
             if (!f) throw Error("cannot open key file");
@@ -66,7 +82,7 @@ int main(int argc, char **argv)
             return 0;
         }
         if (argc != 4 || std::string(argv[1]) != "env") {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | seeds <fasta> | reads <file> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

@@ -77,6 +77,9 @@ struct Options {
     int k2 = -1;
     std::vector<std::string> input_kmers_1, input_kmers_2;
     long long half_threshold = 40;
+    // --tool seq-cov (src/tools/SequenceCoverage.java:30-72)
+    std::vector<std::string> from_before, from_donor, from_both, itself;
+    std::string read_file;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -104,6 +107,14 @@ const OptSpec TRIPLE_SPECS[] = {
     {"k", "k", 0}, {"k2", "k2", 0}, {"input-files", "i", 2}, {"input-kmers-1", "ik1", 2}, {"input-kmers-2", "ik2", 2}, {"read-files", "r", 2},
     {"output-dir", "o", 0}, {"hash", nullptr, 0}, {"correction", "corr", 1}, {"interval95", nullptr, 1}, {"found-threshold", "found", 0},
     {"half-threshold", "half", 0},
+    {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
+};
+
+// --tool seq-cov: its parameters (SequenceCoverage.java:30-72) and the launch options
+const OptSpec SEQ_COV_SPECS[] = {
+    {"k", "k", 0}, {"from-before", nullptr, 2}, {"from-donor", nullptr, 2}, {"from-both", nullptr, 2}, {"itself", nullptr, 2},
+    {"read-file", "r", 0}, {"output-dir", "o", 0}, {"hash", nullptr, 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
 };
@@ -153,6 +164,7 @@ Options parse_args(int argc, char **argv)
     const std::string tool = tool_of(argc, argv);
     const SpecTable specs = tool == "reads-classifier"          ? SpecTable{std::begin(CLASSIFIER_SPECS), std::end(CLASSIFIER_SPECS)}
                             : tool == "triple-reads-classifier" ? SpecTable{std::begin(TRIPLE_SPECS), std::end(TRIPLE_SPECS)}
+                            : tool == "seq-cov"                 ? SpecTable{std::begin(SEQ_COV_SPECS), std::end(SEQ_COV_SPECS)}
                                                                 : SpecTable{std::begin(SPECS), std::end(SPECS)};
     std::map<std::string, std::vector<std::string>> got;
     for (int i = 1; i < argc; i++) {
@@ -197,6 +209,11 @@ Options parse_args(int argc, char **argv)
     multi("env", o.env);
     multi("input-files", o.input_files);
     multi("read-files", o.read_files);
+    multi("from-before", o.from_before);
+    multi("from-donor", o.from_donor);
+    multi("from-both", o.from_both);
+    multi("itself", o.itself);
+    if (auto v = val("read-file")) o.read_file = *v;
     if (auto v = val("correction")) o.correction = java_bool(*v);
     if (auto v = val("interval95")) o.interval95 = java_bool(*v);
     if (auto v = val("found-threshold")) o.found_threshold = parse_int("found-threshold", *v);
@@ -290,6 +307,15 @@ void usage()
     puts("      --interval95 [<arg>]       set the interval width to probability 0.95 (default false)");
     puts("  -found, --found-threshold <arg>  minimum coverage breadth for class `found`, 0 - 100 % (default 90)");
     puts("  -half, --half-threshold <arg>  minimum coverage breadth for class `half-found`, 0 - 100 % (default 40)");
+    puts("Input parameters of --tool seq-cov (depth and breadth of every sequence's k-mers in four bins of reads; writes seq_cov.csv):");
+    puts("  -k, --k <arg>                  k-mer size (MANDATORY)");
+    puts("      --from-before <args>       reads of the came_from_before bin (MANDATORY)");
+    puts("      --from-donor <args>        reads of the came_from_donor bin (MANDATORY)");
+    puts("      --from-both <args>         reads of the came_from_both bin (MANDATORY)");
+    puts("      --itself <args>            reads of the came_itself bin (MANDATORY)");
+    puts("  -r, --read-file <arg>          file with sequences to classify: reads, genes or contigs (MANDATORY)");
+    puts("  -o, --output-dir <arg>         directory of seq_cov.csv (default <work-dir>/sequence_coverage)");
+    puts("      --hash <arg>               hash function to use for k > 31: poly or fnv1a (default poly)");
     puts("Launch options: -w/--work-dir <dir> (default workDir), -c/--continue, --force, -v/--verbose, -h/--help,");
     puts("                -t/--tool <name>, -p/--available-processors <n> and -m/--memory <arg> (accepted, unused),");
     puts("                --device <n> (GPU ordinal), --devices <a,b,...|a-b> (several GPUs as one table: reads dealt to them,");
@@ -884,15 +910,112 @@ int run_triple_reads_classifier(const Options &o)
     return 0;
 }
 
+// --tool seq-cov (src/tools/SequenceCoverage.java:127-185): four bins of reads counted into four tables (every k-mer), then for
+// every sequence of --read-file the mean depth and the breadth of its k-mers in each (mc_seq_coverage: one key, four probes a
+// window).  Nothing walks these tables: no read store is kept, and a table's counting scratch goes back before the next is counted.
+struct SeqCovBin { const char *param; const std::vector<std::string> *files; };
+
+// one batch of whole sequences through mc_seq_coverage, and its rows
+void seq_cov_batch(mc_ctx *const *tables, const DnaQBatch &b, int k, FILE *out)
+{
+    const size_t n = b.n_reads();
+    if (n == 0) return;
+    const uint64_t n_bases = b.offsets[n];
+    std::vector<uint64_t> words((n_bases + 31) / 32 + 1, 0);
+    for (uint64_t i = 0; i < n_bases; i++) words[i >> 5] |= (uint64_t)(b.codes[i] & 3) << (62 - 2 * (i & 31));
+    std::vector<mc_seq_cov> cov(n * 4);
+    MC_CHECK(tables[0], mc_seq_coverage(tables, 4, words.data(), b.offsets.data(), n, cov.data()));
+    std::string line;
+    for (size_t s = 0; s < n; s++) {
+        const uint64_t len = b.offsets[s + 1] - b.offsets[s];
+        line.resize(len);  // dna.toString(): N is A already (a contig's row is megabytes: built once, written, reused)
+        for (uint64_t i = 0; i < len; i++) line[i] = "AGCT"[b.codes[b.offsets[s] + i] & 3];
+        const double windows = (double)((int32_t)len - k + 1);  // (a Java int; 0 or negative for a sequence shorter than k)
+        for (int t = 0; t < 4; t++) {
+            line += ", " + java_double_to_string((double)cov[s * 4 + t].depth / windows);  // depth * 1. / n: NaN for 0.0 / 0, -0.0 for 0.0 / negative
+            line += ", " + java_double_to_string((double)cov[s * 4 + t].breadth / windows);
+        }
+        line.push_back('\n');
+        if (fwrite(line.data(), 1, line.size(), out) != line.size()) throw Error("cannot write seq_cov.csv");
+    }
+}
+
+int run_seq_cov(const Options &o)
+{
+    // the reference's order of bins (runImpl: donor, before, both, itself), whatever the command line's
+    const SeqCovBin bins[4] = {{"from-donor", &o.from_donor}, {"from-before", &o.from_before}, {"from-both", &o.from_both}, {"itself", &o.itself}};
+    if (o.k < 0) throw Error("Parameter 'k' is mandatory");
+    for (const SeqCovBin &b : {bins[1], bins[0], bins[2], bins[3]})  // (the order the tool declares them in)
+        if (b.files->empty()) throw Error(std::string("Parameter '") + b.param + "' is mandatory");
+    if (o.read_file.empty()) throw Error("Parameter 'read-file' is mandatory");
+    if (o.k < 1 || o.k > 63)
+        throw Error("k = " + std::to_string(o.k) + " is not supported: this build handles k <= 31 (packed keys) and 32 <= k <= 63 (hash keys)");
+    if (!open_work_dir(o, "k=" + std::to_string(o.k) + "\n")) return 0;
+    const std::string out_dir = o.output_dir.empty() ? o.work_dir + "/sequence_coverage" : o.output_dir;
+    write_file(out_dir + "/.keep", "");  // outputDir.mkdirs()
+    remove((out_dir + "/.keep").c_str());
+
+    info("Loading bins ...");
+    Engine E[4];
+    mc_ctx *tables[4];
+    for (int t = 0; t < 4; t++) {  // loadGraph (SequenceCoverage.java:87-101)
+        int mode = MC_KEY_PACKED;
+        if (o.k > 31) {
+            info("Reading hashes of k-mers instead");
+            std::string h = o.hash;
+            for (char &c : h) c = (char)tolower((unsigned char)c);
+            if (h == "fnv1a") { info("Using FNV1a hash function"); mode = MC_KEY_FNV1A; }
+            else { info("Using default polynomial hash function"); mode = MC_KEY_POLY; }
+        }
+        mc_config cfg{};
+        cfg.k = o.k;
+        cfg.key_mode = mode;
+        cfg.device = o.device;
+        cfg.capacity_hint = o.capacity_hint;
+        E[t].open(cfg, {});
+        tables[t] = E[t].c;
+        MC_CHECK(tables[t], mc_set_read_pointers(tables[t], 0));  // (no walk: no read store)
+        load_reads(*bins[t].files, E[t]);
+        MC_CHECK(tables[t], mc_trim(tables[t]));  // (four tables fit where four sets of staging buffers would not)
+    }
+
+    info("Calculating sequence coverage...");
+    DnaQReader reader(o.read_file);
+    FILE *out = fopen((out_dir + "/seq_cov.csv").c_str(), "w");
+    if (!out) throw Error("cannot create " + out_dir + "/seq_cov.csv");
+    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{out};
+    fputs("name, from_donor_depth, from_donor_breadth, from_before_depth, from_before_breadth"
+          ", from_both_depth, from_both_breadth, itself_depth, itself_breadth\n", out);
+    // batches bounded by bases (a batch grows to hold one sequence that is longer); rows in input order
+    constexpr uint64_t BATCH_BASES = 256ull << 20;
+    constexpr size_t BATCH_SEQS = 1u << 22;
+    DnaQBatch b;
+    b.clear();
+    for (;;) {
+        const size_t got = reader.read(b, 1);
+        if (got == 0 || b.codes.size() >= BATCH_BASES || b.n_reads() >= BATCH_SEQS) {
+            seq_cov_batch(tables, b, o.k, out);
+            b.clear();
+        }
+        if (got == 0) break;
+    }
+    closer.f = nullptr;
+    if (fclose(out) != 0) throw Error("cannot write seq_cov.csv");
+    info("Processed all sequences...");
+    write_file(o.work_dir + "/SUCCESS", "");
+    return 0;
+}
+
 int run(const Options &o)
 {
     if (o.tool == "kmer-counter") return run_kmer_counter(o);
     if (o.tool == "environment-finder-multi") return run_multi(o);
     if (o.tool == "reads-classifier") return run_reads_classifier(o);
     if (o.tool == "triple-reads-classifier") return run_triple_reads_classifier(o);
+    if (o.tool == "seq-cov") return run_seq_cov(o);
     if (o.tool != "environment-finder")
         throw Error("Tool '" + o.tool + "' is not part of this build: only environment-finder, kmer-counter, environment-finder-multi, "
-                    "reads-classifier and triple-reads-classifier are");
+                    "reads-classifier, triple-reads-classifier and seq-cov are");
     if (o.k < 0) throw Error("Parameter 'k' is mandatory");
     if (o.seq.empty()) throw Error("Parameter 'seq' is mandatory");
     if (o.output.empty()) throw Error("Parameter 'output' is mandatory");

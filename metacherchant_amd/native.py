@@ -69,6 +69,7 @@ READ_COV_DTYPE = np.dtype([("sum", np.int32), ("covered", np.int32), ("last", np
 CLASSIFY_CORRECTION = 1  # mc_classify_reads flags: findReadWithCorrection
 LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fingerprint, so distinct reads share one
 CLASS_NOT_FOUND, CLASS_HALF_FOUND, CLASS_FOUND = 0, 1, 2  # mc_triple_classes
+SEQ_COV_MAX_TABLES = 4  # mc_seq_coverage
 
 
 # every symbol include/mcgpu.h declares; tests check that the library exports all of them
@@ -81,7 +82,7 @@ EXPORTS = [
     "mc_superkmer_fine_buckets", "mc_extract_superkmers_binned_dev", "mc_add_superkmers_binned_dev",
     "mc_read_store_seek", "mc_read_store_tell", "mc_read_store_import_dev", "mc_get_stats", "mc_reset_stats", "mc_trim", "mc_synth_reads_dev", "mc_synth_genome",
     "mc_shard_export", "mc_shard_attach", "mc_shard_detach", "mc_classify_reads", "mc_classify_reads_dev",
-    "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev",
+    "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev", "mc_seq_coverage", "mc_seq_coverage_dev",
 ]
 
 _LIB = None
@@ -168,6 +169,9 @@ def load():
         L.mc_reads_last_copy_dev.argtypes = [vp, vp, vp, u64, i32, vp]
         L.mc_triple_classes.argtypes = [vp, C.POINTER(ReadCov), C.POINTER(ReadCov), u64p, u64p, u64, i32, u8p, u8p, u32p, u32p, u8p, u8p]
         L.mc_triple_classes_dev.argtypes = [vp] + [vp] * 4 + [u64, i32] + [vp] * 6
+    if hasattr(L, "mc_seq_coverage"):
+        L.mc_seq_coverage.argtypes = [C.POINTER(vp), C.c_uint32, u64p, u64p, u64, vp]
+        L.mc_seq_coverage_dev.argtypes = [C.POINTER(vp), C.c_uint32, vp, vp, u64, vp]
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -560,6 +564,35 @@ class Context:
                         err_per_10k, d_words, d_offsets):
         self._chk(self._L.mc_synth_reads_dev(self._h, genome_seed, n_contigs, contig_len, read_seed, first_read,
                                              n_reads, read_len, err_per_10k, _dptr(d_words), _dptr(d_offsets)))
+
+
+def _table_handles(contexts):
+    contexts = list(contexts)
+    return contexts, (C.c_void_p * max(len(contexts), 1))(*[c._h for c in contexts])
+
+
+def seq_coverage(contexts, codes_or_words, offsets, packed=None):
+    """mc_seq_coverage: depth and breadth of every sequence's k-mers in each of the contexts' tables (1 .. SEQ_COV_MAX_TABLES contexts of
+    one k, key mode and device, finalized; the same one may come several times).  Sequences as Context.classify_reads takes reads: base
+    codes 0..3 (uint8, N already 0) or packed words, and n_seqs + 1 base offsets.  Returns uint64 [n_seqs, n_tables, 2]: the sum of
+    the windows' coverages and the number of covered windows."""
+    contexts, handles = _table_handles(contexts)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = max(len(offsets) - 1, 0)
+    words = Context._words(codes_or_words, offsets, packed)
+    out = np.zeros((n, len(contexts), 2), dtype=np.uint64)
+    rc = load().mc_seq_coverage(handles, len(contexts), _p(words, C.c_uint64), _p(offsets, C.c_uint64), n, out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise McError(rc, (load().mc_last_error(contexts[0]._h) or b"").decode() if contexts else "")
+    return out
+
+
+def seq_coverage_dev(contexts, d_words, d_offsets, n_seqs, d_out):
+    """mc_seq_coverage_dev: d_out holds n_seqs * n_tables * 2 uint64 (mc_seq_cov records); the call zeroes it first"""
+    contexts, handles = _table_handles(contexts)
+    rc = load().mc_seq_coverage_dev(handles, len(contexts), _dptr(d_words), _dptr(d_offsets), int(n_seqs), _dptr(d_out))
+    if rc != 0:
+        raise McError(rc, (load().mc_last_error(contexts[0]._h) or b"").decode() if contexts else "")
 
 
 def key_owner(key, n_owners):

@@ -10,18 +10,51 @@
 # A third leg, when MC_PATCHED_JAR names a jar built from the reference with integration/patches/* applied and
 # integration/java/gpu/McGpu.java + integration/jni/mcgpu_jni.c built (integration/README.md): the same command with
 # MC_GPU_DEVICE=0, i.e. the original Java host over the C ABI, diffed against the other two.
+#   MC_REFERENCE_JAR=... scripts/compare_with_java.sh seq-cov [n_reads] [k]
+# runs `--tool seq-cov` both ways instead: four bins of n_reads / 4 reads each, the sequences of --read-file a few reads, one shorter
+# than k - 1, one of k - 1 bases and a contig; seq_cov.csv is compared byte for byte (the doubles are Double.toString's: a JDK
+# before 19 may print a digit more for rare values).
 # Exit status 0 = every file identical.  The Java log's timestamps around "Loading file" ... "Hashtable size" ...
 # "Finished processing all sequences!" are printed as the reference's phase times on this box's cores.
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
+if [ "${1:-}" != "seq-cov" ]; then
 N=${1:-200000}; K=${2:-31}; shift $(( $# > 2 ? 2 : $# )) || true
 EXTRA=("$@")
 [ ${#EXTRA[@]} -eq 0 ] && EXTRA=(--coverage 5 --maxkmers 100000 --bothdirs False)
+fi
 command -v java >/dev/null || { echo "no java on PATH: this script needs a JVM (the graft image has none)"; exit 2; }
 [ -f "${MC_REFERENCE_JAR:-}" ] || { echo "set MC_REFERENCE_JAR to the reference's metacherchant.jar"; exit 2; }
 CLI="$ROOT/metacherchant_amd/lib/metacherchant"
 [ -x "$CLI" ] || python3 -c "import sys; sys.path.insert(0, '$ROOT'); import __graft_entry__ as g; g.build()"
 W="$(mktemp -d)"; trap 'rm -rf "$W"' EXIT
+if [ "${1:-}" = "seq-cov" ]; then
+    N=${2:-200000}; K=${3:-31}
+    python3 - "$ROOT" "$W" "$N" "$K" <<'PY'
+import sys
+root, w, n, k = sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
+sys.path.insert(0, root)
+from oracle import pyoracle as po
+L = 150
+glen = max(20000, n * L // 30)
+genome = po.synth_genome(20240531, glen)
+for i, name in enumerate(("donor", "before", "both", "itself")):
+    reads = po.synth_reads(genome, 1, glen, 42 + i, 0, n // 4, L, 100)
+    with open("%s/%s.fasta" % (w, name), "w") as f:
+        for r in range(n // 4):
+            f.write(">r%d\n%s\n" % (r, po.decode(reads[r * L:(r + 1) * L])))
+q = po.synth_reads(genome, 1, glen, 4242, 0, 1000, L, 100)
+with open(w + "/seqs.fasta", "w") as f:
+    for r in range(1000):
+        f.write(">q%d\n%s\n" % (r, po.decode(q[r * L:(r + 1) * L])))
+    f.write(">short\n%s\n>nan\n%s\n>contig\n%s\n" % (po.decode(genome[:k - 2]), po.decode(genome[:k - 1]), po.decode(genome[:glen // 2])))
+PY
+    BINS=(--from-donor "$W/donor.fasta" --from-before "$W/before.fasta" --from-both "$W/both.fasta" --itself "$W/itself.fasta" -r "$W/seqs.fasta")
+    java -jar "$MC_REFERENCE_JAR" --tool seq-cov -k "$K" "${BINS[@]}" -o "$W/java_out" --work-dir "$W/java_wd" --force > "$W/java.stdout" 2> "$W/java.log"
+    "$CLI" --tool seq-cov -k "$K" "${BINS[@]}" -o "$W/hip_out" --work-dir "$W/hip_wd" --force 2> "$W/hip.log"
+    if cmp -s "$W/java_out/seq_cov.csv" "$W/hip_out/seq_cov.csv"; then echo "identical  seq_cov.csv"; exit 0; fi
+    echo "DIFFERENT  seq_cov.csv"; exit 1
+fi
 python3 - "$ROOT" "$W" "$N" <<'PY'
 import sys
 root, w, n = sys.argv[1], sys.argv[2], int(sys.argv[3])
