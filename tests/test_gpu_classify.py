@@ -9,7 +9,7 @@ from tests.helpers import ragged_case
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(15, 0), (31, 0), (45, 1), (63, 1), (63, 2)]  # (k, key mode): packed, polynomial, FNV-1a
+CASES = [(15, 0), (31, 0), (45, 1), (63, 1), (63, 2), (32, 1), (32, 2), (22, 0)]  # (k, key mode): packed, polynomial, FNV-1a
 
 
 def _graph_reads(k):

@@ -121,7 +121,8 @@ def test_cli_multi_sequence_dirs_and_flags(cli, tmp_path, extra, kw):
     _assert_same_tree(res, out, want)
 
 
-@pytest.mark.parametrize("k,hash_name,mode", [(41, "poly", po.KEY_POLY), (63, "fnv1a", po.KEY_FNV1A), (21, "poly", po.KEY_POLY)])
+@pytest.mark.parametrize("k,hash_name,mode", [(41, "poly", po.KEY_POLY), (63, "fnv1a", po.KEY_FNV1A), (21, "poly", po.KEY_POLY), (32, "poly", po.KEY_POLY),
+                                                 (32, "fnv1a", po.KEY_FNV1A)])
 def test_cli_hash_key_modes(cli, tmp_path, k, hash_name, mode):
     """k > 31 (or --forcehash): the table key is the reference's 64-bit hash (src/utils/*Hash.java)."""
     genome, reads, _ = synth_case(1, 30000, 5000, 150, 30)

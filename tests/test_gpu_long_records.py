@@ -91,7 +91,7 @@ def test_long_records_count_and_walk(mc, monkeypatch, k, bins):
 
 
 @pytest.mark.parametrize("bins", [None, "2"])
-@pytest.mark.parametrize("k", [33, 63, 50])
+@pytest.mark.parametrize("k", [33, 63, 50] + [k for k in range(34, 63) if k != 50])
 def test_long_records_of_ragged_reads(mc, monkeypatch, k, bins):
     """Empty reads, reads of k - 1, k and k + 1 bases, reads of every length up to 220: windows never span two reads (the
     128-bit read-start mask of k_skl_extract), runs are cut at 32 windows, tiles end inside reads."""

@@ -56,7 +56,7 @@ def test_count_config1_k31(mc, err, count_path):
     ctx.close()
 
 
-@pytest.mark.parametrize("k,mode", [(31, 0), (23, 0), (27, 0), (30, 0), (21, 0), (5, 0), (1, 0), (63, 1), (33, 1), (47, 2), (31, 1), (64 - 1, 2)])
+@pytest.mark.parametrize("k,mode", [(31, 0), (23, 0), (27, 0), (30, 0), (21, 0), (5, 0), (1, 0), (63, 1), (33, 1), (47, 2), (31, 1), (64 - 1, 2), (32, 1), (32, 2), (22, 0), (16, 1)])
 def test_count_ragged_reads_all_key_modes(mc, k, mode, count_path):
     """Empty reads, reads shorter than k, k-1, k, ragged lengths; packed key, poly and fnv1a hashes."""
     rng = np.random.default_rng(100 + k + mode)
@@ -126,6 +126,21 @@ def test_empty_input_and_state_errors(mc):
     ctx.close()
 
 
+def test_superkmer_records_are_for_packed_keys_from_k_23(mc):
+    """mc_superkmer_capacity: 0 -- count window by window, deal keys -- for every hashed context (k = 32 and its neighbours among
+    them) and for packed keys below SK_MIN_K = 23; records from there on."""
+    for mode in (mc.KEY_POLY, mc.KEY_FNV1A):
+        for k in range(1, 64):
+            with mc.Context(k, mode, 0, 0) as ctx:
+                assert ctx.superkmer_capacity(100000, 700) == 0, (k, mode)
+    for k in (1, 21, 22):
+        with mc.Context(k, mc.KEY_PACKED, 0, 0) as ctx:
+            assert ctx.superkmer_capacity(100000, 700) == 0, k
+    for k in (23, 31):
+        with mc.Context(k, mc.KEY_PACKED, 0, 0) as ctx:
+            assert ctx.superkmer_capacity(100000, 700) > 0, k
+
+
 def test_table_grows_from_small(mc, count_path):
     """No capacity hint: the table starts at 4 M slots and is rebuilt as it fills."""
     _, reads, off = synth_case(4, 2_000_000, 120_000, 150, 100)
@@ -189,7 +204,7 @@ def test_bfs_branching_graph_and_duplicate_seeds(mc):
     starts = rng.integers(0, len(genome) - L, n)
     reads = np.concatenate([genome[s:s + L] for s in starts])
     off = np.arange(n + 1, dtype=np.uint64) * L
-    for k, mode in [(21, po.KEY_PACKED), (31, po.KEY_PACKED), (33, po.KEY_POLY)]:
+    for k, mode in [(21, po.KEY_PACKED), (31, po.KEY_PACKED), (33, po.KEY_POLY), (32, po.KEY_POLY), (32, po.KEY_FNV1A)]:
         t, _ = oracle_table(reads, off, k, mode)
         ctx, nd = _gpu_table(mc, po.pack(reads), off, k, mode)
         _assert_tables_equal(ctx, nd, t)
@@ -621,7 +636,7 @@ def test_extract_keys_by_owner_and_merge_pairs(mc, count_path2, monkeypatch):
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(11)
     _, codes, off = ragged_case(rng, 900)
-    for k, mode in [(31, po.KEY_PACKED), (41, po.KEY_POLY)]:
+    for k, mode in [(31, po.KEY_PACKED), (41, po.KEY_POLY), (32, po.KEY_POLY)]:
         t, n = oracle_table(codes, off, k, mode)
         words = po.pack(codes)
         d_words = torch.from_numpy(words.view(np.int64)).to(dev)
@@ -713,7 +728,7 @@ def test_superkmer_records_by_owner(mc, k):
     merged.close()
 
 
-@pytest.mark.parametrize("k,mode_name", [(31, "KEY_PACKED"), (25, "KEY_PACKED"), (21, "KEY_PACKED"), (45, "KEY_POLY"), (31, "KEY_FNV1A")])
+@pytest.mark.parametrize("k,mode_name", [(31, "KEY_PACKED"), (25, "KEY_PACKED"), (21, "KEY_PACKED"), (45, "KEY_POLY"), (31, "KEY_FNV1A"), (32, "KEY_POLY")])
 def test_bfs_table_straight_from_gathered_pairs(mc, k, mode_name):
     """Rank 0's side of the gather: the exported shards, side by side with padding between them, go straight into a
     BFS-only context; the walk equals the oracle's on the table of all reads and still has its hints."""
@@ -800,7 +815,7 @@ def test_hints_survive_exchange_and_speed_up_the_walk(mc):
     ex.close()
 
 
-@pytest.mark.parametrize("k,mode,n_owners", [(31, "packed", 3), (27, "packed", 2), (41, "poly", 3), (21, "packed", 2)])
+@pytest.mark.parametrize("k,mode,n_owners", [(31, "packed", 3), (27, "packed", 2), (41, "poly", 3), (21, "packed", 2), (32, "poly", 2)])
 def test_walk_over_the_owners_tables_in_place(mc, k, mode, n_owners):
     """Several GPUs, the walk without a gather (include/mcgpu.h mc_shard_export / mc_shard_attach): the reads' super-k-mer
     records (keys for hash keys and k < 23) are dealt to `n_owners` contexts -- shares of the one GPU here --, every owner

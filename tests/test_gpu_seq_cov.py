@@ -9,7 +9,7 @@ from tests.helpers import synth_case
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(21, 0), (31, 0), (41, 1), (63, 1), (63, 2)]  # (k, key mode): packed, polynomial, FNV-1a
+CASES = [(21, 0), (31, 0), (41, 1), (63, 1), (63, 2), (32, 1)]  # (k, key mode): packed, polynomial, FNV-1a
 GENOME = 200000
 
 

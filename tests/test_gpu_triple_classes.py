@@ -9,7 +9,7 @@ from tests.test_gpu_classify import _graph_reads, _pack, _query_reads
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(21, 0, 41, 1), (31, 0, 63, 2)]  # (k, mode, k2, mode2): packed then polynomial, packed then FNV-1a
+CASES = [(21, 0, 41, 1), (31, 0, 63, 2), (22, 0, 32, 1)]  # (k, mode, k2, mode2): packed then polynomial, packed then FNV-1a
 
 
 @pytest.fixture(scope="module")
