@@ -445,6 +445,24 @@ int mc_seq_coverage_dev(mc_ctx *const *tables, uint32_t n_tables, const uint64_t
 int mc_seq_coverage(mc_ctx *const *tables, uint32_t n_tables, const uint64_t *words, const uint64_t *seq_offsets, uint64_t n_seqs,
                     mc_seq_cov *out);
 
+/* ---- presence: which of up to four tables hold each of n k-mers (BigLong2ShortHashMap.contains, as the recipient-visualiser asks
+ * it of its four class tables for every k-mer of an environment, src/tools/RecipientVisualiser.java:157-169).
+ * K-mers come as oriented packed k-mers in the layout of mc_bfs_result and mc_kmer_keys (hi may be NULL when k <= 32).
+ * mask[i] bit t is set exactly when tables[t] contains the key of k-mer i -- where mc_get would not answer -1; the key is the
+ * contexts' own (getKmerKey: the canonical packed k-mer, or the polynomial / FNV-1a hash, colliding hash keys sharing a counter as
+ * everywhere else), so a k-mer and its reverse complement get the same mask; key 0 (poly-A) is legal.  The k-mer is keyed once
+ * and looked up in all n_tables tables, in one launch.
+ * tables: n_tables contexts (1 .. MC_PRESENCE_MAX_TABLES) with the same k, key mode and device, each after mc_finalize_counts; the
+ * same context may be named more than once.  A table of hash keys still in minimizer bins is moved to hash-prefix regions first, as
+ * mc_classify_reads does.  The kernel runs on tables[0]'s stream, and messages go to tables[0]'s last error.
+ * Errors: MC_EINVAL for null pointers, n_tables of 0 or above MC_PRESENCE_MAX_TABLES, or contexts that differ in k, key mode or
+ * device; MC_ESTATE when a context is not finalized.  n == 0 is MC_OK after these checks.  mask is not written on an error.
+ * mc_kmer_presence takes host pointers, mc_kmer_presence_dev device ones. */
+#define MC_PRESENCE_MAX_TABLES 4
+int mc_kmer_presence_dev(mc_ctx *const *tables, uint32_t n_tables, const uint64_t *d_hi, const uint64_t *d_lo, uint64_t n,
+                         uint8_t *d_mask);
+int mc_kmer_presence(mc_ctx *const *tables, uint32_t n_tables, const uint64_t *hi, const uint64_t *lo, uint64_t n, uint8_t *mask);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

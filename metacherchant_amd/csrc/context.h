@@ -1,6 +1,6 @@
 // The library's context and what more than one unit of it needs (host side; private to libmcgpu.so, not include/mcgpu.h).
 //
-// The library is seven units, each defining and launching its own kernels:
+// The library is eight units, each defining and launching its own kernels:
 //   mcgpu.hip       the table, the key join, the counting pipeline, the context ABI, and the table work of the walk (solid table,
 //                   the check of its "absent" look-ups)
 //   reads_file.hip  the device tokeniser's driver and mc_add_reads_file
@@ -9,6 +9,7 @@
 //   classify.hip    mc_classify_reads*: the reads-classifier's per-read coverage (classify.h: its verdict), and mc_triple_classes*
 //   last_copy.hip   mc_reads_last_copy*: the last read with the same bases, for the triple-reads-classifier (hipCUB's radix sort)
 //   seq_cov.hip     mc_seq_coverage*: depth and breadth of sequences of any length in up to four tables at once, cut by positions
+//   presence.hip    mc_kmer_presence*: which of up to four tables hold each of a list of k-mers, one launch
 // A function below the "across units" line is what one unit lends another; everything else stays static in its unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -442,6 +443,22 @@ struct DevBuf {  // RAII device buffer for temporaries
     DevBuf &operator=(const DevBuf &) = delete;
     void reset() { if (p) (void)hipFree(p); p = nullptr; }
     hipError_t alloc(size_t n) { reset(); return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(T)); }
+};
+
+// (calls that read several tables: mc_seq_coverage, mc_kmer_presence) every distinct context's mutex, taken in the order of their addresses (two calls that name the same contexts in different
+// orders cannot wait for each other)
+struct TablesLock {
+    std::vector<mc_ctx *> distinct;
+    TablesLock(mc_ctx *const *tables, uint32_t n_tables) : distinct(tables, tables + n_tables)
+    {
+        std::sort(distinct.begin(), distinct.end(), std::less<mc_ctx *>());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        for (mc_ctx *c : distinct) c->mu.lock();
+    }
+    ~TablesLock()
+    {
+        for (auto it = distinct.rbegin(); it != distinct.rend(); ++it) (*it)->mu.unlock();
+    }
 };
 
 // a table of hash keys in minimizer bins (count_long.h): a bare key does not say which bin it is in (mcgpu.hip by_key_ready)

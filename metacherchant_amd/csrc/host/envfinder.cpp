@@ -1688,6 +1688,60 @@ std::string Environment::graph_txt() const
     return out;
 }
 
+Environment::Colour Environment::colour_of_mask(unsigned mask)
+{
+    switch (mask & 15u) {
+    case 0: return BLACK;
+    case 1: return RED;
+    case 2: return BLUE;
+    case 4: return GREEN;
+    case 8: return YELLOW;
+    default: return GREY;
+    }
+}
+
+const char *Environment::colour_name(Colour c)
+{
+    static const char *const names[] = {"RED", "GREEN", "BLUE", "GREY", "YELLOW", "BLACK"};
+    return c < 0 ? "" : names[c];
+}
+
+void Environment::set_colours(const std::function<Colour(kmer_t)> &of)
+{
+    colours_.clear();
+    colours_.reserve(subgraph_.size());
+    subgraph_.for_each([&](kmer_t seq, int, int) { colours_.push_back(of(seq)); });
+    coloured_ = true;
+}
+
+Environment::Outside Environment::outside_neighbours() const
+{
+    Outside o;
+    const int top = 2 * (k_ - 1);
+    uint32_t ordinal = 0;
+    subgraph_.for_each([&](kmer_t kmer, int, int) {
+        for (unsigned c = 0; c < 4; c++) {  // allNeighbors: left and right interleaved, A G C T
+            const kmer_t nb[2] = {((kmer_t)c << top) | (kmer >> 2), ((kmer << 2) & kmer_mask(k_)) | c};
+            for (const kmer_t x : nb)
+                if (subgraph_.find_entry(normalize128(x, k_)) < 0) { o.kmers.push_back(x); o.of.push_back(ordinal); }
+        }
+        ordinal++;
+    });
+    return o;
+}
+
+size_t Environment::extensions(const Outside &o, const uint8_t *in_graph)
+{
+    size_t n = 0;
+    for (size_t i = 0; i < o.of.size();) {  // (the entries of one k-mer lie together)
+        size_t j = i, hits = 0;
+        for (; j < o.of.size() && o.of[j] == o.of[i]; j++) hits += in_graph[j] != 0;
+        n += hits == 1;
+        i = j;
+    }
+    return n;
+}
+
 void Environment::merge_nodes(int first_plus, int second_minus)
 {
     const int first_minus = nodes_[first_plus].rc, second_plus = nodes_[second_minus].rc;
@@ -1718,8 +1772,9 @@ void Environment::create_picture()
         const bool g = std::binary_search(gene_kmers_.begin(), gene_kmers_.end(), seq) ||
                        std::binary_search(gene_kmers_.begin(), gene_kmers_.end(), rc);
         const int id = (int)nodes_.size();
-        nodes_.push_back(Node{unpack_kmer128(seq, k_), id, g, false, id + 1, {}});
-        nodes_.push_back(Node{unpack_kmer128(rc, k_), id + 1, g, false, id, {}});
+        const Colour col = coloured_ ? colours_[(size_t)id / 2] : NO_COLOUR;
+        nodes_.push_back(Node{unpack_kmer128(seq, k_), id, g, false, id + 1, {}, col});
+        nodes_.push_back(Node{unpack_kmer128(rc, k_), id + 1, g, false, id, {}, col});
         packed.push_back(seq);
         packed.push_back(rc);
     });
@@ -1753,7 +1808,8 @@ void Environment::create_picture()
         for (size_t i = 0; i < nodes_.size(); i++) {
             if (!nodes_[i].deleted && nodes_[i].neighbors.size() == 1) {
                 const int other = nodes_[i].neighbors[0];
-                if (nodes_[(size_t)other].neighbors.size() != 1 || nodes_[i].is_gene != nodes_[(size_t)other].is_gene)
+                if (nodes_[(size_t)other].neighbors.size() != 1 || nodes_[i].colour != nodes_[(size_t)other].colour ||
+                    nodes_[i].is_gene != nodes_[(size_t)other].is_gene)  // (uncoloured nodes all have NO_COLOUR)
                     continue;
                 merge_nodes((int)i, other);
                 acted = true;
@@ -1811,7 +1867,7 @@ std::string Environment::graph_gfa() const
         }
         coverage += (long long)last * (k_ - 1);
         out += "S\t" + node_id(n) + "\t" + s + "\tLN:i:" + std::to_string(s.size()) + "\tKC:i:" + std::to_string(coverage) +
-               (n.is_gene ? "\tCL:Z:GREEN" : "") + "\n";
+               (coloured_ ? std::string("\tCL:Z:") + colour_name(n.colour) : std::string(n.is_gene ? "\tCL:Z:GREEN" : "")) + "\n";
     }
     for (const Node &i : nodes_) {
         if (i.deleted) continue;

@@ -220,10 +220,26 @@ struct BfsPass {
 };
 
 // ---- src/algo/OneSequenceCalculator.java (after the BFS) + src/algo/SingleNode.java +
-// src/io/writers/GFAWriter.java + src/io/writers/TSVWriter.java
+// src/io/writers/GFAWriter.java + src/io/writers/TSVWriter.java; with set_colours, src/algo/SeqEnvCalculator.java (after its BFS)
 class Environment {
 public:
     Environment(int k, std::vector<std::string> gene_sequences);
+    // SingleNode.Color, in the enum's order; colour_of_mask: src/tools/RecipientVisualiser.java:157-169 with bit 0 = from_donor,
+    // 1 = from_before (the came_from_baseline files), 2 = from_both, 3 = itself
+    enum Colour : int8_t { NO_COLOUR = -1, RED, GREEN, BLUE, GREY, YELLOW, BLACK };
+    static Colour colour_of_mask(unsigned mask);
+    static const char *colour_name(Colour c);
+    // The recipient-visualiser's nodes (SeqEnvCalculator.java:165-206): of(k-mer) is asked for every entry of the subgraph in its
+    // iteration order; create_picture then merges only nodes of one colour (:214) and graph_gfa ends every S line with CL:Z:<colour>.
+    // Without this call nothing changes: environment-finder's files.
+    void set_colours(const std::function<Colour(kmer_t)> &of);
+    // extendEnvironment (SeqEnvCalculator.java:119-149) adds nothing -- its `cont` is the k-mer itself -- but logs how many k-mers of
+    // the subgraph have exactly one of their eight neighbours outside it and in the graph.  outside_neighbours: those neighbours that
+    // are not in the subgraph (oriented, allNeighbors order, one entry an occurrence) with the ordinal of their k-mer;
+    // extensions: the count, given which of them the graph holds.
+    struct Outside { std::vector<kmer_t> kmers; std::vector<uint32_t> of; };
+    Outside outside_neighbours() const;
+    static size_t extensions(const Outside &o, const uint8_t *in_graph);
     // :217-219 (+ runTrimPaths :241-262 when trim): distanceToKmer -> subgraph
     void add_pass(const BfsPass &p, bool trim);
     size_t size() const { return subgraph_.size(); }
@@ -244,6 +260,7 @@ private:
         bool is_gene, deleted = false;
         int rc;                      // index of the reverse-complement node
         std::vector<int> neighbors;  // successors of rc(this), in node-array order
+        Colour colour = NO_COLOUR;
     };
     void merge_nodes(int first_plus, int second_minus);
     std::string node_id(const Node &n) const;
@@ -252,6 +269,8 @@ private:
     std::vector<kmer_t> gene_kmers_;  // sorted: every k-window of the gene sequences, for isGeneNode
     JavaKmerMap subgraph_;
     bool d_treeified_ = false;
+    bool coloured_ = false;
+    std::vector<Colour> colours_;  // by the subgraph's iteration order (set_colours)
     std::vector<Node> nodes_;
 };
 

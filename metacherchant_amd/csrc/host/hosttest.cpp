@@ -5,11 +5,15 @@
 // dump format (text): k chunk_length trim n_genes / gene strings / n_passes / per pass: dir n /
 // n lines "kmer dist cov last".  Also: `mc_hosttest seeds <fasta>` and `mc_hosttest reads <file>`
 // print what the seed reader / read ingest deliver; `fmt` and `dtoa` print Java's number formats.
+// `mc_hosttest colour <dump> <out_dir> <name>`: one sequence of the recipient-visualiser.  dump: k / the sequence / n / n lines
+// "kmer dist cov mask" (its walk, in insertion order, with every k-mer's class mask) / m / m k-mers the graph holds beside them;
+// writes <out_dir>/<name>_seqs.fasta and <name>.gfa and prints the "Extending endings" line.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <functional>
 #include <iostream>
+#include <map>
 
 #include "envfinder.h"
 
@@ -81,8 +85,45 @@ int main(int argc, char **argv)
             for (const auto &l : r.log) printf("%s\n", l.c_str());
             return 0;
         }
+        if (argc == 5 && std::string(argv[1]) == "colour") {
+            std::ifstream f(argv[2]);
+            if (!f) throw Error("cannot open dump");
+            int k;
+            std::string sequence;
+            size_t n, m;
+            f >> k >> sequence >> n;
+            Environment env(k, {sequence});
+            BfsPass pass;
+            std::map<kmer_t, unsigned> mask_of;
+            for (size_t i = 0; i < n; i++) {
+                int d, c;
+                unsigned mask;
+                std::string kmer;
+                f >> kmer >> d >> c >> mask;
+                pass.kmers.push_back(pack_kmer128(kmer));
+                pass.dist.push_back(d); pass.cov.push_back((int16_t)c); pass.last.push_back(0);
+                mask_of[normalize128(pass.kmers.back(), k)] = mask;
+            }
+            env.add_pass(pass, false);
+            std::map<kmer_t, int> graph;
+            f >> m;
+            for (size_t i = 0; i < m; i++) {
+                std::string kmer;
+                f >> kmer;
+                graph[normalize128(pack_kmer128(kmer), k)] = 1;
+            }
+            const Environment::Outside o = env.outside_neighbours();
+            std::vector<uint8_t> in_graph(o.kmers.size());
+            for (size_t i = 0; i < o.kmers.size(); i++) in_graph[i] = graph.count(normalize128(o.kmers[i], k)) != 0;
+            printf("Extending endings by %zu kmers\n", Environment::extensions(o, in_graph.data()));
+            env.set_colours([&](kmer_t s) { return Environment::colour_of_mask(mask_of.at(s)); });
+            env.create_picture();
+            write_file(std::string(argv[3]) + "/" + argv[4] + "_seqs.fasta", env.seqs_fasta(0));
+            write_file(std::string(argv[3]) + "/" + argv[4] + ".gfa", env.graph_gfa());
+            return 0;
+        }
         if (argc != 4 || std::string(argv[1]) != "env") {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

@@ -80,6 +80,9 @@ struct Options {
     // --tool seq-cov (src/tools/SequenceCoverage.java:30-72)
     std::vector<std::string> from_before, from_donor, from_both, itself;
     std::string read_file;
+    // --tool recipient-visualiser (src/tools/RecipientVisualiser.java:42-92)
+    std::vector<std::string> after_files;
+    std::string input_dir, ext;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -117,6 +120,14 @@ const OptSpec SEQ_COV_SPECS[] = {
     {"read-file", "r", 0}, {"output-dir", "o", 0}, {"hash", nullptr, 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
+};
+
+// --tool recipient-visualiser: its parameters (RecipientVisualiser.java:42-92) and the launch options
+const OptSpec RECIPIENT_SPECS[] = {
+    {"k", "k", 0}, {"after-files", "after", 2}, {"seq", "seq", 0}, {"maxkmers", nullptr, 0}, {"maxradius", nullptr, 0}, {"hash", nullptr, 0},
+    {"output-dir", "o", 0}, {"input-dir", "i", 0}, {"ext", "ext", 0},
+    {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0},
 };
 
 struct SpecTable {
@@ -165,6 +176,7 @@ Options parse_args(int argc, char **argv)
     const SpecTable specs = tool == "reads-classifier"          ? SpecTable{std::begin(CLASSIFIER_SPECS), std::end(CLASSIFIER_SPECS)}
                             : tool == "triple-reads-classifier" ? SpecTable{std::begin(TRIPLE_SPECS), std::end(TRIPLE_SPECS)}
                             : tool == "seq-cov"                 ? SpecTable{std::begin(SEQ_COV_SPECS), std::end(SEQ_COV_SPECS)}
+                            : tool == "recipient-visualiser"    ? SpecTable{std::begin(RECIPIENT_SPECS), std::end(RECIPIENT_SPECS)}
                                                                 : SpecTable{std::begin(SPECS), std::end(SPECS)};
     std::map<std::string, std::vector<std::string>> got;
     for (int i = 1; i < argc; i++) {
@@ -213,6 +225,9 @@ Options parse_args(int argc, char **argv)
     multi("from-donor", o.from_donor);
     multi("from-both", o.from_both);
     multi("itself", o.itself);
+    multi("after-files", o.after_files);
+    if (auto v = val("input-dir")) o.input_dir = *v;
+    if (auto v = val("ext")) o.ext = *v;
     if (auto v = val("read-file")) o.read_file = *v;
     if (auto v = val("correction")) o.correction = java_bool(*v);
     if (auto v = val("interval95")) o.interval95 = java_bool(*v);
@@ -316,6 +331,17 @@ void usage()
     puts("  -r, --read-file <arg>          file with sequences to classify: reads, genes or contigs (MANDATORY)");
     puts("  -o, --output-dir <arg>         directory of seq_cov.csv (default <work-dir>/sequence_coverage)");
     puts("      --hash <arg>               hash function to use for k > 31: poly or fnv1a (default poly)");
+    puts("Input parameters of --tool recipient-visualiser (one coloured GFA a sequence: its environment in the post-FMT graph, every k-mer");
+    puts("coloured by the class files of the reads-classifier script that hold it; writes <output-dir>/after/comp_<i>{.gfa,_seqs.fasta}):");
+    puts("  -k, --k <arg>                  k-mer size (MANDATORY)");
+    puts("  -after, --after-files <args>   post-FMT recipient metagenomic reads (MANDATORY)");
+    puts("  -seq, --seq <arg>              FASTA file with sequences (MANDATORY)");
+    puts("      --maxkmers <arg>           maximum number of k-mers in created subgraph");
+    puts("      --maxradius <arg>          maximum distance in k-mers from starting gene (default 1000)");
+    puts("      --hash <arg>               hash function to use for k > 31: poly or fnv1a (default poly)");
+    puts("  -o, --output-dir <arg>         output directory (default <work-dir>/graph)");
+    puts("  -i, --input-dir <arg>          directory of came_from_{donor,baseline,both}_{1,2,s}.<ext> and came_itself_{1,2,s}.<ext> (MANDATORY)");
+    puts("  -ext, --ext <arg>              extension of those files (MANDATORY)");
     puts("Launch options: -w/--work-dir <dir> (default workDir), -c/--continue, --force, -v/--verbose, -h/--help,");
     puts("                -t/--tool <name>, -p/--available-processors <n> and -m/--memory <arg> (accepted, unused),");
     puts("                --device <n> (GPU ordinal), --devices <a,b,...|a-b> (several GPUs as one table: reads dealt to them,");
@@ -1006,6 +1032,173 @@ int run_seq_cov(const Options &o)
     return 0;
 }
 
+// --tool recipient-visualiser (src/tools/RecipientVisualiser.java:185-223, src/algo/SeqEnvCalculator.java): the environment of every
+// sequence of --seq in the graph of the post-FMT reads (mc_bfs_batch: all eight neighbours, count > 0), every k-mer coloured by which
+// of the four class tables hold it (mc_kmer_presence: one call a batch of sequences), one coloured GFA and one FASTA a sequence.
+// The reference runs the sequences on a thread pool; each writes its own files, and the log lines here come in sequence order.
+int run_recipient_visualiser(const Options &o)
+{
+    if (o.k < 0) throw Error("Parameter 'k' is mandatory");
+    if (o.after_files.empty()) throw Error("Parameter 'after-files' is mandatory");
+    if (o.seq.empty()) throw Error("Parameter 'seq' is mandatory");
+    if (o.input_dir.empty()) throw Error("Parameter 'input-dir' is mandatory");
+    if (o.ext.empty()) throw Error("Parameter 'ext' is mandatory");
+    if (o.k < 1 || o.k > 63)
+        throw Error("k = " + std::to_string(o.k) + " is not supported: this build handles k <= 31 (packed keys) and 32 <= k <= 63 (hash keys)");
+    if (!o.devices.empty()) throw Error("--devices is for --tool environment-finder: recipient-visualiser keeps its five tables on one device (--device)");
+    // (the class files, RecipientVisualiser.java:194-205: donor, baseline, both, itself are bits 0..3 of a k-mer's mask)
+    const char *const classes[4] = {"came_from_donor", "came_from_baseline", "came_from_both", "came_itself"};
+    std::vector<std::string> class_files[4];
+    for (int t = 0; t < 4; t++)
+        for (const char *part : {"_1.", "_2.", "_s."}) {
+            class_files[t].push_back(o.input_dir + "/" + classes[t] + part + o.ext);
+            FILE *f = fopen(class_files[t].back().c_str(), "rb");
+            if (!f) throw Error("Could not read class file " + class_files[t].back());
+            fclose(f);
+        }
+    if (!open_work_dir(o, "k=" + std::to_string(o.k) + "\nseq=" + o.seq + "\ninput-dir=" + o.input_dir + "\next=" + o.ext + "\n")) return 0;
+    const std::string out_dir = (o.output_dir.empty() ? o.work_dir + "/graph" : o.output_dir) + "/after";
+    const int64_t maxradius = o.maxradius < 0 ? 1000 : o.maxradius;  // (the parameter's default; --maxkmers has none)
+
+    info("Loading after reads ...");
+    int mode = MC_KEY_PACKED;
+    if (o.k > 31) {  // loadAfterGraphs :108-123
+        info("Reading hashes of k-mers instead");
+        std::string h = o.hash;
+        for (char &c : h) c = (char)tolower((unsigned char)c);
+        if (h == "fnv1a") { info("Using FNV1a hash function"); mode = MC_KEY_FNV1A; }
+        else { info("Using default polynomial hash function"); mode = MC_KEY_POLY; }
+    }
+    mc_config cfg{};
+    cfg.k = o.k;
+    cfg.key_mode = mode;
+    cfg.device = o.device;
+    cfg.capacity_hint = o.capacity_hint;
+    Engine G, E[4];  // the graph, then the class tables: all five stay on the device
+    G.open(cfg, {});
+    G.set_coverage_hint(1);
+    load_reads(o.after_files, G);
+    MC_CHECK(G.c, mc_trim(G.c));
+    mc_ctx *tables[4];
+    cfg.capacity_hint = 0;
+    for (int t = 0; t < 4; t++) {
+        E[t].open(cfg, {});
+        tables[t] = E[t].c;
+        MC_CHECK(tables[t], mc_set_read_pointers(tables[t], 0));  // (no walk on these: no read store)
+        load_reads(class_files[t], E[t]);
+        MC_CHECK(tables[t], mc_trim(tables[t]));
+    }
+
+    // ReadersUtils.loadDnaQs: every record whole, N as A
+    DnaQBatch seqs;
+    seqs.clear();
+    try {
+        DnaQReader reader(o.seq);
+        while (reader.read(seqs, 1u << 16)) {}
+    } catch (const Error &) {
+        throw Error("Could not load sequences from " + o.after_files[0]);  // (the reference names this file, :127)
+    }
+    const size_t n_seqs = seqs.n_reads();
+
+    info("Creating after images ...");
+    // Jobs a call: mc_bfs_batch gives every job device arrays for max(--maxkmers, its windows) + 512 vertices -- 2^20 when --maxkmers
+    // is not given -- at some 64 bytes a vertex (k-mer, distance, coverage, flags, the visited index), and its result comes back in
+    // host arrays of 23 bytes a vertex.  A call takes as many sequences as fit a quarter of the device memory that is free now that
+    // the five tables are loaded: at most 256 (the environment-finder's chunk; beyond it a launch gains nothing), at least one.
+    size_t free_b = 0, total_b = 0;
+    hip_check(hipSetDevice(o.device), "hipSetDevice");
+    hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+    uint64_t longest = 0;
+    for (size_t s = 0; s < n_seqs; s++) longest = std::max<uint64_t>(longest, seqs.offsets[s + 1] - seqs.offsets[s]);
+    const uint64_t per_job = 64 * ((o.maxkmers >= 0 ? std::max<uint64_t>((uint64_t)o.maxkmers, longest) : std::max<uint64_t>(1ull << 20, longest)) + 512);
+    const size_t chunk = (size_t)std::min<uint64_t>(256, std::max<uint64_t>(1, free_b / 4 / per_job));
+    const kmer_t kmask = o.k >= 64 ? ~(kmer_t)0 : (((kmer_t)1 << (2 * o.k)) - 1);
+
+    for (size_t s0 = 0; s0 < n_seqs; s0 += chunk) {
+        const size_t s1 = std::min(n_seqs, s0 + chunk);
+        std::vector<std::string> text(s1 - s0);
+        std::vector<std::vector<uint64_t>> shi(s1 - s0), slo(s1 - s0);
+        std::vector<mc_bfs_job> jobs;
+        for (size_t s = s0; s < s1; s++) {
+            std::string &t = text[s - s0];
+            for (uint64_t i = seqs.offsets[s]; i < seqs.offsets[s + 1]; i++) t.push_back("AGCT"[seqs.codes[i] & 3]);  // DnaQ.toString()
+            kmer_t v = 0;
+            for (size_t i = 0; i < t.size(); i++) {
+                v = ((v << 2) | (seqs.codes[seqs.offsets[s] + i] & 3u)) & kmask;
+                if (i + 1 >= (size_t)o.k) { shi[s - s0].push_back((uint64_t)(v >> 64)); slo[s - s0].push_back((uint64_t)v); }
+            }
+            jobs.push_back(mc_bfs_job{shi[s - s0].data(), slo[s - s0].data(), shi[s - s0].size(), 0});
+        }
+        std::vector<mc_bfs_result> res(jobs.size());
+        struct ResGuard {  // (an exception below must not leak the library's result arrays)
+            std::vector<mc_bfs_result> &r;
+            ~ResGuard() { for (auto &x : r) mc_bfs_result_free(&x); }
+        } guard{res};
+        G.bfs_batch(jobs.data(), (uint32_t)jobs.size(), 1, o.maxkmers, maxradius, res.data());
+
+        // the colours of the whole batch: one call over the concatenated results
+        std::vector<uint64_t> qhi, qlo;
+        std::vector<size_t> at(res.size() + 1, 0);
+        for (size_t j = 0; j < res.size(); j++) {
+            qhi.insert(qhi.end(), res[j].hi, res[j].hi + res[j].n);
+            qlo.insert(qlo.end(), res[j].lo, res[j].lo + res[j].n);
+            at[j + 1] = qlo.size();
+        }
+        std::vector<uint8_t> mask(qlo.size());
+        if (!qlo.empty()) MC_CHECK(tables[0], mc_kmer_presence(tables, 4, qhi.data(), qlo.data(), qlo.size(), mask.data()));
+
+        // the subgraphs, and what extendEnvironment asks the graph: again one call for the batch
+        std::vector<std::unique_ptr<Environment>> envs(res.size());
+        std::vector<Environment::Outside> outside(res.size());
+        std::vector<std::map<kmer_t, uint8_t>> mask_of(res.size());
+        std::vector<size_t> oat(res.size() + 1, 0);
+        qhi.clear();
+        qlo.clear();
+        for (size_t j = 0; j < res.size(); j++) {
+            const mc_bfs_result &r = res[j];
+            if (r.n) {
+                envs[j].reset(new Environment(o.k, {text[j]}));
+                BfsPass p;
+                p.dir = 0;
+                p.kmers.reserve(r.n);
+                for (uint64_t i = 0; i < r.n; i++) {
+                    p.kmers.push_back(((kmer_t)r.hi[i] << 64) | r.lo[i]);
+                    mask_of[j][normalize128(p.kmers.back(), o.k)] = mask[at[j] + i];
+                }
+                p.dist.assign(r.dist, r.dist + r.n);
+                p.cov.assign(r.cov, r.cov + r.n);
+                p.last.assign(r.n, 0);
+                envs[j]->add_pass(p, false);
+                outside[j] = envs[j]->outside_neighbours();
+                for (const kmer_t x : outside[j].kmers) { qhi.push_back((uint64_t)(x >> 64)); qlo.push_back((uint64_t)x); }
+            }
+            oat[j + 1] = qlo.size();
+        }
+        std::vector<uint8_t> in_graph(qlo.size());
+        mc_ctx *graph[1] = {G.c};
+        if (!qlo.empty()) MC_CHECK(G.c, mc_kmer_presence(graph, 1, qhi.data(), qlo.data(), qlo.size(), in_graph.data()));
+
+        for (size_t j = 0; j < res.size(); j++) {
+            info("Finding environment for sequence " + shorten_label(text[j], o.k));
+            if (!envs[j]) {
+                info("Could not find any k-mers of the target gene in the input, halting.");
+                continue;
+            }
+            Environment &env = *envs[j];
+            info("Extending endings by " + std::to_string(Environment::extensions(outside[j], in_graph.data() + oat[j])) + " kmers");
+            env.set_colours([&](kmer_t kmer) { return Environment::colour_of_mask(mask_of[j].at(kmer)); });
+            env.create_picture();
+            const std::string name = out_dir + "/comp_" + std::to_string(s0 + j);
+            write_file(name + "_seqs.fasta", env.seqs_fasta(0));  // (no chunk-length filter here: SeqEnvCalculator.java:258)
+            write_file(name + ".gfa", env.graph_gfa());
+            envs[j].reset();
+        }
+    }
+    info("Finished processing all sequences!");
+    write_file(o.work_dir + "/SUCCESS", "");
+    return 0;
+}
+
 int run(const Options &o)
 {
     if (o.tool == "kmer-counter") return run_kmer_counter(o);
@@ -1013,9 +1206,10 @@ int run(const Options &o)
     if (o.tool == "reads-classifier") return run_reads_classifier(o);
     if (o.tool == "triple-reads-classifier") return run_triple_reads_classifier(o);
     if (o.tool == "seq-cov") return run_seq_cov(o);
+    if (o.tool == "recipient-visualiser") return run_recipient_visualiser(o);
     if (o.tool != "environment-finder")
         throw Error("Tool '" + o.tool + "' is not part of this build: only environment-finder, kmer-counter, environment-finder-multi, "
-                    "reads-classifier, triple-reads-classifier and seq-cov are");
+                    "reads-classifier, triple-reads-classifier, recipient-visualiser and seq-cov are");
     if (o.k < 0) throw Error("Parameter 'k' is mandatory");
     if (o.seq.empty()) throw Error("Parameter 'seq' is mandatory");
     if (o.output.empty()) throw Error("Parameter 'output' is mandatory");

@@ -258,22 +258,6 @@ int check_tables(mc_ctx *const *tables, uint32_t n_tables)
     return MC_OK;
 }
 
-// every distinct context's mutex, taken in the order of their addresses (two calls that name the same contexts in different
-// orders cannot wait for each other)
-struct TablesLock {
-    std::vector<mc_ctx *> distinct;
-    TablesLock(mc_ctx *const *tables, uint32_t n_tables) : distinct(tables, tables + n_tables)
-    {
-        std::sort(distinct.begin(), distinct.end(), std::less<mc_ctx *>());
-        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-        for (mc_ctx *c : distinct) c->mu.lock();
-    }
-    ~TablesLock()
-    {
-        for (auto it = distinct.rbegin(); it != distinct.rend(); ++it) (*it)->mu.unlock();
-    }
-};
-
 }  // namespace
 
 int mc_seq_coverage_dev(mc_ctx *const *tables, uint32_t n_tables, const uint64_t *d_words, const uint64_t *d_seq_offsets, uint64_t n_seqs,

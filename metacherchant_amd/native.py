@@ -70,6 +70,7 @@ CLASSIFY_CORRECTION = 1  # mc_classify_reads flags: findReadWithCorrection
 LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fingerprint, so distinct reads share one
 CLASS_NOT_FOUND, CLASS_HALF_FOUND, CLASS_FOUND = 0, 1, 2  # mc_triple_classes
 SEQ_COV_MAX_TABLES = 4  # mc_seq_coverage
+PRESENCE_MAX_TABLES = 4  # mc_kmer_presence
 
 
 # every symbol include/mcgpu.h declares; tests check that the library exports all of them
@@ -83,6 +84,7 @@ EXPORTS = [
     "mc_read_store_seek", "mc_read_store_tell", "mc_read_store_import_dev", "mc_get_stats", "mc_reset_stats", "mc_trim", "mc_synth_reads_dev", "mc_synth_genome",
     "mc_shard_export", "mc_shard_attach", "mc_shard_detach", "mc_classify_reads", "mc_classify_reads_dev",
     "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev", "mc_seq_coverage", "mc_seq_coverage_dev",
+    "mc_kmer_presence", "mc_kmer_presence_dev",
 ]
 
 _LIB = None
@@ -172,6 +174,9 @@ def load():
     if hasattr(L, "mc_seq_coverage"):
         L.mc_seq_coverage.argtypes = [C.POINTER(vp), C.c_uint32, u64p, u64p, u64, vp]
         L.mc_seq_coverage_dev.argtypes = [C.POINTER(vp), C.c_uint32, vp, vp, u64, vp]
+    if hasattr(L, "mc_kmer_presence"):
+        L.mc_kmer_presence.argtypes = [C.POINTER(vp), C.c_uint32, u64p, u64p, u64, C.POINTER(C.c_uint8)]
+        L.mc_kmer_presence_dev.argtypes = [C.POINTER(vp), C.c_uint32, vp, vp, u64, vp]
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -591,6 +596,31 @@ def seq_coverage_dev(contexts, d_words, d_offsets, n_seqs, d_out):
     """mc_seq_coverage_dev: d_out holds n_seqs * n_tables * 2 uint64 (mc_seq_cov records); the call zeroes it first"""
     contexts, handles = _table_handles(contexts)
     rc = load().mc_seq_coverage_dev(handles, len(contexts), _dptr(d_words), _dptr(d_offsets), int(n_seqs), _dptr(d_out))
+    if rc != 0:
+        raise McError(rc, (load().mc_last_error(contexts[0]._h) or b"").decode() if contexts else "")
+
+
+def kmer_presence(contexts, hi, lo):
+    """mc_kmer_presence: which of the contexts' tables (1 .. PRESENCE_MAX_TABLES contexts of one k, key mode and device, finalized; the
+    same one may come several times) contain each oriented packed k-mer (hi << 64 | lo, as bfs results list them; hi may be None when
+    k <= 32).  Returns a uint8 array: bit t of entry i is set when contexts[t] holds k-mer i."""
+    contexts, handles = _table_handles(contexts)
+    lo = np.ascontiguousarray(lo, dtype=np.uint64)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64) if hi is not None else None
+    if hi is not None and len(hi) != len(lo):
+        raise ValueError("hi and lo need one entry a k-mer")
+    out = np.zeros(len(lo), dtype=np.uint8)
+    rc = load().mc_kmer_presence(handles, len(contexts), _p(hi, C.c_uint64) if hi is not None else None, _p(lo, C.c_uint64), len(lo),
+                                 _p(out, C.c_uint8))
+    if rc != 0:
+        raise McError(rc, (load().mc_last_error(contexts[0]._h) or b"").decode() if contexts else "")
+    return out
+
+
+def kmer_presence_dev(contexts, d_hi, d_lo, n, d_mask):
+    """mc_kmer_presence_dev: d_hi (may be None when k <= 32) and d_lo hold n uint64 each, d_mask n bytes"""
+    contexts, handles = _table_handles(contexts)
+    rc = load().mc_kmer_presence_dev(handles, len(contexts), _dptr(d_hi), _dptr(d_lo), int(n), _dptr(d_mask))
     if rc != 0:
         raise McError(rc, (load().mc_last_error(contexts[0]._h) or b"").decode() if contexts else "")
 

@@ -14,11 +14,14 @@
 # runs `--tool seq-cov` both ways instead: four bins of n_reads / 4 reads each, the sequences of --read-file a few reads, one shorter
 # than k - 1, one of k - 1 bases and a contig; seq_cov.csv is compared byte for byte (the doubles are Double.toString's: a JDK
 # before 19 may print a digit more for rare values).
+#   MC_REFERENCE_JAR=... scripts/compare_with_java.sh recipient-visualiser [n_reads] [k]
+# runs `--tool recipient-visualiser` both ways: n_reads post-FMT reads, the twelve class files cut from them by where a read lies, a
+# dozen genes; every comp_<i>.gfa and comp_<i>_seqs.fasta under <output-dir>/after is compared byte for byte, and so is the set of files.
 # Exit status 0 = every file identical.  The Java log's timestamps around "Loading file" ... "Hashtable size" ...
 # "Finished processing all sequences!" are printed as the reference's phase times on this box's cores.
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
-if [ "${1:-}" != "seq-cov" ]; then
+if [ "${1:-}" != "seq-cov" ] && [ "${1:-}" != "recipient-visualiser" ]; then
 N=${1:-200000}; K=${2:-31}; shift $(( $# > 2 ? 2 : $# )) || true
 EXTRA=("$@")
 [ ${#EXTRA[@]} -eq 0 ] && EXTRA=(--coverage 5 --maxkmers 100000 --bothdirs False)
@@ -54,6 +57,45 @@ PY
     "$CLI" --tool seq-cov -k "$K" "${BINS[@]}" -o "$W/hip_out" --work-dir "$W/hip_wd" --force 2> "$W/hip.log"
     if cmp -s "$W/java_out/seq_cov.csv" "$W/hip_out/seq_cov.csv"; then echo "identical  seq_cov.csv"; exit 0; fi
     echo "DIFFERENT  seq_cov.csv"; exit 1
+fi
+if [ "${1:-}" = "recipient-visualiser" ]; then
+    N=${2:-20000}; K=${3:-31}
+    python3 - "$ROOT" "$W" "$N" "$K" <<'PY'
+import os, sys
+root, w, n, k = sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
+sys.path.insert(0, root)
+from oracle import pyoracle as po
+L = 150
+glen = max(20000, n * L // 10)
+genome = po.synth_genome(20240531, glen)
+reads = po.synth_reads(genome, 1, glen, 42, 0, n, L, 100)
+os.makedirs(w + "/classes")
+masks = (1, 2, 4, 8, 3, 12, 0, 15)  # by the eighth of the read set a read is in: the classes that get it
+names = ("came_from_donor", "came_from_baseline", "came_from_both", "came_itself")
+out = {(c, m): open("%s/classes/%s_%s.fasta" % (w, c, m), "w") for c in names for m in "12s"}
+with open(w + "/after.fasta", "w") as f:
+    for r in range(n):
+        s = po.decode(reads[r * L:(r + 1) * L])
+        f.write(">r%d\n%s\n" % (r, s))
+        for t, c in enumerate(names):
+            if masks[r * 8 // n] >> t & 1:
+                out[(c, "12s"[r % 3])].write(">r%d\n%s\n" % (r, s))
+for f in out.values():
+    f.close()
+with open(w + "/genes.fasta", "w") as f:
+    for g in range(12):
+        f.write(">g%d\n%s\n" % (g, po.decode(genome[g * glen // 12:g * glen // 12 + 300])))
+    f.write(">absent\n%s\n" % ("ACGT" * 20))
+PY
+    ARGS=(-k "$K" -after "$W/after.fasta" -seq "$W/genes.fasta" -i "$W/classes" -ext fasta --maxkmers 5000 --maxradius 200)
+    java -jar "$MC_REFERENCE_JAR" --tool recipient-visualiser "${ARGS[@]}" -o "$W/java_out" --work-dir "$W/java_wd" --force > "$W/java.stdout" 2> "$W/java.log"
+    "$CLI" --tool recipient-visualiser "${ARGS[@]}" -o "$W/hip_out" --work-dir "$W/hip_wd" --force 2> "$W/hip.log"
+    status=0
+    if [ "$(cd "$W/java_out" && find . -type f | sort)" != "$(cd "$W/hip_out" && find . -type f | sort)" ]; then echo "DIFFERENT  the sets of files"; status=1; fi
+    for f in $(cd "$W/java_out" && find . -type f | sort); do
+        if cmp -s "$W/java_out/$f" "$W/hip_out/$f"; then echo "identical  $f"; else echo "DIFFERENT  $f"; status=1; fi
+    done
+    exit $status
 fi
 python3 - "$ROOT" "$W" "$N" <<'PY'
 import sys
