@@ -159,40 +159,16 @@ int mc_triple_classes(mc_ctx *c, const mc_read_cov *cov1, const mc_read_cov *cov
     if (n_pairs && (!cov1 || !cov2 || !offsets1 || !offsets2 || !class1 || !class2 || (pass2 && !(prev1 && prev2 && last1 && last2))))
         return fail(c, MC_EINVAL, "mc_triple_classes: null pointer");
     if (n_pairs == 0) return mc_triple_classes_dev(c, nullptr, nullptr, nullptr, nullptr, 0, half_pct, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    DevBuf<mc_read_cov> dc1, dc2;
-    DevBuf<uint64_t> do1, do2;
-    DevBuf<uint8_t> dp1, dp2, dk1, dk2;
-    DevBuf<uint32_t> dl1, dl2;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        HIPCHK(c, hipSetDevice(c->cfg.device));
-        HIPCHK(c, dc1.alloc(n_pairs));
-        HIPCHK(c, dc2.alloc(n_pairs));
-        HIPCHK(c, do1.alloc(n_pairs + 1));
-        HIPCHK(c, do2.alloc(n_pairs + 1));
-        HIPCHK(c, dk1.alloc(n_pairs));
-        HIPCHK(c, dk2.alloc(n_pairs));
-        HIPCHK(c, hipMemcpy(dc1.p, cov1, n_pairs * sizeof(mc_read_cov), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(dc2.p, cov2, n_pairs * sizeof(mc_read_cov), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(do1.p, offsets1, (n_pairs + 1) * 8, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(do2.p, offsets2, (n_pairs + 1) * 8, hipMemcpyHostToDevice));
-        if (pass2) {
-            HIPCHK(c, dp1.alloc(n_pairs));
-            HIPCHK(c, dp2.alloc(n_pairs));
-            HIPCHK(c, dl1.alloc(n_pairs));
-            HIPCHK(c, dl2.alloc(n_pairs));
-            HIPCHK(c, hipMemcpy(dp1.p, prev1, n_pairs, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy(dp2.p, prev2, n_pairs, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy(dl1.p, last1, n_pairs * 4, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy(dl2.p, last2, n_pairs * 4, hipMemcpyHostToDevice));
-        }
-    }
-    int rc = mc_triple_classes_dev(c, dc1.p, dc2.p, do1.p, do2.p, n_pairs, half_pct, dp1.p, dp2.p, dl1.p, dl2.p, dk1.p, dk2.p);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(c, hipMemcpy(class1, dk1.p, n_pairs, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(class2, dk2.p, n_pairs, hipMemcpyDeviceToHost));
-    return MC_OK;
+    HostStage st(c);
+    const mc_read_cov *dc1 = st.in(cov1, n_pairs), *dc2 = st.in(cov2, n_pairs);
+    const uint64_t *do1 = st.in(offsets1, n_pairs + 1), *do2 = st.in(offsets2, n_pairs + 1);
+    const uint8_t *dp1 = st.in(prev1, n_pairs), *dp2 = st.in(prev2, n_pairs);  // (pass 2: all four, checked above; else none)
+    const uint32_t *dl1 = st.in(last1, n_pairs), *dl2 = st.in(last2, n_pairs);
+    uint8_t *dk1 = st.out<uint8_t>(n_pairs), *dk2 = st.out<uint8_t>(n_pairs);
+    if (int rc = st.staged()) return rc;
+    if (int rc = mc_triple_classes_dev(c, dc1, dc2, do1, do2, n_pairs, half_pct, dp1, dp2, dl1, dl2, dk1, dk2)) return rc;
+    if (int rc = st.back(class1, dk1, n_pairs)) return rc;
+    return st.back(class2, dk2, n_pairs);
 }
 
 int mc_classify_reads_dev(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_read_offsets, uint64_t n_reads, const int32_t *d_bad_pos,
@@ -212,12 +188,9 @@ int mc_classify_reads_dev(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_
     const int corr = (flags & MC_CLASSIFY_CORRECTION) ? 1 : 0;
     const dim3 grid(grid_for(n_reads * 64, CL_THREADS, 1 << 18)), block(CL_THREADS);
     const int k = c->cfg.k;
-    if (c->cfg.key_mode == MC_KEY_PACKED)
-        hipLaunchKernelGGL(k_classify<KEY_PACKED>, grid, block, 0, c->stream, d_words, d_read_offsets, n_reads, d_bad_pos, k, c->view(), thr, z, corr, d_out);
-    else if (c->cfg.key_mode == MC_KEY_POLY)
-        hipLaunchKernelGGL(k_classify<KEY_POLY>, grid, block, 0, c->stream, d_words, d_read_offsets, n_reads, d_bad_pos, k, c->view(), thr, z, corr, d_out);
-    else
-        hipLaunchKernelGGL(k_classify<KEY_FNV1A>, grid, block, 0, c->stream, d_words, d_read_offsets, n_reads, d_bad_pos, k, c->view(), thr, z, corr, d_out);
+    for_key_mode(c->cfg.key_mode, [&](auto mode) {
+        hipLaunchKernelGGL(k_classify<mode()>, grid, block, 0, c->stream, d_words, d_read_offsets, n_reads, d_bad_pos, k, c->view(), thr, z, corr, d_out);
+    });
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MC_OK;
@@ -229,26 +202,11 @@ int mc_classify_reads(mc_ctx *c, const uint64_t *words, const uint64_t *read_off
     if (!c) return MC_EINVAL;
     if (n_reads && (!words || !read_offsets || !out)) return fail(c, MC_EINVAL, "mc_classify_reads: null pointer");
     if (n_reads == 0) return mc_classify_reads_dev(c, nullptr, nullptr, 0, nullptr, found_pct, z, flags, nullptr);
-    const uint64_t n_words = (read_offsets[n_reads] + 31) / 32 + 1;
-    DevBuf<uint64_t> dw, doff;
-    DevBuf<int32_t> dbad;
-    DevBuf<mc_read_cov> dout;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        HIPCHK(c, hipSetDevice(c->cfg.device));
-        HIPCHK(c, dw.alloc(n_words));
-        HIPCHK(c, doff.alloc(n_reads + 1));
-        HIPCHK(c, dout.alloc(n_reads));
-        HIPCHK(c, hipMemcpy(dw.p, words, n_words * 8, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(doff.p, read_offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice));
-        if (bad_pos) {
-            HIPCHK(c, dbad.alloc(n_reads));
-            HIPCHK(c, hipMemcpy(dbad.p, bad_pos, n_reads * 4, hipMemcpyHostToDevice));
-        }
-    }
-    int rc = mc_classify_reads_dev(c, dw.p, doff.p, n_reads, dbad.p, found_pct, z, flags, dout.p);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(c, hipMemcpy(out, dout.p, n_reads * sizeof(mc_read_cov), hipMemcpyDeviceToHost));
-    return MC_OK;
+    HostStage st(c);
+    const uint64_t *dw = st.in(words, packed_words(read_offsets, n_reads)), *doff = st.in(read_offsets, n_reads + 1);
+    const int32_t *dbad = st.in(bad_pos, n_reads);
+    mc_read_cov *dout = st.out<mc_read_cov>(n_reads);
+    if (int rc = st.staged()) return rc;
+    if (int rc = mc_classify_reads_dev(c, dw, doff, n_reads, dbad, found_pct, z, flags, dout)) return rc;
+    return st.back(out, dout, n_reads);
 }

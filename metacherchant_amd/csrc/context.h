@@ -10,7 +10,9 @@
 //   last_copy.hip   mc_reads_last_copy*: the last read with the same bases, for the triple-reads-classifier (hipCUB's radix sort)
 //   seq_cov.hip     mc_seq_coverage*: depth and breadth of sequences of any length in up to four tables at once, cut by positions
 //   presence.hip    mc_kmer_presence*: which of up to four tables hold each of a list of k-mers, one launch
-// A function below the "across units" line is what one unit lends another; everything else stays static in its unit.
+// multi_table.h is what seq_cov.hip and presence.hip share: one key's home slots in several tables, the probing behind them, and the
+// host's checks of a list of contexts.  A function below the "across units" line is what one unit lends another; everything else
+// stays static in its unit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +23,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mcgpu.h"
@@ -444,6 +447,78 @@ struct DevBuf {  // RAII device buffer for temporaries
     void reset() { if (p) (void)hipFree(p); p = nullptr; }
     hipError_t alloc(size_t n) { reset(); return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(T)); }
 };
+
+// The host form of a call: inputs go up into device buffers of its own and results come back, under the context's lock; in between
+// (staged) the lock is free, for the device form takes it itself.  The first failure is kept, and everything after it is left out.
+struct HostStage {
+    mc_ctx *c;
+    std::unique_lock<std::mutex> lock;
+    std::vector<void *> bufs;
+    int rc;
+    explicit HostStage(mc_ctx *ctx) : c(ctx), lock(ctx->mu), rc(set_device()) {}
+    HostStage(const HostStage &) = delete;
+    HostStage &operator=(const HostStage &) = delete;
+    ~HostStage()
+    {
+        if (lock.owns_lock()) lock.unlock();
+        for (void *p : bufs) (void)hipFree(p);
+    }
+    template <typename T>
+    T *out(uint64_t n)  // a device buffer of n elements
+    {
+        void *p = nullptr;
+        if (!rc) rc = alloc(&p, std::max<uint64_t>(n, 1) * sizeof(T));
+        return static_cast<T *>(p);
+    }
+    template <typename T>
+    const T *in(const T *host, uint64_t n)  // ... holding the host's n elements; NULL for an optional input that is not given
+    {
+        T *p = host ? out<T>(n) : nullptr;
+        if (p) rc = copy(p, host, n * sizeof(T), hipMemcpyHostToDevice);
+        return p;
+    }
+    int staged()
+    {
+        lock.unlock();
+        return rc;
+    }
+    template <typename T>
+    int back(T *host, const T *dev, uint64_t n)  // after the device form: the result
+    {
+        if (!lock.owns_lock()) lock.lock();
+        return copy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost);
+    }
+
+private:
+    int set_device()
+    {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        return MC_OK;
+    }
+    int alloc(void **p, size_t bytes)
+    {
+        HIPCHK(c, hipMalloc(p, bytes));
+        bufs.push_back(*p);
+        return MC_OK;
+    }
+    int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+    {
+        HIPCHK(c, hipMemcpy(dst, src, bytes, kind));
+        return MC_OK;
+    }
+};
+
+// 64-bit words of n packed reads (32 bases a word), the pad word behind them included
+inline uint64_t packed_words(const uint64_t *offsets, uint64_t n) { return (offsets[n] + 31) / 32 + 1; }
+
+// f(the key mode as a constant: std::integral_constant<int, KEY_...>), for a kernel that is a template over it
+template <typename F>
+void for_key_mode(int key_mode, F &&f)
+{
+    if (key_mode == MC_KEY_PACKED) f(std::integral_constant<int, KEY_PACKED>());
+    else if (key_mode == MC_KEY_POLY) f(std::integral_constant<int, KEY_POLY>());
+    else f(std::integral_constant<int, KEY_FNV1A>());
+}
 
 // (calls that read several tables: mc_seq_coverage, mc_kmer_presence) every distinct context's mutex, taken in the order of their addresses (two calls that name the same contexts in different
 // orders cannot wait for each other)

@@ -172,21 +172,10 @@ int mc_reads_last_copy(mc_ctx *c, const uint64_t *words, const uint64_t *read_of
     if (n_reads >= (1ull << 32)) return fail(c, MC_EINVAL, "mc_reads_last_copy: %llu reads (at most 2^32 - 1)", (unsigned long long)n_reads);
     if (n_reads && (!words || !read_offsets || !last)) return fail(c, MC_EINVAL, "mc_reads_last_copy: null pointer");
     if (n_reads == 0) return MC_OK;
-    const uint64_t n_words = (read_offsets[n_reads] + 31) / 32 + 1;
-    DevBuf<uint64_t> dw, doff;
-    DevBuf<uint32_t> dlast;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        HIPCHK(c, hipSetDevice(c->cfg.device));
-        HIPCHK(c, dw.alloc(n_words));
-        HIPCHK(c, doff.alloc(n_reads + 1));
-        HIPCHK(c, dlast.alloc(n_reads));
-        HIPCHK(c, hipMemcpy(dw.p, words, n_words * 8, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(doff.p, read_offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice));
-    }
-    int rc = mc_reads_last_copy_dev(c, dw.p, doff.p, n_reads, flags, dlast.p);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(c, hipMemcpy(last, dlast.p, n_reads * 4, hipMemcpyDeviceToHost));
-    return MC_OK;
+    HostStage st(c);
+    const uint64_t *dw = st.in(words, packed_words(read_offsets, n_reads)), *doff = st.in(read_offsets, n_reads + 1);
+    uint32_t *dlast = st.out<uint32_t>(n_reads);
+    if (int rc = st.staged()) return rc;
+    if (int rc = mc_reads_last_copy_dev(c, dw, doff, n_reads, flags, dlast)) return rc;
+    return st.back(last, dlast, n_reads);
 }

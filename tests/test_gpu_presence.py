@@ -177,3 +177,45 @@ def test_presence_refusals(oracle):
         with pytest.raises(native.McError) as e:
             m.kmer_presence([a, k31], None, lo0)
         assert e.value.code == -1
+
+
+def test_tables_in_bins_and_in_hash_prefix_regions_in_one_call(oracle, monkeypatch):
+    """Tables of one call that disagree on mm_k (packed k = 31): tables 0 and 2 in minimizer bins, tables 1 and 3 -- created with
+    MC_SUPERKMERS=0 -- in hash-prefix regions; mc_kmer_presence and mc_seq_coverage against the oracle, for two lists of tables."""
+    import metacherchant_amd as m
+    k, mode = 31, 0
+    parts, q, want = _case(oracle, k, mode)
+    assert sorted(set(want.tolist())) == list(range(16)), sorted(set(want.tolist()))
+    _, reads, off = synth_case(1, 200000, 2000, 150, 100, first_read=0)
+    n_seqs = 250
+    codes, seq_off = reads[:int(off[n_seqs])], off[:n_seqs + 1]
+    get = np.zeros((n_seqs, 4, 2), dtype=np.uint64)  # per sequence and table: the sum of max(get, 0), the windows with get > 0
+    for s in range(n_seqs):
+        for v in _windows(codes[int(seq_off[s]):int(seq_off[s + 1])], np.array([0, int(seq_off[s + 1] - seq_off[s])]), k):
+            key = oracle.key(_codes(v, k), k, mode)
+            for t in range(4):
+                c = max(parts[t][0].get(key), 0)
+                get[s, t, 0] += c
+                get[s, t, 1] += c > 0
+    hi, lo = _split(q)
+    ctxs = []
+    try:
+        for t, (_, pcodes, o) in enumerate(parts):
+            with monkeypatch.context() as mp:  # (the switch is read once per context, by mc_create)
+                if t & 1:
+                    mp.setenv("MC_SUPERKMERS", "0")
+                else:
+                    mp.delenv("MC_SUPERKMERS", raising=False)
+                c = m.Context(k, mode, 0, 0)
+            ctxs.append(c)
+            c.add_reads_packed(oracle.pack(pcodes), o)
+            c.finalize()
+        for pick in ([0, 1, 2, 3], [1, 0]):
+            w = np.zeros_like(want)
+            for j, t in enumerate(pick):
+                w |= ((want >> t) & 1) << j
+            assert np.array_equal(m.kmer_presence([ctxs[t] for t in pick], hi, lo), w), pick
+            assert np.array_equal(m.seq_coverage([ctxs[t] for t in pick], codes, seq_off), get[:, pick, :]), pick
+    finally:
+        for c in ctxs:
+            c.close()
