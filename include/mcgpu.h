@@ -463,6 +463,33 @@ int mc_kmer_presence_dev(mc_ctx *const *tables, uint32_t n_tables, const uint64_
                          uint8_t *d_mask);
 int mc_kmer_presence(mc_ctx *const *tables, uint32_t n_tables, const uint64_t *hi, const uint64_t *lo, uint64_t n, uint8_t *mask);
 
+/* ---- reads in a set: how many windows of every read are k-mers of a small exact set, and which reads that keeps -- the
+ * environment-assembler-finder's filter of the reads by an environment (src/algo/ReadsFilter.java:47-68; membership is
+ * subgraph.containsKey(normalizeDna(kmer)), src/algo/OneSequenceCalculator.java:150-152: a test on the k-mer's bases, not on its
+ * table key, so hash keys and their collisions play no part here).
+ * Reads come in the layout of mc_classify_reads (whole, N as code 0, the pad word).  The set is n_set oriented packed k-mers in the
+ * layout of mc_bfs_result and mc_kmer_presence (hi may be NULL when k <= 32, and is not read then), in any orientation, duplicates
+ * allowed: the call canonicalises them, a k-mer and its reverse complement are one member.  k is the context's; its key mode and its
+ * table play no part (any context, before or after mc_finalize_counts).  For read r of length L:
+ *   hits[r] = #{i in 0 .. L - k - 1 : window i is a member} -- the reference's loop is `i < len - k`: the last window is never
+ *             tested; there is no early exit in hits;
+ *   keep[r] = hits[r] >= max(1, (L - k + 1) * pct / 100), in Java's int arithmetic (the division truncates).
+ * A read with L <= k has no tested window: hits 0, keep 0.  pct = 100 therefore keeps no read at all.
+ * The set becomes an open-addressing table of canonical k-mers in device memory (one word a slot for k <= 32, two above, at most
+ * half full) and a bit filter that every workgroup holds in LDS; a window that the filter passes is compared with the table's
+ * k-mer in full, so the result never rests on the filter.  flags & MC_READS_IN_SET_WEAK_FILTER (tests only): no filter, every
+ * window goes to the table (as it does for sets of more than 2^19 k-mers).
+ * Errors: MC_EINVAL for null pointers (hi at k <= 32 excepted), pct outside 0 .. 100, or n_set >= 2^31.  n_reads == 0 is MC_OK;
+ * n_set == 0 is MC_OK with every output 0.  Outputs are not written on an error.
+ * mc_reads_in_set takes host pointers, mc_reads_in_set_dev device ones (d_hits: 4 bytes a read, d_keep: one). */
+#define MC_READS_IN_SET_WEAK_FILTER 1
+int mc_reads_in_set_dev(mc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_read_offsets, uint64_t n_reads,
+                        const uint64_t *d_set_hi, const uint64_t *d_set_lo, uint64_t n_set, int pct, int flags,
+                        uint32_t *d_hits, uint8_t *d_keep);
+int mc_reads_in_set(mc_ctx *ctx, const uint64_t *words, const uint64_t *read_offsets, uint64_t n_reads,
+                    const uint64_t *set_hi, const uint64_t *set_lo, uint64_t n_set, int pct, int flags,
+                    uint32_t *hits, uint8_t *keep);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

@@ -1688,6 +1688,14 @@ std::string Environment::graph_txt() const
     return out;
 }
 
+std::vector<kmer_t> Environment::kmers() const
+{
+    std::vector<kmer_t> out;
+    out.reserve(subgraph_.size());
+    subgraph_.for_each([&](kmer_t key, int, int) { out.push_back(key); });
+    return out;
+}
+
 Environment::Colour Environment::colour_of_mask(unsigned mask)
 {
     switch (mask & 15u) {
@@ -1922,6 +1930,47 @@ void Environment::write_all(const std::string &out_prefix, int chunk_length)
     write_file(out_prefix + "/graph.gfa", graph_gfa());
     write_file(out_prefix + "/tsvs/edges.tsv", tsv_edges());
     write_file(out_prefix + "/tsvs/nodes.tsv", tsv_nodes());
+}
+
+// ------------------------------------------------------------------------------------------ cutReads<i>.fasta
+
+CutReadsWriter::CutReadsWriter(const std::string &path, int file_index) : path_(path), f_(nullptr), index_(file_index)
+{
+    write_file(path, "");  // outputCutReads.getParentFile().mkdirs(); new PrintWriter(...)
+    f_ = fopen(path.c_str(), "wb");
+    if (!f_) throw Error("Could not write " + path);
+}
+
+CutReadsWriter::~CutReadsWriter()
+{
+    if (f_) fclose(f_);
+}
+
+void CutReadsWriter::flush()
+{
+    if (!buf_.empty() && fwrite(buf_.data(), 1, buf_.size(), f_) != buf_.size()) throw Error("Could not write " + path_);
+    buf_.clear();
+}
+
+void CutReadsWriter::add(const uint8_t *codes, size_t n)
+{
+    kept_++;
+    buf_.push_back('>');
+    append_uint(buf_, (unsigned long long)index_);
+    buf_.push_back('|');
+    append_uint(buf_, kept_);
+    buf_.push_back('\n');
+    for (size_t i = 0; i < n; i++) buf_.push_back("AGCT"[codes[i] & 3]);
+    buf_.push_back('\n');
+    if (buf_.size() >= (1u << 20)) flush();
+}
+
+void CutReadsWriter::close()
+{
+    flush();
+    FILE *f = f_;
+    f_ = nullptr;
+    if (fclose(f) != 0) throw Error("Could not write " + path_);
 }
 
 // ------------------------------------------------------------------------------------------ environment-finder-multi

@@ -6,6 +6,7 @@
 // Citations: src/... = reference src/; itmo!/x = ru/ifmo/genetics/x in lib/itmo-assembler-src.jar.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <deque>
 #include <functional>
 #include <map>
@@ -243,6 +244,9 @@ public:
     // :217-219 (+ runTrimPaths :241-262 when trim): distanceToKmer -> subgraph
     void add_pass(const BfsPass &p, bool trim);
     size_t size() const { return subgraph_.size(); }
+    // the subgraph's keys (normalised k-mers) in its iteration order, graph.txt's: what isContainedInSubgraph tests against
+    // (OneSequenceCalculator.java:150-152)
+    std::vector<kmer_t> kmers() const;
     bool order_guaranteed() const { return !subgraph_.treeified() && !d_treeified_; }
     std::string graph_txt() const;                    // printEnvironment :297-310
     void create_picture();                            // initializeStructures + doMerge :387-451
@@ -275,6 +279,26 @@ private:
 };
 
 void write_file(const std::string &path, const std::string &text);  // mkdirs + write
+
+// ---- the environment-assembler-finder's cutReads<i>.fasta (src/algo/ReadsFilter.java:36-41,58-66): created empty with its
+// directory, then `>i|n` and the bases as DnaQ.toString() prints them for every kept read of file i, n counting them from 1
+class CutReadsWriter {
+public:
+    CutReadsWriter(const std::string &path, int file_index);
+    ~CutReadsWriter();
+    CutReadsWriter(const CutReadsWriter &) = delete;
+    CutReadsWriter &operator=(const CutReadsWriter &) = delete;
+    void add(const uint8_t *codes, size_t n);  // base codes A0 G1 C2 T3 (N is 0 already)
+    uint64_t kept() const { return kept_; }
+    void close();  // throws Error when the file could not be written
+
+private:
+    std::string path_, buf_;
+    FILE *f_;
+    int index_;
+    uint64_t kept_ = 0;
+    void flush();
+};
 
 // ---- --tool environment-finder-multi: src/tools/EnvironmentFinderMultiMain.java,
 // src/algo/MultiSequenceCalculator.java, src/algo/MultiNode.java, src/io/writers/GFAWriterMulti.java,

@@ -8,6 +8,9 @@
 // `mc_hosttest colour <dump> <out_dir> <name>`: one sequence of the recipient-visualiser.  dump: k / the sequence / n / n lines
 // "kmer dist cov mask" (its walk, in insertion order, with every k-mer's class mask) / m / m k-mers the graph holds beside them;
 // writes <out_dir>/<name>_seqs.fasta and <name>.gfa and prints the "Extending endings" line.
+// `mc_hosttest kmers <dump>`: the subgraph's keys of an `env` dump, one a line, as Environment::kmers lists them.
+// `mc_hosttest cutreads <reads file> <keep> <out.fasta> <index>`: the reads whose character in <keep> (one '0' / '1' a read) is '1'
+// through CutReadsWriter.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -122,8 +125,23 @@ int main(int argc, char **argv)
             write_file(std::string(argv[3]) + "/" + argv[4] + ".gfa", env.graph_gfa());
             return 0;
         }
-        if (argc != 4 || std::string(argv[1]) != "env") {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
+        if (argc == 6 && std::string(argv[1]) == "cutreads") {
+            const std::string keep = argv[3];
+            CutReadsWriter out(argv[4], atoi(argv[5]));
+            DnaQReader reader(argv[2]);
+            DnaQBatch b;
+            b.clear();
+            while (reader.read(b, 1000)) {}
+            if (keep.size() != b.n_reads()) throw Error("one character of <keep> a read");
+            for (size_t r = 0; r < b.n_reads(); r++)
+                if (keep[r] == '1') out.add(b.codes.data() + b.offsets[r], (size_t)(b.offsets[r + 1] - b.offsets[r]));
+            out.close();
+            printf("%llu\n", (unsigned long long)out.kept());
+            return 0;
+        }
+        const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
+        if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);
@@ -148,6 +166,10 @@ int main(int argc, char **argv)
                 pass.dist[i] = d; pass.cov[i] = (int16_t)c; pass.last[i] = (uint8_t)l;
             }
             env.add_pass(pass, trim != 0);
+        }
+        if (list_kmers) {
+            for (const kmer_t v : env.kmers()) printf("%s\n", unpack_kmer128(v, k).c_str());
+            return 0;
         }
         env.write_all(argv[3], chunk);
         return 0;

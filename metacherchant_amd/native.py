@@ -71,6 +71,7 @@ LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fi
 CLASS_NOT_FOUND, CLASS_HALF_FOUND, CLASS_FOUND = 0, 1, 2  # mc_triple_classes
 SEQ_COV_MAX_TABLES = 4  # mc_seq_coverage
 PRESENCE_MAX_TABLES = 4  # mc_kmer_presence
+READS_IN_SET_WEAK_FILTER = 1  # mc_reads_in_set flags (tests only): no bit filter, every window is looked up in the set's table
 
 
 # every symbol include/mcgpu.h declares; tests check that the library exports all of them
@@ -84,7 +85,7 @@ EXPORTS = [
     "mc_read_store_seek", "mc_read_store_tell", "mc_read_store_import_dev", "mc_get_stats", "mc_reset_stats", "mc_trim", "mc_synth_reads_dev", "mc_synth_genome",
     "mc_shard_export", "mc_shard_attach", "mc_shard_detach", "mc_classify_reads", "mc_classify_reads_dev",
     "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev", "mc_seq_coverage", "mc_seq_coverage_dev",
-    "mc_kmer_presence", "mc_kmer_presence_dev",
+    "mc_kmer_presence", "mc_kmer_presence_dev", "mc_reads_in_set", "mc_reads_in_set_dev",
 ]
 
 _LIB = None
@@ -177,6 +178,9 @@ def load():
     if hasattr(L, "mc_kmer_presence"):
         L.mc_kmer_presence.argtypes = [C.POINTER(vp), C.c_uint32, u64p, u64p, u64, C.POINTER(C.c_uint8)]
         L.mc_kmer_presence_dev.argtypes = [C.POINTER(vp), C.c_uint32, vp, vp, u64, vp]
+    if hasattr(L, "mc_reads_in_set"):
+        L.mc_reads_in_set.argtypes = [vp, u64p, u64p, u64, u64p, u64p, u64, i32, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+        L.mc_reads_in_set_dev.argtypes = [vp, vp, vp, u64, vp, vp, u64, i32, i32, vp, vp]
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -623,6 +627,32 @@ def kmer_presence_dev(contexts, d_hi, d_lo, n, d_mask):
     rc = load().mc_kmer_presence_dev(handles, len(contexts), _dptr(d_hi), _dptr(d_lo), int(n), _dptr(d_mask))
     if rc != 0:
         raise McError(rc, (load().mc_last_error(contexts[0]._h) or b"").decode() if contexts else "")
+
+
+def reads_in_set(context, codes_or_words, offsets, hi, lo, pct=1, weak=False, packed=None):
+    """mc_reads_in_set: for every read, the number of its windows 0 .. L - k - 1 (the last window is never tested, as in the reference's
+    ReadsFilter) whose k-mer, or its reverse complement, is one of the oriented packed k-mers (hi << 64 | lo; hi may be None when
+    k <= 32; any orientation, duplicates allowed), and whether the read is kept: hits >= max(1, (L - k + 1) * pct // 100).  Reads as
+    Context.classify_reads takes them.  Needs no table.  weak: the tests' run without the bit filter (the result is the same).
+    Returns (hits uint32, keep bool)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = max(len(offsets) - 1, 0)
+    words = Context._words(codes_or_words, offsets, packed)
+    lo = np.ascontiguousarray(lo, dtype=np.uint64)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64) if hi is not None else None
+    if hi is not None and len(hi) != len(lo):
+        raise ValueError("hi and lo need one entry a k-mer")
+    hits, keep = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+    context._chk(load().mc_reads_in_set(context._h, _p(words, C.c_uint64), _p(offsets, C.c_uint64), n, _p(hi, C.c_uint64) if hi is not None else None,
+                                        _p(lo, C.c_uint64), len(lo), int(pct), READS_IN_SET_WEAK_FILTER if weak else 0, _p(hits, C.c_uint32),
+                                        _p(keep, C.c_uint8)))
+    return hits, keep.astype(bool)
+
+
+def reads_in_set_dev(context, d_words, d_offsets, n_reads, d_hi, d_lo, n_set, d_hits, d_keep, pct=1, weak=False):
+    """mc_reads_in_set_dev: d_hi (may be None when k <= 32) and d_lo hold n_set uint64 each, d_hits 4 bytes a read, d_keep one"""
+    context._chk(load().mc_reads_in_set_dev(context._h, _dptr(d_words), _dptr(d_offsets), int(n_reads), _dptr(d_hi), _dptr(d_lo), int(n_set), int(pct),
+                                            READS_IN_SET_WEAK_FILTER if weak else 0, _dptr(d_hits), _dptr(d_keep)))
 
 
 def key_owner(key, n_owners):
