@@ -490,6 +490,40 @@ int mc_reads_in_set(mc_ctx *ctx, const uint64_t *words, const uint64_t *read_off
                     const uint64_t *set_hi, const uint64_t *set_lo, uint64_t n_set, int pct, int flags,
                     uint32_t *hits, uint8_t *keep);
 
+/* ---- components: which k-mers of the table hang together -- what the fmt-visualizer's walks reach (src/tools/FMTVisualizer.java:
+ * 113-139 starts src/algo/KmerEnvCalculator.java's runBfs at every window whose count is still above 0; the walk has no visited set
+ * but zeroes every k-mer it pops, so it reaches exactly the connected component of its first k-mer, and the scan's seeds are the
+ * first windows of the components in scan order).
+ * Sequences come in the layout of mc_classify_reads (whole, N as code 0, the pad word).
+ *   vertex     a key of the table with get > 0 that at least one window of the sequences holds (a counted k-mer that no window
+ *              of the sequences holds is in no component);
+ *   edge       between the keys of two k-mers that are StringUtils.allNeighbors of each other;
+ *   numbering  components by the scan position (sequence, then offset) of their first window: the reference's comp<N>;
+ *   members    of component c: entries comp_offsets[c] .. comp_offsets[c + 1] - 1 of hi / lo / cov.  Member 0 is the seed window's
+ *              k-mer in the read's orientation; the order of the others is unspecified (it may differ from call to call).
+ * The table is only read (a table of hash keys still in minimizer bins is moved to hash-prefix regions first, as mc_classify_reads
+ * does; every mc_get answer stays what it was).
+ * Work: one sweep of the windows (first[slot] = the smallest scan position of a window that holds the slot's key), one sweep of the
+ * table with eight look-ups a claimed slot and a lock-free union-find over slot numbers (32-bit parents below 2^32 slots), two
+ * more sweeps to list the members; the roots are sorted on the host.  12 or 16 bytes of device memory a table slot while it runs.
+ * Limit, hash keys only: the k-mer of a key's first window explores for the key.  The reference's walk also steps onto a string
+ * that was never read but whose hash is a key, and goes on from THAT string's neighbours.  Results equal the reference's exactly when
+ * no two distinct canonical k-mers among the members and their neighbours share a key; for packed keys (k <= 31) always.
+ * Errors: MC_EINVAL for null pointers, MC_ESTATE before mc_finalize_counts; n_seqs == 0 (or no bases) is MC_OK with an empty
+ * result (comp_offsets = {0}).  *out is zeroed on an error.  Free a result with mc_components_free (NULL and zeroed results are
+ * fine).  mc_components takes host pointers, mc_components_dev device ones; the result is on the host in both. */
+typedef struct {
+    uint64_t n_components, n_kmers;
+    uint64_t *comp_offsets;        /* n_components + 1: members of component c are [comp_offsets[c], comp_offsets[c+1]) */
+    uint64_t *seed_seq, *seed_pos; /* per component: sequence index and base offset of its first window in scan order */
+    uint64_t *hi, *lo;             /* per member: one oriented k-mer that holds the key (hi all zero when k <= 32) */
+    int16_t  *cov;                 /* per member: what mc_get answers for its key */
+    double device_ms;              /* summed device time of the passes (HIP events) */
+} mc_components_result;  /* (not mc_components: C has one name space for typedefs and functions) */
+int mc_components_dev(mc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_seq_offsets, uint64_t n_seqs, mc_components_result *out);
+int mc_components(mc_ctx *ctx, const uint64_t *words, const uint64_t *seq_offsets, uint64_t n_seqs, mc_components_result *out);
+void mc_components_free(mc_components_result *r);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

@@ -1,6 +1,6 @@
 // The library's context and what more than one unit of it needs (host side; private to libmcgpu.so, not include/mcgpu.h).
 //
-// The library is nine units, each defining and launching its own kernels:
+// The library is ten units, each defining and launching its own kernels:
 //   mcgpu.hip       the table, the key join, the counting pipeline, the context ABI, and the table work of the walk (solid table,
 //                   the check of its "absent" look-ups)
 //   reads_file.hip  the device tokeniser's driver and mc_add_reads_file
@@ -11,6 +11,7 @@
 //   seq_cov.hip     mc_seq_coverage*: depth and breadth of sequences of any length in up to four tables at once, cut by positions
 //   presence.hip    mc_kmer_presence*: which of up to four tables hold each of a list of k-mers, one launch
 //   reads_in_set.hip mc_reads_in_set*: every read's windows against a small exact set of k-mers behind a bit filter in LDS
+//   components.hip  mc_components*: the connected components of the table's k-mers that a set of sequences holds (union-find over slots)
 // multi_table.h is what seq_cov.hip and presence.hip share: one key's home slots in several tables, the probing behind them, and the
 // host's checks of a list of contexts.  A function below the "across units" line is what one unit lends another; everything else
 // stays static in its unit.

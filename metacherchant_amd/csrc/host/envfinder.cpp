@@ -1666,6 +1666,11 @@ void Environment::add_pass(const BfsPass &p, bool trim)
     if (d.treeified()) d_treeified_ = true;  // (a removal from a treeified bin of distanceToKmer: runTrimPaths)
 }
 
+void Environment::add_puts(const std::vector<std::pair<kmer_t, int>> &puts)
+{
+    for (const auto &p : puts) subgraph_.put(normalize128(p.first, k_), p.second);
+}
+
 static inline void append_uint(std::string &out, unsigned long long v)
 {
     char buf[24];

@@ -243,6 +243,10 @@ public:
     static size_t extensions(const Outside &o, const uint8_t *in_graph);
     // :217-219 (+ runTrimPaths :241-262 when trim): distanceToKmer -> subgraph
     void add_pass(const BfsPass &p, bool trim);
+    // The fmt-visualizer's subgraph (src/algo/KmerEnvCalculator.java:87-89): subgraph.put(normalizeDna(kmer), value) for every entry,
+    // in the order given -- the walk's pops, a k-mer popped again overwriting its value where it is.  With no gene sequences the
+    // nodes are not gene nodes and seqs_fasta's header is KmerEnvCalculator's `Id<n>`; colours as set_colours gives them.
+    void add_puts(const std::vector<std::pair<kmer_t, int>> &puts);
     size_t size() const { return subgraph_.size(); }
     // the subgraph's keys (normalised k-mers) in its iteration order, graph.txt's: what isContainedInSubgraph tests against
     // (OneSequenceCalculator.java:150-152)

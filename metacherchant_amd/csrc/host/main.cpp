@@ -8,6 +8,8 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -16,7 +18,9 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include <hip/hip_runtime_api.h>
@@ -85,6 +89,9 @@ struct Options {
     // --tool recipient-visualiser (src/tools/RecipientVisualiser.java:42-92)
     std::vector<std::string> after_files;
     std::string input_dir, ext;
+    // --tool fmt-visualizer (src/tools/FMTVisualizer.java:39-85)
+    std::vector<std::string> donor_files, before_files;
+    int processors = 0;  // -p: the threads that replay the components' walks (0: as many as the machine has, 16 at most)
     // --tool environment-assembler-finder (src/tools/EnvironmentAssemblerFinder.java:33-122)
     long long procfiltration = 1;
     std::string assembler, assemblerpath;
@@ -130,6 +137,14 @@ const OptSpec SEQ_COV_SPECS[] = {
 // --tool recipient-visualiser: its parameters (RecipientVisualiser.java:42-92) and the launch options
 const OptSpec RECIPIENT_SPECS[] = {
     {"k", "k", 0}, {"after-files", "after", 2}, {"seq", "seq", 0}, {"maxkmers", nullptr, 0}, {"maxradius", nullptr, 0}, {"hash", nullptr, 0},
+    {"output-dir", "o", 0}, {"input-dir", "i", 0}, {"ext", "ext", 0},
+    {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0},
+};
+
+// --tool fmt-visualizer: its parameters (FMTVisualizer.java:39-85) and the launch options
+const OptSpec FMT_SPECS[] = {
+    {"k", "k", 0}, {"donor-files", "donor", 2}, {"before-files", "before", 2}, {"after-files", "after", 2}, {"hash", nullptr, 0},
     {"output-dir", "o", 0}, {"input-dir", "i", 0}, {"ext", "ext", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0},
@@ -192,6 +207,7 @@ Options parse_args(int argc, char **argv)
                             : tool == "seq-cov"                 ? SpecTable{std::begin(SEQ_COV_SPECS), std::end(SEQ_COV_SPECS)}
                             : tool == "recipient-visualiser"    ? SpecTable{std::begin(RECIPIENT_SPECS), std::end(RECIPIENT_SPECS)}
                             : tool == "environment-assembler-finder" ? SpecTable{std::begin(ASSEMBLER_SPECS), std::end(ASSEMBLER_SPECS)}
+                            : tool == "fmt-visualizer"          ? SpecTable{std::begin(FMT_SPECS), std::end(FMT_SPECS)}
                                                                 : SpecTable{std::begin(SPECS), std::end(SPECS)};
     std::map<std::string, std::vector<std::string>> got;
     for (int i = 1; i < argc; i++) {
@@ -241,6 +257,9 @@ Options parse_args(int argc, char **argv)
     multi("from-both", o.from_both);
     multi("itself", o.itself);
     multi("after-files", o.after_files);
+    multi("donor-files", o.donor_files);
+    multi("before-files", o.before_files);
+    if (auto v = val("available-processors")) o.processors = (int)parse_int("available-processors", *v);
     if (auto v = val("input-dir")) o.input_dir = *v;
     if (auto v = val("ext")) o.ext = *v;
     if (auto v = val("read-file")) o.read_file = *v;
@@ -361,6 +380,17 @@ void usage()
     puts("  -o, --output-dir <arg>         output directory (default <work-dir>/graph)");
     puts("  -i, --input-dir <arg>          directory of came_from_{donor,baseline,both}_{1,2,s}.<ext> and came_itself_{1,2,s}.<ext> (MANDATORY)");
     puts("  -ext, --ext <arg>              extension of those files (MANDATORY)");
+    puts("Input parameters of --tool fmt-visualizer (one coloured GFA a connected component of the donor, the pre-FMT and the post-FMT graph, every");
+    puts("k-mer coloured by the class files that hold it; writes <output-dir>/{donor,before,after}/comp<N>{.gfa,_seqs.fasta}):");
+    puts("  -k, --k <arg>                  k-mer size (MANDATORY)");
+    puts("  -donor, --donor-files <args>   donor metagenomic reads (MANDATORY)");
+    puts("  -before, --before-files <args> pre-FMT recipient metagenomic reads (MANDATORY)");
+    puts("  -after, --after-files <args>   post-FMT recipient metagenomic reads (MANDATORY)");
+    puts("      --hash <arg>               hash function to use for k > 31: poly or fnv1a (default poly)");
+    puts("  -o, --output-dir <arg>         output directory (default <work-dir>/graph)");
+    puts("  -i, --input-dir <arg>          directory of {settle,not_settle,stay,gone,came_from_*,came_itself}_{1,2,s}.<ext> (MANDATORY)");
+    puts("  -ext, --ext <arg>              extension of those files (MANDATORY)");
+    puts("  -p, --available-processors <n> threads that replay the components' walks");
     puts("Input parameters of --tool environment-assembler-finder (the environment of ONE sequence, then the reads of every -i file that belong");
     puts("to it as <output>/cutReads<i>.fasta; with --assembler, their assembly and the environment again, at k = 55, in the contigs):");
     puts("  -k, --k <arg>                  k-mer size (MANDATORY)");
@@ -1229,6 +1259,171 @@ int run_recipient_visualiser(const Options &o)
     return 0;
 }
 
+// --tool fmt-visualizer (src/tools/FMTVisualizer.java:223-317, src/algo/KmerEnvCalculator.java): for the donor, the pre-FMT and the
+// post-FMT reads in turn, one coloured GFA and one FASTA a connected component of the phase's graph.  The reference walks from every
+// window whose count is still above 0 and zeroes what it reaches; here mc_components gives the components with their seeds at once,
+// mc_kmer_presence the class tables of every member, and only what the walk's ORDER decides is replayed on the host, a component
+// at a time on -p threads (the reference cannot: every walk writes the one shared map): the FIFO without a visited set over the
+// component's own k-mer -> count map, which gives the order of the subgraph's puts and the coverage 0 of a k-mer popped twice.
+
+// KmerEnvCalculator.runBfs (:60-76) over one component: `canon` sorted, `count` beside it (zeroed here); the puts in pop order
+std::vector<std::pair<kmer_t, int>> replay_component_walk(int k, kmer_t seed, const std::vector<kmer_t> &canon, std::vector<int> &count)
+{
+    const kmer_t kmask = ((kmer_t)1 << (2 * k)) - 1;
+    const int top = 2 * (k - 1);
+    auto at = [&](kmer_t v) -> int {
+        const kmer_t c = normalize128(v, k);
+        const auto it = std::lower_bound(canon.begin(), canon.end(), c);
+        return it != canon.end() && *it == c ? (int)(it - canon.begin()) : -1;
+    };
+    std::vector<kmer_t> queue{seed};
+    std::vector<std::pair<kmer_t, int>> puts;
+    for (size_t head = 0; head < queue.size(); head++) {
+        const kmer_t kmer = queue[head];
+        for (unsigned c = 0; c < 4; c++) {  // allNeighbors: A, G, C, T, the left neighbour before the right one
+            const kmer_t nb[2] = {((kmer_t)c << top) | (kmer >> 2), ((kmer << 2) & kmask) | c};
+            for (const kmer_t x : nb) {
+                const int e = at(x);
+                if (e >= 0 && count[(size_t)e] > 0) queue.push_back(x);
+            }
+        }
+        const int e = at(kmer);  // (a member: it was queued with a count above 0)
+        puts.emplace_back(kmer, count[(size_t)e]);
+        count[(size_t)e] = 0;  // addAndBound(key, -get)
+    }
+    return puts;
+}
+
+void fmt_phase(const Options &o, int mode, const std::string &name, const std::vector<std::string> &files, const std::vector<std::string> &classes,
+               const std::string &out_root)
+{
+    info("Loading " + name + " reads ...");
+    if (o.k > 31) {
+        info("Reading hashes of k-mers instead");
+        info(mode == MC_KEY_FNV1A ? "Using FNV1a hash function" : "Using default polynomial hash function");
+    }
+    const uint32_t nt = (uint32_t)classes.size();
+    std::vector<std::vector<std::string>> class_files(nt);
+    for (uint32_t t = 0; t < nt; t++)
+        for (const char *part : {"_1.", "_2.", "_s."}) {
+            class_files[t].push_back(o.input_dir + "/" + classes[t] + part + o.ext);
+            FILE *f = fopen(class_files[t].back().c_str(), "rb");
+            if (!f) throw Error("Could not read class file " + class_files[t].back());
+            fclose(f);
+        }
+    mc_config cfg{};
+    cfg.k = o.k;
+    cfg.key_mode = mode;
+    cfg.device = o.device;
+    cfg.capacity_hint = o.capacity_hint;
+    Engine G, E[4];  // the graph, then the two or four class tables: all on the device until the phase ends
+    G.open(cfg, {});
+    MC_CHECK(G.c, mc_set_read_pointers(G.c, 0));  // (nothing walks these tables: no read store)
+    load_reads(files, G);
+    MC_CHECK(G.c, mc_trim(G.c));
+    mc_ctx *tables[4] = {};
+    cfg.capacity_hint = 0;
+    for (uint32_t t = 0; t < nt; t++) {
+        E[t].open(cfg, {});
+        tables[t] = E[t].c;
+        MC_CHECK(tables[t], mc_set_read_pointers(tables[t], 0));
+        load_reads(class_files[t], E[t]);
+        MC_CHECK(tables[t], mc_trim(tables[t]));
+    }
+    // ReadersUtils.loadDnaQs: the phase's reads again, every record whole, N as A
+    DnaQBatch seqs;
+    seqs.clear();
+    try {
+        for (const std::string &f : files) {
+            DnaQReader reader(f);
+            while (reader.read(seqs, 1u << 16)) {}
+        }
+    } catch (const Error &) {
+        throw Error("Could not load sequences from " + o.donor_files[0]);  // (all three phases name this file, :117,137,161)
+    }
+    info("Creating " + name + " image ...");
+    const uint64_t n_bases = seqs.codes.size();
+    std::vector<uint64_t> words(n_bases / 32 + 2, 0);
+    for (uint64_t i = 0; i < n_bases; i++) words[i >> 5] |= (uint64_t)(seqs.codes[i] & 3u) << (62 - 2 * (i & 31));
+    mc_components_result res{};
+    struct ResGuard {
+        mc_components_result &r;
+        ~ResGuard() { mc_components_free(&r); }
+    } guard{res};
+    MC_CHECK(G.c, mc_components(G.c, words.data(), seqs.offsets.data(), seqs.n_reads(), &res));
+    std::vector<uint8_t> mask(res.n_kmers);
+    if (res.n_kmers) MC_CHECK(tables[0], mc_kmer_presence(tables, nt, res.hi, res.lo, res.n_kmers, mask.data()));
+    const std::string out_dir = out_root + "/" + name;
+    std::atomic<uint64_t> next{0};
+    std::mutex err_mu;
+    std::string err;
+    auto work = [&] {
+        for (uint64_t c; (c = next.fetch_add(1)) < res.n_components;) {
+            try {
+                const uint64_t a = res.comp_offsets[c], b = res.comp_offsets[c + 1];
+                std::vector<std::pair<kmer_t, uint64_t>> order;  // (canonical k-mer, member)
+                order.reserve(b - a);
+                for (uint64_t i = a; i < b; i++) order.emplace_back(normalize128(((kmer_t)res.hi[i] << 64) | res.lo[i], o.k), i);
+                std::sort(order.begin(), order.end());
+                std::vector<kmer_t> canon;
+                std::vector<int> count;
+                for (const auto &e : order) { canon.push_back(e.first); count.push_back(res.cov[e.second]); }
+                const kmer_t seed = ((kmer_t)res.hi[a] << 64) | res.lo[a];
+                Environment env(o.k, {});
+                env.add_puts(replay_component_walk(o.k, seed, canon, count));
+                env.set_colours([&](kmer_t kmer) {
+                    const auto it = std::lower_bound(canon.begin(), canon.end(), kmer);
+                    const unsigned m = mask[order[(size_t)(it - canon.begin())].second];
+                    if (nt == 4) return Environment::colour_of_mask(m);
+                    // getDonorColorNode / getBeforeColorNode (:195-207): bit 0 the found class (settle, stay), bit 1 the other
+                    return m == 1 ? Environment::GREEN : m == 2 ? Environment::BLUE : m == 3 ? Environment::GREY : Environment::BLACK;
+                });
+                env.create_picture();
+                const std::string file = out_dir + "/comp" + std::to_string(c);
+                write_file(file + "_seqs.fasta", env.seqs_fasta(1));
+                write_file(file + ".gfa", env.graph_gfa());
+            } catch (const std::exception &e) {
+                std::lock_guard<std::mutex> g(err_mu);
+                if (err.empty()) err = e.what();
+            }
+        }
+    };
+    if (res.n_components) write_file(out_dir + "/comp0.gfa", "");  // (the directory, made once before the threads write into it)
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const uint64_t n_threads = std::max<uint64_t>(1, std::min<uint64_t>(o.processors > 0 ? (uint64_t)o.processors : std::min(hw, 16u), res.n_components));
+    std::vector<std::thread> pool;
+    for (uint64_t t = 1; t < n_threads; t++) pool.emplace_back(work);
+    work();
+    for (auto &th : pool) th.join();
+    if (!err.empty()) throw Error(err);
+}
+
+int run_fmt_visualizer(const Options &o)
+{
+    if (o.k < 0) throw Error("Parameter 'k' is mandatory");
+    if (o.donor_files.empty()) throw Error("Parameter 'donor-files' is mandatory");
+    if (o.before_files.empty()) throw Error("Parameter 'before-files' is mandatory");
+    if (o.after_files.empty()) throw Error("Parameter 'after-files' is mandatory");
+    if (o.input_dir.empty()) throw Error("Parameter 'input-dir' is mandatory");
+    if (o.ext.empty()) throw Error("Parameter 'ext' is mandatory");
+    if (o.k < 1 || o.k > 63)
+        throw Error("k = " + std::to_string(o.k) + " is not supported: this build handles k <= 31 (packed keys) and 32 <= k <= 63 (hash keys)");
+    if (!o.devices.empty()) throw Error("--devices is for --tool environment-finder: fmt-visualizer keeps a phase's tables on one device (--device)");
+    if (!open_work_dir(o, "k=" + std::to_string(o.k) + "\ninput-dir=" + o.input_dir + "\next=" + o.ext + "\n")) return 0;
+    const std::string out_root = o.output_dir.empty() ? o.work_dir + "/graph" : o.output_dir;
+    int mode = MC_KEY_PACKED;
+    if (o.k > 31) {
+        std::string h = o.hash;
+        for (char &c : h) c = (char)tolower((unsigned char)c);
+        mode = h == "fnv1a" ? MC_KEY_FNV1A : MC_KEY_POLY;
+    }
+    fmt_phase(o, mode, "donor", o.donor_files, {"settle", "not_settle"}, out_root);
+    fmt_phase(o, mode, "before", o.before_files, {"stay", "gone"}, out_root);
+    fmt_phase(o, mode, "after", o.after_files, {"came_from_donor", "came_from_baseline", "came_from_both", "came_itself"}, out_root);
+    write_file(o.work_dir + "/SUCCESS", "");
+    return 0;
+}
+
 // --tool environment-assembler-finder (src/tools/EnvironmentAssemblerFinder.java:175-240): the environment of one sequence, then every
 // read of every --reads file tested against it (src/algo/ReadsFilter.java: mc_reads_in_set_dev, whole reads in batches, the set of
 // the environment's k-mers on the device once a phase) and the reads that belong to it written to <output>/cutReads<i>.fasta; with
@@ -1467,9 +1662,10 @@ int run(const Options &o)
     if (o.tool == "seq-cov") return run_seq_cov(o);
     if (o.tool == "recipient-visualiser") return run_recipient_visualiser(o);
     if (o.tool == "environment-assembler-finder") return run_assembler_finder(o);
+    if (o.tool == "fmt-visualizer") return run_fmt_visualizer(o);
     if (o.tool != "environment-finder")
         throw Error("Tool '" + o.tool + "' is not part of this build: only environment-finder, kmer-counter, environment-finder-multi, "
-                    "reads-classifier, triple-reads-classifier, recipient-visualiser, environment-assembler-finder and seq-cov are");
+                    "reads-classifier, triple-reads-classifier, recipient-visualiser, environment-assembler-finder, fmt-visualizer and seq-cov are");
     if (o.k < 0) throw Error("Parameter 'k' is mandatory");
     if (o.seq.empty()) throw Error("Parameter 'seq' is mandatory");
     if (o.output.empty()) throw Error("Parameter 'output' is mandatory");

@@ -806,4 +806,34 @@ __device__ __forceinline__ int table_get(const TableView &t, uint64_t key)
     return -1;
 }
 
+// table_get answering WHERE (components.hip): the key's slot when its count is above 0 (*count: as stored), `beside` for the hash key
+// that is counted beside the table, TABLE_NOWHERE otherwise.  The probing loop is table_get's above, line for line: a change to the
+// probing rule goes into both (and into multi_table.h probe_behind_home).
+constexpr unsigned long long TABLE_NOWHERE = ~0ull;
+template <int MODE>
+__device__ __forceinline__ unsigned long long table_locate(const TableView &t, uint64_t key, unsigned long long beside, uint32_t *count)
+{
+    if (MODE != KEY_PACKED && key == EMPTY_KEY) {
+        const unsigned long long e = *t.empty_cnt;
+        *count = e > 32767ull ? 32767u : (uint32_t)e;
+        return e ? beside : TABLE_NOWHERE;
+    }
+    uint64_t s = slot_of(t, key);
+    uint64_t base = s & ~(uint64_t)t.rmask;
+    const uint64_t home = s & t.rmask;
+    const uint32_t max_probes = t.rmask + 1 < TABLE_MAX_PROBES ? t.rmask + 1 : TABLE_MAX_PROBES;
+    for (uint32_t hop = 0; hop < TABLE_CHAIN; hop++, base = next_region_base(base, t.rmask, t.n_regions), s = base | home)
+    for (uint32_t probe = 0; probe < max_probes; probe++) {
+        const uint4 raw = *reinterpret_cast<const uint4 *>(t.slots + s);
+        const uint64_t cur = ((uint64_t)raw.y << 32) | raw.x;
+        if (cur == key) {
+            *count = raw.z;
+            return raw.z ? s : TABLE_NOWHERE;
+        }
+        if (cur == EMPTY_KEY) return TABLE_NOWHERE;
+        s = base | ((s + 1) & t.rmask);
+    }
+    return TABLE_NOWHERE;
+}
+
 }  // namespace mc

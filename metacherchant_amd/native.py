@@ -65,6 +65,13 @@ class ReadCov(C.Structure):
     _fields_ = [("sum", C.c_int32), ("covered", C.c_int32), ("last", C.c_int16), ("found", C.c_uint8), ("pad", C.c_uint8)]
 
 
+class _Components(C.Structure):
+    """mc_components_result"""
+    _fields_ = [("n_components", C.c_uint64), ("n_kmers", C.c_uint64), ("comp_offsets", C.POINTER(C.c_uint64)),
+                ("seed_seq", C.POINTER(C.c_uint64)), ("seed_pos", C.POINTER(C.c_uint64)), ("hi", C.POINTER(C.c_uint64)),
+                ("lo", C.POINTER(C.c_uint64)), ("cov", C.POINTER(C.c_int16)), ("device_ms", C.c_double)]
+
+
 READ_COV_DTYPE = np.dtype([("sum", np.int32), ("covered", np.int32), ("last", np.int16), ("found", np.uint8), ("pad", np.uint8)])
 CLASSIFY_CORRECTION = 1  # mc_classify_reads flags: findReadWithCorrection
 LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fingerprint, so distinct reads share one
@@ -86,6 +93,7 @@ EXPORTS = [
     "mc_shard_export", "mc_shard_attach", "mc_shard_detach", "mc_classify_reads", "mc_classify_reads_dev",
     "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev", "mc_seq_coverage", "mc_seq_coverage_dev",
     "mc_kmer_presence", "mc_kmer_presence_dev", "mc_reads_in_set", "mc_reads_in_set_dev",
+    "mc_components", "mc_components_dev", "mc_components_free",
 ]
 
 _LIB = None
@@ -181,6 +189,11 @@ def load():
     if hasattr(L, "mc_reads_in_set"):
         L.mc_reads_in_set.argtypes = [vp, u64p, u64p, u64, u64p, u64p, u64, i32, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
         L.mc_reads_in_set_dev.argtypes = [vp, vp, vp, u64, vp, vp, u64, i32, i32, vp, vp]
+    if hasattr(L, "mc_components"):
+        L.mc_components.argtypes = [vp, u64p, u64p, u64, C.POINTER(_Components)]
+        L.mc_components_dev.argtypes = [vp, vp, vp, u64, C.POINTER(_Components)]
+        L.mc_components_free.argtypes = [C.POINTER(_Components)]
+        L.mc_components_free.restype = None
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -653,6 +666,40 @@ def reads_in_set_dev(context, d_words, d_offsets, n_reads, d_hi, d_lo, n_set, d_
     """mc_reads_in_set_dev: d_hi (may be None when k <= 32) and d_lo hold n_set uint64 each, d_hits 4 bytes a read, d_keep one"""
     context._chk(load().mc_reads_in_set_dev(context._h, _dptr(d_words), _dptr(d_offsets), int(n_reads), _dptr(d_hi), _dptr(d_lo), int(n_set), int(pct),
                                             READS_IN_SET_WEAK_FILTER if weak else 0, _dptr(d_hits), _dptr(d_keep)))
+
+
+def _components_result(r):
+    """the library's arrays as numpy arrays of our own, and the library's freed"""
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+    try:
+        nc, nk = int(r.n_components), int(r.n_kmers)
+        return {"n_components": nc, "n_kmers": nk, "comp_offsets": arr(r.comp_offsets, nc + 1, np.uint64), "seed_seq": arr(r.seed_seq, nc, np.uint64),
+                "seed_pos": arr(r.seed_pos, nc, np.uint64), "hi": arr(r.hi, nk, np.uint64), "lo": arr(r.lo, nk, np.uint64),
+                "cov": arr(r.cov, nk, np.int16), "device_ms": float(r.device_ms)}
+    finally:
+        load().mc_components_free(C.byref(r))
+
+
+def components(context, codes_or_words, offsets, packed=None):
+    """mc_components: the connected components of the table's k-mers (get > 0) that the sequences' windows hold, two keys joined when
+    their k-mers are allNeighbors of each other; components numbered by their first window in scan order (the fmt-visualizer's
+    comp<N>).  Sequences as Context.classify_reads takes reads.  Returns a dict of numpy arrays: comp_offsets (n_components + 1),
+    seed_seq, seed_pos (a component), hi, lo, cov (a member; member comp_offsets[c] is component c's seed window as the read has
+    it), and n_components, n_kmers, device_ms."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = max(len(offsets) - 1, 0)
+    words = Context._words(codes_or_words, offsets, packed)
+    r = _Components()
+    context._chk(load().mc_components(context._h, _p(words, C.c_uint64), _p(offsets, C.c_uint64), n, C.byref(r)))
+    return _components_result(r)
+
+
+def components_dev(context, d_words, d_offsets, n_seqs):
+    """mc_components_dev: the sequences are in device memory; the result comes back as components' does"""
+    r = _Components()
+    context._chk(load().mc_components_dev(context._h, _dptr(d_words), _dptr(d_offsets), int(n_seqs), C.byref(r)))
+    return _components_result(r)
 
 
 def key_owner(key, n_owners):
