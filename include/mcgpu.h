@@ -524,6 +524,44 @@ int mc_components_dev(mc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_se
 int mc_components(mc_ctx *ctx, const uint64_t *words, const uint64_t *seq_offsets, uint64_t n_seqs, mc_components_result *out);
 void mc_components_free(mc_components_result *r);
 
+/* ---- unitigs: the state that the reference's unitig compaction ends in (initializeStructures + doMerge of
+ * src/algo/OneSequenceCalculator.java:387-451, SeqEnvCalculator and KmerEnvCalculator alike), from link analysis.
+ * Input: n oriented packed k-mers in the layout of mc_kmer_presence (hi may be NULL when k <= 32) in the subgraph's iteration order,
+ * and a merge class for each (the caller folds colour and is_gene into it).  Entry e makes node 2e (the k-mer as given) and node
+ * 2e + 1 (its reverse complement).  k is the context's; its key mode and its table play no part.
+ *   neighbours(p)  the nodes whose (k-1)-prefix is the (k-1)-suffix of node p ^ 1, ascending: deg[p] of them (at most 5: four
+ *                  successor strings, of which one may be a palindrome that both its nodes spell), in nbr one list after another;
+ *   link p -- q    neighbours(p) = {q}, neighbours(q) = {p}, and the classes of their entries are equal: what doMerge merges.  A node
+ *                  has at most one, so links tie entries into chains, open or closed;
+ *   irregular      a closed chain, or one with a link where q == p (a hairpin) or q == p ^ 1 (a self-loop).  (An entry that is its own
+ *                  reverse complement has no link: both its nodes spell it, so whatever it follows has two neighbours.)  Only there
+ *                  does the loop's result depend on its scan order: the entries of such chains are listed in `irregular`,
+ *                  ascending, and left to the caller;
+ *   unitig         a regular chain of m >= 2 entries, oriented nodes a_1 -> ... -> a_m spelling S (m + k - 1 bases).  The loop leaves
+ *                  a_1 alive with label S and rc = a_m ^ 1, a_m ^ 1 alive with label rc(S) and rc = a_1, every other node of the chain
+ *                  deleted, no neighbours list changed.  A chain is listed once, read from that end where first < last_rc, by
+ *                  ascending first; bases holds S from base_offsets[u] on, packed as reads are, every unitig starting a new word.
+ * Nodes of entries that are in no unitig and not irregular stay as they are.  The result is a function of the input alone.
+ * Errors: MC_EINVAL for null pointers (hi at k <= 32 excepted), n >= 2^30, or two entries that are the same k-mer or each other's
+ * reverse complement.  n == 0 is MC_OK with an empty result (base_offsets = {0}).  *out is zeroed on an error.  Free a result with
+ * mc_unitigs_free (NULL and zeroed results are fine).  mc_unitigs takes host pointers, mc_unitigs_dev device ones; the result is on
+ * the host in both. */
+typedef struct {
+    uint64_t n_nodes;                 /* 2 * n */
+    uint8_t  *deg;                    /* per node: length of its neighbours list */
+    uint32_t *nbr;                    /* the lists one after another in node order, each ascending */
+    uint64_t n_unitigs;               /* regular chains of >= 2 entries, by ascending `first` */
+    uint32_t *first, *last_rc;        /* a_1 and a_m ^ 1 */
+    uint64_t *base_offsets;           /* n_unitigs + 1, in bases, each a multiple of 32 */
+    uint64_t *bases;                  /* S of every unitig, packed as reads are (A0 G1 C2 T3, first base most significant) */
+    uint64_t n_irregular;
+    uint32_t *irregular;              /* entries of irregular chains, ascending; untouched by the call */
+    double device_ms;                 /* summed device time of the passes (HIP events) */
+} mc_unitigs_result;  /* (not mc_unitigs: C has one name space for typedefs and functions) */
+int mc_unitigs_dev(mc_ctx *ctx, const uint64_t *d_hi, const uint64_t *d_lo, const uint8_t *d_cls, uint64_t n, mc_unitigs_result *out);
+int mc_unitigs(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint8_t *cls, uint64_t n, mc_unitigs_result *out);
+void mc_unitigs_free(mc_unitigs_result *r);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

@@ -1,6 +1,6 @@
 // The library's context and what more than one unit of it needs (host side; private to libmcgpu.so, not include/mcgpu.h).
 //
-// The library is ten units, each defining and launching its own kernels:
+// The library is eleven units, each defining and launching its own kernels:
 //   mcgpu.hip       the table, the key join, the counting pipeline, the context ABI, and the table work of the walk (solid table,
 //                   the check of its "absent" look-ups)
 //   reads_file.hip  the device tokeniser's driver and mc_add_reads_file
@@ -12,9 +12,10 @@
 //   presence.hip    mc_kmer_presence*: which of up to four tables hold each of a list of k-mers, one launch
 //   reads_in_set.hip mc_reads_in_set*: every read's windows against a small exact set of k-mers behind a bit filter in LDS
 //   components.hip  mc_components*: the connected components of the table's k-mers that a set of sequences holds (union-find over slots)
+//   unitigs.hip     mc_unitigs*: what the reference's unitig compaction leaves of a set of k-mers, by link analysis and pointer jumping
 // multi_table.h is what seq_cov.hip and presence.hip share: one key's home slots in several tables, the probing behind them, and the
-// host's checks of a list of contexts.  A function below the "across units" line is what one unit lends another; everything else
-// stays static in its unit.
+// host's checks of a list of contexts; kmer_set.h what reads_in_set.hip and unitigs.hip share: the key and hash of a call's exact
+// set.  A function below the "across units" line is what one unit lends another; everything else stays static in its unit.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -220,6 +220,29 @@ struct BfsPass {
     std::vector<uint8_t> last;
 };
 
+// ---- initializeStructures + doMerge (src/algo/OneSequenceCalculator.java:387-451) over oriented k-mers in node order: entry e makes
+// node 2e (kmers[e]) and node 2e + 1 (its reverse complement); two nodes merge only when cls is equal for their entries.
+struct PictureNode {
+    std::string sequence;
+    bool deleted = false;
+    int rc = 0;                  // index of the reverse-complement node
+    std::vector<int> neighbors;  // successors of rc(this), in node-array order
+};
+// What the loop ends in, from link analysis: the fields of mc_unitigs_result (include/mcgpu.h has the definitions), owned.
+struct UnitigsResult {
+    std::vector<uint8_t> deg;
+    std::vector<uint32_t> nbr, first, last_rc, irregular;
+    std::vector<uint64_t> base_offsets, bases;
+};
+// fills a result for the k-mers and classes given (mc_unitigs on a context, or unitigs_by_links); throws Error
+using Compactor = std::function<void(int k, const std::vector<kmer_t> &kmers, const std::vector<uint8_t> &cls, UnitigsResult &out)>;
+// the host's link analysis: no label is built before the chains are known.  The model of csrc/unitigs.hip.
+void unitigs_by_links(int k, const std::vector<kmer_t> &kmers, const std::vector<uint8_t> &cls, UnitigsResult &out);
+// Without a compactor: the reference's loop on labels, pass after pass over all nodes.  With one: the nodes are built from its result
+// and the same loop runs over the nodes of the irregular entries only.  Alive nodes, `deleted` and the neighbours lists come out
+// the same either way; what a deleted node keeps as label and rc depends on the loop's scan order and is never read.
+std::vector<PictureNode> make_picture(int k, const std::vector<kmer_t> &kmers, const std::vector<uint8_t> &cls, const Compactor *compact = nullptr);
+
 // ---- src/algo/OneSequenceCalculator.java (after the BFS) + src/algo/SingleNode.java +
 // src/io/writers/GFAWriter.java + src/io/writers/TSVWriter.java; with set_colours, src/algo/SeqEnvCalculator.java (after its BFS)
 class Environment {
@@ -253,13 +276,14 @@ public:
     std::vector<kmer_t> kmers() const;
     bool order_guaranteed() const { return !subgraph_.treeified() && !d_treeified_; }
     std::string graph_txt() const;                    // printEnvironment :297-310
-    void create_picture();                            // initializeStructures + doMerge :387-451
+    // initializeStructures + doMerge :387-451 (make_picture; colour and is_gene make the merge class)
+    void create_picture(const Compactor *compact = nullptr);
     std::string seqs_fasta(int chunk_length) const;   // outputNodeSequences :354-385
     std::string graph_gfa() const;                    // GFAWriter.java:47-99
     std::string tsv_nodes() const;                    // TSVWriter.java:35-49
     std::string tsv_edges() const;                    // TSVWriter.java:51-79
     // writes graph.txt (+ the identical env.txt README.md:98 names), seqs.fasta, graph.gfa, tsvs/*
-    void write_all(const std::string &out_prefix, int chunk_length);
+    void write_all(const std::string &out_prefix, int chunk_length, const Compactor *compact = nullptr);
 
 private:
     struct Node {
@@ -270,7 +294,6 @@ private:
         std::vector<int> neighbors;  // successors of rc(this), in node-array order
         Colour colour = NO_COLOUR;
     };
-    void merge_nodes(int first_plus, int second_minus);
     std::string node_id(const Node &n) const;
     int k_;
     std::vector<std::string> genes_;

@@ -11,6 +11,10 @@
 // `mc_hosttest kmers <dump>`: the subgraph's keys of an `env` dump, one a line, as Environment::kmers lists them.
 // `mc_hosttest cutreads <reads file> <keep> <out.fasta> <index>`: the reads whose character in <keep> (one '0' / '1' a read) is '1'
 // through CutReadsWriter.
+// `mc_hosttest unitigs <file>`: unitig compaction both ways.  file: k n / n lines "kmer class" (oriented k-mers in node order).  Prints
+// the link analysis ("U first last_rc bases" a unitig, "I entry" an irregular entry), then the node state of the reference's loop
+// ("O id deleted rc label neighbours") and of the link analysis with the loop over the irregular entries ("N ..."); a deleted node's
+// label and rc print as "-" (they depend on the loop's scan order and are never read).
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -139,9 +143,46 @@ int main(int argc, char **argv)
             printf("%llu\n", (unsigned long long)out.kept());
             return 0;
         }
+        if (argc == 3 && std::string(argv[1]) == "unitigs") {
+            std::ifstream f(argv[2]);
+            if (!f) throw Error("cannot open the k-mer file");
+            int k;
+            size_t n;
+            f >> k >> n;
+            std::vector<kmer_t> kmers(n);
+            std::vector<uint8_t> cls(n);
+            for (size_t i = 0; i < n; i++) {
+                std::string kmer;
+                int c;
+                f >> kmer >> c;
+                if ((int)kmer.size() != k) throw Error("a k-mer of the file is not k long");
+                kmers[i] = pack_kmer128(kmer);
+                cls[i] = (uint8_t)c;
+            }
+            UnitigsResult r;
+            unitigs_by_links(k, kmers, cls, r);
+            for (size_t u = 0; u < r.first.size(); u++) {
+                std::string bases;  // (whole words: the padding prints as A)
+                for (uint64_t i = r.base_offsets[u]; i < r.base_offsets[u + 1]; i++) bases.push_back("AGCT"[(r.bases[i >> 5] >> (62 - 2 * (i & 31))) & 3]);
+                printf("U %u %u %s\n", r.first[u], r.last_rc[u], bases.c_str());
+            }
+            for (const uint32_t e : r.irregular) printf("I %u\n", e);
+            const Compactor by_links = unitigs_by_links;
+            for (int way = 0; way < 2; way++) {
+                const std::vector<PictureNode> nodes = make_picture(k, kmers, cls, way ? &by_links : nullptr);
+                for (size_t i = 0; i < nodes.size(); i++) {
+                    const PictureNode &nd = nodes[i];
+                    std::string nb;
+                    for (const int j : nd.neighbors) nb += (nb.empty() ? "" : ",") + std::to_string(j);
+                    printf("%c %zu %d %s %s [%s]\n", way ? 'N' : 'O', i, nd.deleted ? 1 : 0, nd.deleted ? "-" : std::to_string(nd.rc).c_str(),
+                           nd.deleted ? "-" : nd.sequence.c_str(), nb.c_str());
+                }
+            }
+            return 0;
+        }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

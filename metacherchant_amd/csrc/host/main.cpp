@@ -19,6 +19,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -26,6 +27,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "envfinder.h"
+#include "gpu_compactor.h"
 #include "mcgpu.h"
 
 using namespace mch;
@@ -95,6 +97,9 @@ struct Options {
     // --tool environment-assembler-finder (src/tools/EnvironmentAssemblerFinder.java:33-122)
     long long procfiltration = 1;
     std::string assembler, assemblerpath;
+    // --compact: who compacts an environment's k-mers into unitigs (no counterpart in the reference; the files are the same)
+    std::string compact = "auto";
+    bool compact_given = false;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -107,6 +112,7 @@ const OptSpec SPECS[] = {
     {"merge", nullptr, 1}, {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0},
     {"continue", "c", 1}, {"force", nullptr, 1}, {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0},
     {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"output-dir", nullptr, 0}, {"env", "e", 2}, {"geneid", "g", 0},
+    {"compact", nullptr, 0},
 };
 
 // --tool reads-classifier: its parameters (ReadsClassifier.java:42-95) and the launch options
@@ -139,7 +145,7 @@ const OptSpec RECIPIENT_SPECS[] = {
     {"k", "k", 0}, {"after-files", "after", 2}, {"seq", "seq", 0}, {"maxkmers", nullptr, 0}, {"maxradius", nullptr, 0}, {"hash", nullptr, 0},
     {"output-dir", "o", 0}, {"input-dir", "i", 0}, {"ext", "ext", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0},
 };
 
 // --tool fmt-visualizer: its parameters (FMTVisualizer.java:39-85) and the launch options
@@ -147,7 +153,7 @@ const OptSpec FMT_SPECS[] = {
     {"k", "k", 0}, {"donor-files", "donor", 2}, {"before-files", "before", 2}, {"after-files", "after", 2}, {"hash", nullptr, 0},
     {"output-dir", "o", 0}, {"input-dir", "i", 0}, {"ext", "ext", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0},
 };
 
 // --tool environment-assembler-finder: its parameters (EnvironmentAssemblerFinder.java:33-122) and the launch options
@@ -156,7 +162,7 @@ const OptSpec ASSEMBLER_SPECS[] = {
     {"coverage", nullptr, 0}, {"bothdirs", nullptr, 1}, {"chunklength", nullptr, 0}, {"forcehash", nullptr, 1}, {"hash", nullptr, 0},
     {"threads", nullptr, 0}, {"trim", nullptr, 1}, {"procfiltration", "pf", 0}, {"assembler", nullptr, 0}, {"assemblerpath", nullptr, 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0},
 };
 
 struct SpecTable {
@@ -274,6 +280,11 @@ Options parse_args(int argc, char **argv)
     if (auto v = val("threads")) (void)parse_int("threads", *v);  // (accepted, unused: the filter is one launch a batch)
     if (auto v = val("assembler")) o.assembler = *v;
     if (auto v = val("assemblerpath")) o.assemblerpath = *v;
+    if (auto v = val("compact")) {
+        if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--compact takes host, gpu or auto, not '" + *v + "'");
+        o.compact = *v;
+        o.compact_given = true;
+    }
     if (auto v = val("seq")) o.seq = *v;
     if (auto v = val("hicseq")) o.hicseq = *v;
     if (auto v = val("output")) o.output = *v;
@@ -407,6 +418,9 @@ void usage()
     puts("                --device <n> (GPU ordinal), --devices <a,b,...|a-b> (several GPUs as one table: reads dealt to them,");
     puts("                k-mers exchanged by owner over xGMI, BFS on the first), --capacity-hint <distinct k-mers>");
     puts("                (sizes the table once; with -k 33..63 every batch then travels as super-k-mer records, not only the first)");
+    puts("                --compact host|gpu|auto (environment-finder, environment-assembler-finder, recipient-visualiser, fmt-visualizer:");
+    puts("                who compacts an environment's k-mers into unitigs; the files are the same; default auto: the GPU from");
+    puts("                10000 k-mers on, the smallest size measured, where it already wins; the host below)");
 }
 
 #define MC_CHECK(ctx, call)                                                       \
@@ -467,6 +481,42 @@ struct Engine {
     void bfs_batch(const mc_bfs_job *jobs, uint32_t n, int cov, int64_t mk, int64_t mr, mc_bfs_result *out)
     {
         check(g ? mc_group_bfs_batch(g, jobs, n, cov, mk, mr, out) : mc_bfs_batch(c, jobs, n, cov, mk, mr, out));
+    }
+};
+
+// --compact: the unitig compaction of an environment on the host (Environment::create_picture's loop on labels), on the GPU (mc_unitigs
+// on a context of the run; the host then only runs the loop over the entries of irregular chains), or `auto`, the default: on the GPU
+// from COMPACT_AUTO_MIN k-mers on.  That is the smallest size scripts/unitigs_bench.py has timed, and there the GPU's way already
+// takes less than half the host's time, as at every larger size; nobody has measured below it, so the host keeps those.
+constexpr size_t COMPACT_AUTO_MIN = 10000;
+struct Compaction {
+    std::string mode;
+    const Options &o;
+    int k;
+    mc_ctx *ctx = nullptr;
+    CtxGuard own;  // (a group has no context of its own to lend: one more, with an empty table, on the first device, when first needed)
+    Compactor gpu;
+    std::mutex mu;
+    Compaction(const Options &o, const Engine &e, int k) : mode(o.compact), o(o), k(k), ctx(e.c) {}
+    // the compactor for an environment of n k-mers (NULL: the host's loop), named in the log
+    const Compactor *pick(size_t n, const std::string &what)
+    {
+        const bool on_gpu = mode == "gpu" || (mode == "auto" && n >= COMPACT_AUTO_MIN);
+        std::lock_guard<std::mutex> g(mu);
+        info("Compacting " + what + " (" + std::to_string(n) + " k-mers) on the " + (on_gpu ? "GPU (mc_unitigs)" : "host"));
+        if (!on_gpu) return nullptr;
+        if (!gpu) {
+            if (!ctx) {
+                mc_config cfg{};
+                cfg.k = k;
+                cfg.key_mode = MC_KEY_POLY;
+                cfg.device = o.devices.empty() ? o.device : o.devices[0];
+                if (mc_create(&cfg, &own.c) != MC_OK) throw Error(std::string(mc_last_error(nullptr)));
+                ctx = own.c;
+            }
+            gpu = gpu_compactor(ctx);
+        }
+        return &gpu;
     }
 };
 
@@ -1141,6 +1191,7 @@ int run_recipient_visualiser(const Options &o)
     MC_CHECK(G.c, mc_trim(G.c));
     mc_ctx *tables[4];
     cfg.capacity_hint = 0;
+    Compaction compaction(o, G, o.k);
     for (int t = 0; t < 4; t++) {
         E[t].open(cfg, {});
         tables[t] = E[t].c;
@@ -1247,7 +1298,7 @@ int run_recipient_visualiser(const Options &o)
             Environment &env = *envs[j];
             info("Extending endings by " + std::to_string(Environment::extensions(outside[j], in_graph.data() + oat[j])) + " kmers");
             env.set_colours([&](kmer_t kmer) { return Environment::colour_of_mask(mask_of[j].at(kmer)); });
-            env.create_picture();
+            env.create_picture(compaction.pick(env.size(), "comp_" + std::to_string(s0 + j)));
             const std::string name = out_dir + "/comp_" + std::to_string(s0 + j);
             write_file(name + "_seqs.fasta", env.seqs_fasta(0));  // (no chunk-length filter here: SeqEnvCalculator.java:258)
             write_file(name + ".gfa", env.graph_gfa());
@@ -1322,6 +1373,7 @@ void fmt_phase(const Options &o, int mode, const std::string &name, const std::v
     load_reads(files, G);
     MC_CHECK(G.c, mc_trim(G.c));
     mc_ctx *tables[4] = {};
+    Compaction compaction(o, G, o.k);
     cfg.capacity_hint = 0;
     for (uint32_t t = 0; t < nt; t++) {
         E[t].open(cfg, {});
@@ -1378,7 +1430,7 @@ void fmt_phase(const Options &o, int mode, const std::string &name, const std::v
                     // getDonorColorNode / getBeforeColorNode (:195-207): bit 0 the found class (settle, stay), bit 1 the other
                     return m == 1 ? Environment::GREEN : m == 2 ? Environment::BLUE : m == 3 ? Environment::GREY : Environment::BLACK;
                 });
-                env.create_picture();
+                env.create_picture(compaction.pick(env.size(), "comp" + std::to_string(c)));
                 const std::string file = out_dir + "/comp" + std::to_string(c);
                 write_file(file + "_seqs.fasta", env.seqs_fasta(1));
                 write_file(file + ".gfa", env.graph_gfa());
@@ -1523,6 +1575,7 @@ bool assembler_finder_phase(const Options &o, int k, int coverage, const std::ve
     cfg.capacity_hint = o.capacity_hint;
     Engine E;
     E.open(cfg, {});
+    Compaction compaction(o, E, k);
     E.set_coverage_hint(coverage);
     load_reads(reads, E);
 
@@ -1583,7 +1636,7 @@ bool assembler_finder_phase(const Options &o, int k, int coverage, const std::ve
         if (!env.order_guaranteed())
             logline("WARN", "--trim removed k-mers from a treeified java.util.HashMap bin: line order of " + prefix + " may differ from the JVM's inside that bin");
         members = env.kmers();
-        env.write_all(prefix, o.chunklength);
+        env.write_all(prefix, o.chunklength, compaction.pick(env.size(), prefix));
     }
 
     // the set goes up once; every file's reads stream through in batches
@@ -1655,6 +1708,8 @@ int run_assembler_finder(const Options &o)
 
 int run(const Options &o)
 {
+    if (o.compact_given && (o.tool == "kmer-counter" || o.tool == "environment-finder-multi"))  // (they share environment-finder's table)
+        throw Error("--compact does not apply to --tool " + o.tool);
     if (o.tool == "kmer-counter") return run_kmer_counter(o);
     if (o.tool == "environment-finder-multi") return run_multi(o);
     if (o.tool == "reads-classifier") return run_reads_classifier(o);
@@ -1697,6 +1752,7 @@ int run(const Options &o)
     cfg.capacity_hint = o.capacity_hint;
     Engine E;
     E.open(cfg, o.devices);
+    Compaction compaction(o, E, o.k);
     if (!o.devices.empty()) info("Counting on " + std::to_string(o.devices.size()) + " devices");
     E.set_coverage_hint(o.coverage);
 
@@ -1798,7 +1854,7 @@ int run(const Options &o)
             if (!env.order_guaranteed())
                 logline("WARN", "--trim removed k-mers from a treeified java.util.HashMap bin: line order of " + calcs[c].out_prefix +
                                 " may differ from the JVM's inside that bin");
-            env.write_all(calcs[c].out_prefix, o.chunklength);
+            env.write_all(calcs[c].out_prefix, o.chunklength, compaction.pick(env.size(), calcs[c].out_prefix));
         }
         out_ms += ms_between(tb1, std::chrono::steady_clock::now());
     }

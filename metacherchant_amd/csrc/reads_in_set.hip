@@ -19,6 +19,7 @@
 // every window goes to the table.  DESIGN.md "reads-in-set" has the sizes and the registers,
 // tests/test_reads_in_set_kernel_resources.py holds the kernels to them.
 #include "context.h"
+#include "kmer_set.h"  // RsKey, rs_key, rs_hash, rs_home: shared with unitigs.hip
 
 namespace {
 
@@ -29,41 +30,9 @@ constexpr int RS_FILTER_WORDS_LG = 14;            // 2^14 words of 64 bits: 128 
 constexpr int RS_FILTER_WORDS = 1 << RS_FILTER_WORDS_LG;
 constexpr uint64_t RS_FILTER_MAX_SET = 1ull << 19;  // more k-mers than this: over a third of the windows would pass, no filter
 constexpr int RS_BUILD_THREADS = 256;
-constexpr uint64_t RS_EMPTY = ~0ull;              // no canonical k-mer's word (see RsKey)
-
-// A canonical k-mer as the table holds it.  k <= 32: the k-mer itself in `a` (all ones is never canonical: its reverse
-// complement is 0).  k > 32: the 2k <= 126 bits as two words that can never be all ones either: a = hi : top bit of lo (at most 63
-// bits), b = lo without its top bit.  Each word then has its own "empty" mark, and the build needs no 128-bit atomic.
-struct RsKey {
-    uint64_t a, b;
-};
-
-// (the four words by value: a choice between two structs by reference is a choice between two addresses, and puts both in scratch)
-template <bool WIDE>
-__device__ __forceinline__ RsKey rs_key(uint64_t fw_hi, uint64_t fw_lo, uint64_t rc_hi, uint64_t rc_lo)
-{
-    if (!WIDE) return RsKey{min(fw_lo, rc_lo), 0};
-    const bool f = fw_hi < rc_hi || (fw_hi == rc_hi && fw_lo <= rc_lo);
-    const uint64_t hi = f ? fw_hi : rc_hi, lo = f ? fw_lo : rc_lo;
-    return RsKey{(hi << 1) | (lo >> 63), lo & ~(1ull << 63)};
-}
-
-// 32 mixed bits of a key: the filter takes all of them (14 for the word, 3 x 6 for the bits), the table the top bits of a multiple
-template <bool WIDE>
-__device__ __forceinline__ uint32_t rs_hash(const RsKey &key)
-{
-    uint32_t h = (uint32_t)key.a ^ ((uint32_t)(key.a >> 32) * 0x85ebca6bu);
-    if (WIDE) h ^= ((uint32_t)key.b * 0xc2b2ae35u) ^ ((uint32_t)(key.b >> 32) * 0x27d4eb2fu);
-    h ^= h >> 16;
-    h *= 0x7feb352du;
-    h ^= h >> 15;
-    h *= 0x846ca68bu;
-    return h ^ (h >> 16);
-}
 
 __device__ __forceinline__ uint64_t rs_filter_bits(uint32_t h) { return (1ull << (h & 63)) | (1ull << ((h >> 6) & 63)) | (1ull << ((h >> 12) & 63)); }
 __device__ __forceinline__ uint32_t rs_filter_word(uint32_t h) { return h >> (32 - RS_FILTER_WORDS_LG); }
-__device__ __forceinline__ uint64_t rs_home(uint32_t h, int lg_cap) { return (uint64_t)((h * 0x9e3779b1u) >> (32 - lg_cap)); }
 
 // table: 2^lg_cap slots of one word (k <= 32) or two (above), all ones when the call starts; filter: RS_FILTER_WORDS words, zero
 template <bool WIDE>

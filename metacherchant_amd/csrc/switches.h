@@ -36,6 +36,7 @@ struct mc_switches {
     bool bfs_stats = false;                   // MC_BFS_STATS=1: walk statistics on stderr
     // diagnostics
     bool ingest_debug = false;                // MC_INGEST_DEBUG=1: what the counting and reading paths decided, on stderr
+    bool unitigs_stats = false;               // MC_UNITIGS_STATS=1: device time of every pass of mc_unitigs on stderr, a line a call
     // mc_group
     bool group_gather_reads = true;           // MC_EXCHANGE_GATHER_READS=0: the other devices' records carry no pointers
     int group_transport = 0;                  // MC_GROUP_TRANSPORT=rccl|peer: 1 | 2; 0: as the config's flags say
@@ -68,6 +69,7 @@ inline mc_switches read_switches()
     if (const char *e = getenv("MC_BFS_TRACE_DUMP")) s.bfs_trace_dump = e;
     s.bfs_stats = getenv("MC_BFS_STATS") != nullptr;
     s.ingest_debug = getenv("MC_INGEST_DEBUG") != nullptr;
+    s.unitigs_stats = getenv("MC_UNITIGS_STATS") != nullptr;
     s.group_gather_reads = !off("MC_EXCHANGE_GATHER_READS");
     if (const char *e = getenv("MC_GROUP_TRANSPORT")) s.group_transport = !strcmp(e, "rccl") ? 1 : !strcmp(e, "peer") ? 2 : 0;
     if (const char *e = getenv("MC_GROUP_BATCH_READS")) if (*e) s.group_batch_reads = std::max<uint64_t>(strtoull(e, nullptr, 10), 1024);

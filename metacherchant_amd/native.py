@@ -72,6 +72,13 @@ class _Components(C.Structure):
                 ("lo", C.POINTER(C.c_uint64)), ("cov", C.POINTER(C.c_int16)), ("device_ms", C.c_double)]
 
 
+class _Unitigs(C.Structure):
+    """mc_unitigs_result"""
+    _fields_ = [("n_nodes", C.c_uint64), ("deg", C.POINTER(C.c_uint8)), ("nbr", C.POINTER(C.c_uint32)), ("n_unitigs", C.c_uint64),
+                ("first", C.POINTER(C.c_uint32)), ("last_rc", C.POINTER(C.c_uint32)), ("base_offsets", C.POINTER(C.c_uint64)),
+                ("bases", C.POINTER(C.c_uint64)), ("n_irregular", C.c_uint64), ("irregular", C.POINTER(C.c_uint32)), ("device_ms", C.c_double)]
+
+
 READ_COV_DTYPE = np.dtype([("sum", np.int32), ("covered", np.int32), ("last", np.int16), ("found", np.uint8), ("pad", np.uint8)])
 CLASSIFY_CORRECTION = 1  # mc_classify_reads flags: findReadWithCorrection
 LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fingerprint, so distinct reads share one
@@ -93,7 +100,7 @@ EXPORTS = [
     "mc_shard_export", "mc_shard_attach", "mc_shard_detach", "mc_classify_reads", "mc_classify_reads_dev",
     "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev", "mc_seq_coverage", "mc_seq_coverage_dev",
     "mc_kmer_presence", "mc_kmer_presence_dev", "mc_reads_in_set", "mc_reads_in_set_dev",
-    "mc_components", "mc_components_dev", "mc_components_free",
+    "mc_components", "mc_components_dev", "mc_components_free", "mc_unitigs", "mc_unitigs_dev", "mc_unitigs_free",
 ]
 
 _LIB = None
@@ -194,6 +201,11 @@ def load():
         L.mc_components_dev.argtypes = [vp, vp, vp, u64, C.POINTER(_Components)]
         L.mc_components_free.argtypes = [C.POINTER(_Components)]
         L.mc_components_free.restype = None
+    if hasattr(L, "mc_unitigs"):
+        L.mc_unitigs.argtypes = [vp, u64p, u64p, C.POINTER(C.c_uint8), u64, C.POINTER(_Unitigs)]
+        L.mc_unitigs_dev.argtypes = [vp, vp, vp, vp, u64, C.POINTER(_Unitigs)]
+        L.mc_unitigs_free.argtypes = [C.POINTER(_Unitigs)]
+        L.mc_unitigs_free.restype = None
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -582,6 +594,14 @@ class Context:
         """mc_trim: the counting pipeline's scratch and the pools' idle blocks go back to the driver."""
         self._chk(self._L.mc_trim(self._h))
 
+    def unitigs(self, hi, lo, cls):
+        """mc_unitigs: see the module's unitigs()"""
+        return unitigs(self, hi, lo, cls)
+
+    def unitigs_dev(self, d_hi, d_lo, d_cls, n):
+        """mc_unitigs_dev: see the module's unitigs_dev()"""
+        return unitigs_dev(self, d_hi, d_lo, d_cls, n)
+
     def synth_reads_dev(self, genome_seed, n_contigs, contig_len, read_seed, first_read, n_reads, read_len,
                         err_per_10k, d_words, d_offsets):
         self._chk(self._L.mc_synth_reads_dev(self._h, genome_seed, n_contigs, contig_len, read_seed, first_read,
@@ -700,6 +720,47 @@ def components_dev(context, d_words, d_offsets, n_seqs):
     r = _Components()
     context._chk(load().mc_components_dev(context._h, _dptr(d_words), _dptr(d_offsets), int(n_seqs), C.byref(r)))
     return _components_result(r)
+
+
+def _unitigs_result(r):
+    """the library's arrays as numpy arrays of our own, and the library's freed"""
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+    try:
+        nn, nu, ni = int(r.n_nodes), int(r.n_unitigs), int(r.n_irregular)
+        deg = arr(r.deg, nn, np.uint8)
+        off = arr(r.base_offsets, nu + 1, np.uint64)
+        return {"n_nodes": nn, "deg": deg, "nbr": arr(r.nbr, int(deg.sum(dtype=np.uint64)), np.uint32), "n_unitigs": nu,
+                "first": arr(r.first, nu, np.uint32), "last_rc": arr(r.last_rc, nu, np.uint32), "base_offsets": off,
+                "bases": arr(r.bases, int(off[nu]) // 32, np.uint64), "n_irregular": ni, "irregular": arr(r.irregular, ni, np.uint32),
+                "device_ms": float(r.device_ms)}
+    finally:
+        load().mc_unitigs_free(C.byref(r))
+
+
+def unitigs(context, hi, lo, cls):
+    """mc_unitigs: what the reference's unitig compaction (initializeStructures + doMerge) leaves of the oriented packed k-mers
+    (hi << 64 | lo in the subgraph's iteration order; hi may be None when k <= 32) with merge classes cls (uint8).  Entry e makes
+    nodes 2e and 2e + 1 (its reverse complement).  Returns a dict of numpy arrays: deg (a node) and nbr (the neighbours lists one after
+    another), first, last_rc and base_offsets (n_unitigs + 1, in bases) of the unitigs with their packed bases, irregular (the entries
+    of chains whose result depends on the loop's scan order, left to the caller), and n_nodes, n_unitigs, n_irregular, device_ms.
+    Needs no table."""
+    lo = np.ascontiguousarray(lo, dtype=np.uint64)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64) if hi is not None else None
+    cls = np.ascontiguousarray(cls, dtype=np.uint8)
+    if (hi is not None and len(hi) != len(lo)) or len(cls) != len(lo):
+        raise ValueError("hi, lo and cls need one entry a k-mer")
+    r = _Unitigs()
+    context._chk(load().mc_unitigs(context._h, _p(hi, C.c_uint64) if hi is not None else None, _p(lo, C.c_uint64), _p(cls, C.c_uint8), len(lo),
+                                   C.byref(r)))
+    return _unitigs_result(r)
+
+
+def unitigs_dev(context, d_hi, d_lo, d_cls, n):
+    """mc_unitigs_dev: d_hi (may be None when k <= 32) and d_lo hold n uint64 each, d_cls n bytes; the result comes back as unitigs' does"""
+    r = _Unitigs()
+    context._chk(load().mc_unitigs_dev(context._h, _dptr(d_hi), _dptr(d_lo), _dptr(d_cls), int(n), C.byref(r)))
+    return _unitigs_result(r)
 
 
 def key_owner(key, n_owners):
