@@ -15,6 +15,9 @@
 // the link analysis ("U first last_rc bases" a unitig, "I entry" an irregular entry), then the node state of the reference's loop
 // ("O id deleted rc label neighbours") and of the link analysis with the loop over the irregular entries ("N ..."); a deleted node's
 // label and rc print as "-" (they depend on the loop's scan order and are never read).
+// `mc_hosttest placement <k>`: where the table puts a key (csrc/kmer_hash.h, the functions the kernels compile).  Reads hexadecimal
+// 64-bit words from stdin, one a line, and prints for each "fmix64 sk_order sk_bin sk_hmin_of_kmer": the hash of the word as a key, the
+// order and the bin of its low 32 bits, and the smallest order among the SK_M-mers of the word as a packed k-mer of k bases.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -22,6 +25,7 @@
 #include <iostream>
 #include <map>
 
+#include "../kmer_hash.h"
 #include "envfinder.h"
 
 using namespace mch;
@@ -143,6 +147,15 @@ int main(int argc, char **argv)
             printf("%llu\n", (unsigned long long)out.kept());
             return 0;
         }
+        if (argc == 3 && std::string(argv[1]) == "placement") {
+            const int k = atoi(argv[2]);
+            if (k < mc::SK_M || k > 32) throw Error("placement: k from 15 to 32");
+            unsigned long long w;
+            while (scanf("%llx", &w) == 1)
+                printf("%llx %x %x %x\n", (unsigned long long)mc::fmix64(w), mc::sk_order((uint32_t)w), mc::sk_bin((uint32_t)w),
+                       mc::sk_hmin_of_kmer(k < 32 ? w & ((1ull << (2 * k)) - 1) : w, k));
+            return 0;
+        }
         if (argc == 3 && std::string(argv[1]) == "unitigs") {
             std::ifstream f(argv[2]);
             if (!f) throw Error("cannot open the k-mer file");
@@ -182,7 +195,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kmer_hash.h"  // fmix64, rc_packed, sk_order, sk_bin, sk_hmin_of_kmer: the part a host compiler can read too
+
 namespace mc {
 
 constexpr int KEY_PACKED = 0, KEY_POLY = 1, KEY_FNV1A = 2;
@@ -14,14 +16,6 @@ struct Kmer {  // oriented k-mer, 2k bits right-aligned in 128, first base most 
     uint64_t hi, lo;
 };
 
-__host__ __device__ constexpr __forceinline__ uint64_t fmix64(uint64_t x)
-{
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
-
 // SplitMix64, n-th output of the generator seeded with `seed` (DESIGN.md "Synthetic workload")
 __host__ __device__ __forceinline__ uint64_t splitmix(uint64_t seed, uint64_t n)
 {
@@ -29,25 +23,6 @@ __host__ __device__ __forceinline__ uint64_t splitmix(uint64_t seed, uint64_t n)
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
-}
-
-// itmo!/utils/KmerUtils.java:12-22 reverseComplement(kmer, k): reverse the 2-bit groups,
-// complement, right-align.  v_bfrev reverses single bits, so swap the bits of each pair back.
-__host__ __device__ __forceinline__ uint64_t rc_packed(uint64_t x, int k)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint64_t r = __brevll(x);
-#else
-    uint64_t r = x;
-    r = ((r & 0x5555555555555555ull) << 1) | ((r >> 1) & 0x5555555555555555ull);
-    r = ((r & 0x3333333333333333ull) << 2) | ((r >> 2) & 0x3333333333333333ull);
-    r = ((r & 0x0f0f0f0f0f0f0f0full) << 4) | ((r >> 4) & 0x0f0f0f0f0f0f0f0full);
-    r = ((r & 0x00ff00ff00ff00ffull) << 8) | ((r >> 8) & 0x00ff00ff00ff00ffull);
-    r = ((r & 0x0000ffff0000ffffull) << 16) | ((r >> 16) & 0x0000ffff0000ffffull);
-    r = (r << 32) | (r >> 32);
-#endif
-    r = ((r & 0x5555555555555555ull) << 1) | ((r >> 1) & 0x5555555555555555ull);
-    return (~r) >> (64 - 2 * k);
 }
 
 __host__ __device__ __forceinline__ uint32_t base_at(const Kmer &v, int k, int i)
@@ -396,50 +371,13 @@ struct Slot {
 // minimizer, which is what lets the counting pipeline move "super-k-mers" (a run of windows in one
 // 16-byte record) instead of one record per window (count_pipeline.h).  Nothing of this reaches a
 // result: it only decides where in the table a key lives.
-constexpr int SK_M = 15;
-constexpr int SK_MIN_K = 23;  // shorter k-mers: runs too short to pay; regions from fmix64(key) as for hash keys
-constexpr uint32_t SK_MMASK = (1u << (2 * SK_M)) - 1;
-constexpr uint32_t SK_NONE = 0xFFFFFFFFu;  // "no window here" in arrays of minimizer hashes
-
-__host__ __device__ __forceinline__ uint32_t sk_order(uint32_t canon_mmer)
-{  // a bijection of 32-bit words: random-looking total order of the SK_M-mers (ties impossible below 2^30).  It never gives
-   // SK_NONE for an SK_M-mer: the one word it maps there is 0xCCFF8DF3, and canonical 15-mers are below 2^30 (round 3 tested
-   // every hash against it: two of the thirteen instructions a base position costs the extraction kernel)
-    uint32_t x = canon_mmer * 0x9E3779B1u;
-    x ^= x >> 15;
-    return x;
-}
-static_assert(SK_M == 15, "sk_order's image of the SK_M-mers must not hold SK_NONE: check again for another SK_M");
-__host__ __device__ __forceinline__ uint32_t sk_bin(uint32_t hmin)
-{  // the minimum of many hashes is small: mix again before taking top bits as a bin number
-    uint32_t x = hmin;
-    x ^= x >> 16; x *= 0x7FEB352Du;
-    x ^= x >> 15; x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
+// (SK_M and its constants, sk_order, sk_bin and sk_hmin_of_kmer are in kmer_hash.h.)
 // owner rank of everything that shares a minimizer (multi-GPU split): mixed differently from sk_bin, so that
 // the keys one rank owns still spread over all regions of its table
 __host__ __device__ __forceinline__ uint32_t sk_owner(uint32_t hmin, uint32_t n_owners)
 {
     return sk_bin(hmin ^ 0x5BD1E995u) % n_owners;
 }
-__host__ __device__ __forceinline__ uint32_t sk_rc_mmer(uint32_t x)
-{
-    return (uint32_t)rc_packed((uint64_t)x, SK_M);
-}
-// smallest sk_order over the canonical SK_M-mers of a k-mer (either strand gives the same value)
-__host__ __device__ inline uint32_t sk_hmin_of_kmer(uint64_t fw, int k)
-{
-    uint32_t best = SK_NONE;
-    for (int i = 0; i + SK_M <= k; i++) {
-        const uint32_t f = (uint32_t)(fw >> (2 * (k - SK_M - i))) & SK_MMASK, r = sk_rc_mmer(f);
-        const uint32_t h = sk_order(f < r ? f : r);
-        best = h < best ? h : best;
-    }
-    return best;
-}
-
 // ... of a k-mer of up to 64 bases (hi:lo, right-aligned).  Hash keys say nothing about their bases: where such keys live in
 // minimizer bins (k > 32 with polynomial keys, count_pipeline.h "long records") every look-up brings the k-mer itself.
 __host__ __device__ inline uint32_t sk_hmin_of_kmer2(const Kmer &v, int k, bool two = false)
@@ -807,8 +745,10 @@ __device__ __forceinline__ int table_get(const TableView &t, uint64_t key)
 }
 
 // table_get answering WHERE (components.hip): the key's slot when its count is above 0 (*count: as stored), `beside` for the hash key
-// that is counted beside the table, TABLE_NOWHERE otherwise.  The probing loop is table_get's above, line for line: a change to the
-// probing rule goes into both (and into multi_table.h probe_behind_home).
+// that is counted beside the table, TABLE_NOWHERE otherwise.  The probing loop is table_get's above, line for line.  A change to the
+// probing rule goes into every copy by hand: table_add_at and the merge kernel (count_pipeline.h) that place the keys, table_get,
+// this one, multi_table.h probe_behind_home, solid_probe_from above and the builder of the solid copy (mcgpu.hip k_solid_from_leaves).
+// tests/test_gpu_crowded_lookups.py runs all of them over regions that hold more keys than slots and holds them together.
 constexpr unsigned long long TABLE_NOWHERE = ~0ull;
 template <int MODE>
 __device__ __forceinline__ unsigned long long table_locate(const TableView &t, uint64_t key, unsigned long long beside, uint32_t *count)
