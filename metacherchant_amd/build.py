@@ -102,7 +102,7 @@ def build_host(force=False, verbose=False):
     common = [os.path.join(hdir, "envfinder.cpp")]
     hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "gpu_compactor.h"), os.path.join(ROOT, "include", "mcgpu.h")]
     flags = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")]
-    if force or _stale(HOSTTEST, common + hdrs + [os.path.join(hdir, "hosttest.cpp"), os.path.join(CSRC, "kmer_hash.h")]):
+    if force or _stale(HOSTTEST, common + hdrs + [os.path.join(hdir, "hosttest.cpp"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h")]):
         cmd = ["g++"] + flags + ["-o", HOSTTEST, os.path.join(hdir, "hosttest.cpp")] + common + ["-lz", "-ldl"]
         if verbose:
             print(" ".join(cmd))
@@ -146,7 +146,7 @@ def build_host_sanitized(kind, force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     out = os.path.join(LIBDIR, "mc_hosttest_" + kind)
     srcs = [os.path.join(hdir, "hosttest.cpp"), os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(ROOT, "include", "mcgpu.h")]
+    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h"), os.path.join(ROOT, "include", "mcgpu.h")]
     san = {"asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "tsan": ["-fsanitize=thread"]}[kind]
     if force or _stale(out, srcs + hdrs):
         cmd = ["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")] + san + [

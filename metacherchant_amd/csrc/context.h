@@ -213,7 +213,7 @@ struct mc_ctx {
     hipEvent_t ev_seq[16] = {};  // behind every kernel of a per-window run in pieces (add_reads_partitioned_once)
     hipEvent_t ev_t[4] = {};  // P1 start, P1 end, P2 end, P3 end of a pipeline run enqueued without a host round trip in between
     // The read store: the packed bases of every read this context was given since the last mc_clear, batch after
-    // batch (each starting on a word boundary).  Table slots point into it (kmer_device.h ptr_encode) and the BFS
+    // batch (each starting on a word boundary).  Table slots point into it (read_ptr.h ptr_encode) and the BFS
     // reads its look-ahead from it.  rs_from: a BFS-only context (mc_solid_from_pairs_dev) borrows the store of the
     // context that counted this rank's reads (mc_share_read_store).
     uint64_t *rs_words = nullptr;

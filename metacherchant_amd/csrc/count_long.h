@@ -25,6 +25,7 @@
 namespace mc {
 
 constexpr uint32_t SKL_MAX_WINDOWS = 32;
+static_assert(SKL_MAX_WINDOWS == PTR_LONG_WINDOWS, "read_ptr.h ptr_advance_long: j < the windows of a long record");
 constexpr uint32_t P1L_LANES = 57;                      // lanes of a wave's tile that own windows; the 7 above them only supply SK_M-mer hashes
 constexpr uint32_t P1L_TILE = P1L_LANES * PT_ITEMS;     // 456 base positions per wave tile
 constexpr int SKL_MIN_K = 33, SKL_MAX_K = 63;           // (two-word k-mers; mc_create takes hash keys up to k = 63)
@@ -86,16 +87,6 @@ __device__ __forceinline__ void poly_roll(uint64_t &hf, uint64_t &hr, uint32_t o
     hr = (hr - (3u ^ out)) * POLY_INV5 + poly_4x_times(3u ^ in, p_km1);
 }
 __host__ __device__ inline uint64_t pow5(int e) { uint64_t p = 1; for (int i = 0; i < e; i++) p *= 5ull; return p; }
-
-// pointer of the window j <= 31 bases behind the one `aux` names (kmer_device.h ptr_advance serves 16-window records)
-__device__ __forceinline__ uint32_t ptr_advance_long(uint32_t aux, uint32_t j)
-{
-    if (aux == 0) return 0;
-    const uint64_t v = (uint64_t)aux - 1;
-    if (v + SKL_MAX_WINDOWS < PTR_EXACT_END) return aux + j;
-    uint32_t span;
-    return ptr_encode(ptr_decode(aux, &span) + j);  // (a granule: its first base + j names a granule at most one short of the window's)
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Level 1: k_sk1w_extract (count_pipeline.h) for windows of 33 .. 64 bases, compact records only.  What differs:
@@ -538,9 +529,11 @@ __global__ void __launch_bounds__(P3_THREADS) k_p3_long(const uint4 *__restrict_
                 uint64_t hf = 0, hr = 0;
                 if (cnt) poly_start(X0, X1, X2, k, L.polyF, L.polyR, &hf, &hr);
                 // the pointer of the chunk's first window, once; window j of the chunk is j bases on where pointers name places, and
-                // within the slack of the granule where they name granules (kmer_device.h ptr_advance: the same rule)
+                // within the slack of the granule where they name granules (read_ptr.h ptr_advance_long)
                 const uint32_t pbase = ptr_advance_long(p0, j0);
                 const uint32_t pstep = pbase != 0 && (uint64_t)pbase - 1 + SKL_MAX_WINDOWS < PTR_EXACT_END ? 0xFFFFFFFFu : 0u;
+                // (the store's last 32 exact positions: pbase names one place and no other, every window gets its own code)
+                const bool pedge = pbase != 0 && pstep == 0 && (uint64_t)pbase - 1 < PTR_EXACT_END;
 #pragma unroll 1
                 for (uint32_t j = 0; j < SKL_CHUNK; j++) {
                     const bool act = j < cnt;
@@ -567,7 +560,8 @@ __global__ void __launch_bounds__(P3_THREADS) k_p3_long(const uint4 *__restrict_
                         s = lds_probe_claim(key_base, (home + 1u) & (REGION_SLOTS - 1u), key, &unused, &pending, P3_MAX_PROBES - 1u);
                         fits = !((pending >> (tid & 63u)) & 1ull);
                     }
-                    const uint32_t ptr = pbase + (j & pstep);
+                    uint32_t ptr = pbase + (j & pstep);
+                    if (__builtin_expect(pedge, 0)) ptr = ptr_encode((uint64_t)pbase - 1 + j);
                     if (fits) {
                         const uint32_t seen = atomicAdd(&L.cnt[s], cp);
                         if (pbase != 0 && seen <= pk && pk < seen + cp) L.aux[s] = ptr;  // (the occurrence that leaves its pointer is one of these cp)

@@ -511,7 +511,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_p2_scatter(const uint64_t *__res
 //   lo bits 63..32  bases 30 .. 45 (windows + k - 1 <= 16 + 30 bases in all; unused tail zero)
 //   lo bits 31..0   the record's bin word (sk_bin of its minimizer): P2 and, after the table grew, P3 take their
 //                   bucket digits from it
-// A second stream carries the read pointer (kmer_device.h ptr_encode) of the record's first window, or 0.
+// A second stream carries the read pointer (read_ptr.h ptr_encode) of the record's first window, or 0.
 constexpr uint32_t SK_MAX_WINDOWS = 16;  // 16 + (31 - 1) = 46 bases
 
 __device__ __forceinline__ uint32_t sk_windows(uint64_t hi) { return (uint32_t)(hi >> 60) + 1u; }
@@ -1105,11 +1105,18 @@ __global__ void __launch_bounds__(PT_THREADS) k_sk1_records(const uint4 *__restr
     const uint32_t tid = threadIdx.x, n_buckets = np1;
     for (uint32_t i = tid; i < PT_MAX_BUCKETS1_SK; i += PT_THREADS) wcur[i] = 0;
     __syncthreads();
-    const uint64_t n_tiles = (n + PT_TILE - 1) / PT_TILE;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    // Rows of 4 records (64 bytes: one memory sector) are dealt to the workgroups (= segments) round-robin, as mcgpu.hip k_solid_emit
+    // deals its rows: mc_extract_superkmers_dev delivers an owner's records bucket by bucket, and whole tiles of them put a bucket's
+    // records into a few segments only -- the segment capacities count on every segment getting its share of every bucket, so one
+    // record in fifteen went to the spill list, whose records carry no read pointers.
+    constexpr uint32_t WAVES = PT_THREADS / 64, ROW = 4, ROWS_PER_WAVE = 64 / ROW;
+    const uint64_t n_rows = (n + ROW - 1) / ROW;
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    for (uint64_t t0 = 0; t0 * WAVES * ROWS_PER_WAVE * gridDim.x < n_rows; t0 += PT_ITEMS) {
 #pragma unroll
         for (int j = 0; j < PT_ITEMS; j++) {
-            const uint64_t i = tile * PT_TILE + tid + (uint64_t)j * PT_THREADS;
+            const uint64_t local = ((t0 + (uint64_t)j) * WAVES + wave) * ROWS_PER_WAVE + lane / ROW;  // this workgroup's row number
+            const uint64_t i = (local * gridDim.x + blockIdx.x) * ROW + lane % ROW;
             if (i < n) {
                 const uint4 rec = in_recs[i];  // (its bin word rides in rec.x; in_bins / out_bins carry the read pointers)
                 const uint32_t d = mulhi32(rec.x, np1);
@@ -2478,7 +2485,7 @@ __global__ void __launch_bounds__(D2_THREADS, MC_D2_WAVES_PER_EU) k_p3_dedup(con
             uint32_t p0 = L.dptr[f][rs];
             if (p0 == 0) p0 = L.dptr[0][rs];
             if (ptr_tries > 1 && p0 == 0) p0 = L.dptr[1][rs] ? L.dptr[1][rs] : L.dptr[2][rs];  // (fields fill in the order of ALL copies there)
-            return p0 - 1u < 0x7FFFFFEFu ? p0 + j : ptr_advance(p0, j);  // (exact pointers: kmer_device.h ptr_advance's first case)
+            return p0 - 1u < 0x7FFFFFEFu ? p0 + j : ptr_advance(p0, j);  // (exact pointers: read_ptr.h ptr_advance's first case)
         };
         auto note_ptr = [&](uint32_t sg, uint32_t at, uint32_t pw) {  // region slot sg finds its pointer in word `at` of the list
             wl[at] = pw;

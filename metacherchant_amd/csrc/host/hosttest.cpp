@@ -18,6 +18,9 @@
 // `mc_hosttest placement <k>`: where the table puts a key (csrc/kmer_hash.h, the functions the kernels compile).  Reads hexadecimal
 // 64-bit words from stdin, one a line, and prints for each "fmix64 sk_order sk_bin sk_hmin_of_kmer": the hash of the word as a key, the
 // order and the bin of its low 32 bits, and the smallest order among the SK_M-mers of the word as a packed k-mer of k bases.
+// `mc_hosttest pointers <pos>...`: the code of a read pointer (csrc/read_ptr.h, the functions the kernels compile).  For every store
+// position (decimal) one line: ptr_encode(pos), ptr_decode of that code and its span (0 0 for no pointer), ptr_advance(code, j) for
+// j = 0 .. 15 and ptr_advance_long(code, j) for j = 0 .. 31.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -26,6 +29,7 @@
 #include <map>
 
 #include "../kmer_hash.h"
+#include "../read_ptr.h"
 #include "envfinder.h"
 
 using namespace mch;
@@ -156,6 +160,19 @@ int main(int argc, char **argv)
                        mc::sk_hmin_of_kmer(k < 32 ? w & ((1ull << (2 * k)) - 1) : w, k));
             return 0;
         }
+        if (argc >= 3 && std::string(argv[1]) == "pointers") {
+            for (int a = 2; a < argc; a++) {
+                const uint64_t pos = strtoull(argv[a], nullptr, 10);
+                const uint32_t code = mc::ptr_encode(pos);
+                uint32_t span = 0;
+                const uint64_t lo = code ? mc::ptr_decode(code, &span) : 0;
+                printf("%u %llu %u", code, (unsigned long long)lo, span);
+                for (uint32_t j = 0; j < 16; j++) printf(" %u", mc::ptr_advance(code, j));
+                for (uint32_t j = 0; j < mc::PTR_LONG_WINDOWS; j++) printf(" %u", mc::ptr_advance_long(code, j));
+                printf("\n");
+            }
+            return 0;
+        }
         if (argc == 3 && std::string(argv[1]) == "unitigs") {
             std::ifstream f(argv[2]);
             if (!f) throw Error("cannot open the k-mer file");
@@ -195,7 +212,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | pointers <pos>... | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

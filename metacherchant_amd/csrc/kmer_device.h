@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "kmer_hash.h"  // fmix64, rc_packed, sk_order, sk_bin, sk_hmin_of_kmer: the part a host compiler can read too
+#include "read_ptr.h"   // ptr_encode, ptr_decode, ptr_advance, ptr_advance_long: likewise
 
 namespace mc {
 
@@ -248,55 +249,8 @@ __host__ __device__ __forceinline__ Kmer neighbour(const Kmer &v, int k, int dir
 }
 
 // ---------------------------------------------------------------------------------------------
-// Read pointers (Slot::aux).  The context keeps the packed bases of every read it was given (the "read store",
-// mcgpu.hip) and a slot remembers WHERE one occurrence of its key sits in it.  The BFS uses that only to GUESS the
-// next vertices of a linear stretch -- the bases that follow the occurrence in its read are the path a walker will
-// most likely take -- and looks every guess up, so a missing, stale or wrong pointer can cost time but never change a
-// result.  32 bits: 0 = none; v = aux - 1 < 2^31: the occurrence starts at base v of the store, exactly (14 M reads of
-// 150 bases).  Beyond that the value names a GRANULE of the store and the reader matches the k-mer against every offset of
-// it (+ PTR_SLACK, see ptr_advance), in tiers, so that a store a few times the exact range still gets fine pointers:
-//   v in [2^31,            2^31 + 2^30)            granules of   4 bases   positions 2.1 G ..   6.4 G
-//   v in [2^31 + 2^30,     2^31 + 2^30 + 2^29)     granules of  16 bases             6.4 G ..  15.0 G
-//   v in [2^31 + 3 * 2^29, 2^32 - 2)               granules of  64 bases            15.0 G ..  49 G   (beyond: no pointer)
-// (one tier of 64-base granules from 2^31 on, as it was, made the walk over 50 M reads twice as long as over 10 M.)
-constexpr uint64_t PTR_EXACT_END = 1ull << 31;
-constexpr uint32_t PTR_SLACK = 16;
-constexpr uint32_t PTR_T1_LG = 2, PTR_T2_LG = 4, PTR_T3_LG = 6;  // (a hop looks at 512 bases around a pointer: 64 + PTR_SLACK candidate offsets is what fits)
-constexpr uint64_t PTR_T1_N = 1ull << 30, PTR_T2_N = 1ull << 29, PTR_T3_N = (1ull << 29) - 2;
-constexpr uint64_t PTR_T1_POS = PTR_EXACT_END, PTR_T2_POS = PTR_T1_POS + (PTR_T1_N << PTR_T1_LG), PTR_T3_POS = PTR_T2_POS + (PTR_T2_N << PTR_T2_LG);
-__host__ __device__ __forceinline__ uint32_t ptr_encode(uint64_t pos)
-{
-    if (pos < PTR_EXACT_END) return (uint32_t)pos + 1u;
-    uint64_t v;
-    if (pos < PTR_T2_POS) v = PTR_EXACT_END + ((pos - PTR_T1_POS) >> PTR_T1_LG);
-    else if (pos < PTR_T3_POS) v = PTR_EXACT_END + PTR_T1_N + ((pos - PTR_T2_POS) >> PTR_T2_LG);
-    else {
-        const uint64_t g = (pos - PTR_T3_POS) >> PTR_T3_LG;
-        if (g >= PTR_T3_N) return 0u;
-        v = PTR_EXACT_END + PTR_T1_N + PTR_T2_N + g;
-    }
-    return (uint32_t)v + 1u;
-}
-// first base of the range the occurrence starts in; *span = number of candidate offsets
-__host__ __device__ __forceinline__ uint64_t ptr_decode(uint32_t aux, uint32_t *span)
-{
-    const uint64_t v = (uint64_t)aux - 1;
-    if (v < PTR_EXACT_END) { *span = 1; return v; }
-    const uint64_t w = v - PTR_EXACT_END;
-    if (w < PTR_T1_N) { *span = (1u << PTR_T1_LG) + PTR_SLACK; return PTR_T1_POS + (w << PTR_T1_LG); }
-    if (w < PTR_T1_N + PTR_T2_N) { *span = (1u << PTR_T2_LG) + PTR_SLACK; return PTR_T2_POS + ((w - PTR_T1_N) << PTR_T2_LG); }
-    *span = (1u << PTR_T3_LG) + PTR_SLACK;
-    return PTR_T3_POS + ((w - PTR_T1_N - PTR_T2_N) << PTR_T3_LG);
-}
-// pointer of the window j <= 15 bases after the window a pointer names (windows of one super-k-mer record)
-__host__ __device__ __forceinline__ uint32_t ptr_advance(uint32_t aux, uint32_t j)
-{
-    if (aux == 0) return 0;
-    const uint64_t v = (uint64_t)aux - 1;
-    if (v + 16 < PTR_EXACT_END) return aux + j;
-    if (v < PTR_EXACT_END) return ptr_encode(v + j);  // (the last exact positions: window j may lie in the first granule)
-    return aux;  // (a granule: the reader's range has PTR_SLACK to spare)
-}
+// Read pointers (Slot::aux): what they are and their 32-bit code (ptr_encode, ptr_decode, ptr_advance, ptr_advance_long) are in
+// read_ptr.h, which needs nothing of HIP.
 
 // Which occurrence of a key (counted from 0 in the order the counting kernels meet them) leaves its pointer:
 // ptr_from + r with r = a few bits of the key, r < min(4, thr - ptr_from) so that every key that reaches the coverage
@@ -498,6 +452,9 @@ __device__ __forceinline__ uint32_t table_add_at(const TableView &t, uint64_t s,
                 const unsigned long long old =
                     atomicAdd(reinterpret_cast<unsigned long long *>(&p->count), ((unsigned long long)hint << 32) | inc);
                 if (before) *before = (uint32_t)old;  // (another thread may have counted this key in between)
+                // ... and, being the occurrence ptr_pick names, may have left its pointer already: the sum of two pointers is none
+                // -- the one that was there goes back (a plain store like its own: whichever lands last, the slot holds a pointer)
+                if (hint && (old >> 32)) p->aux = (uint32_t)(old >> 32);
                 return 1;
             }
             if (cur == key) {
