@@ -562,6 +562,50 @@ int mc_unitigs_dev(mc_ctx *ctx, const uint64_t *d_hi, const uint64_t *d_lo, cons
 int mc_unitigs(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint8_t *cls, uint64_t n, mc_unitigs_result *out);
 void mc_unitigs_free(mc_unitigs_result *r);
 
+/* ---- the environment join: what environment-finder-multi takes from several graph.txt files at once (initializeStructures of
+ * src/algo/MultiSequenceCalculator.java:51-100, the KC column of src/io/writers/GFAWriterMulti.java, printProbability of
+ * src/tools/EnvironmentFinderMultiMain.java:104-170).  k is the context's; its key mode and its table play no part.
+ * Input:
+ *   entries  n oriented packed k-mers in the layout of mc_kmer_presence (hi may be NULL when k <= 32).  No two may be the same k-mer or
+ *            each other's reverse complement;
+ *   records  the lines of n_graphs graph files (1 to 64) one graph after another: an oriented k-mer as the file spells it (rec_hi may
+ *            be NULL when k <= 32) and its depth; graph g's records are graph_offsets[g] .. graph_offsets[g + 1] - 1 (graph_offsets[0]
+ *            is 0; a graph may be empty).  Every record's k-mer or its reverse complement must be an entry, and a graph must not hold
+ *            the same oriented k-mer twice (it may hold a k-mer and its reverse complement as two records);
+ *   the gene gene_len bases packed as reads are (A0 G1 C2 T3, first base most significant, 32 a word; NULL when gene_len is 0).  A gene
+ *            shorter than k has no window.
+ * Output, per entry e:
+ *   member[e]   bit g is set when graph g holds the entry's k-mer in either orientation (MultiNode.addGraph);
+ *   is_gene[e]  1 when a window of the gene is the entry's k-mer or its reverse complement;
+ *   kc[e]       the sum over g of the depth of graph g's record that is the entry's k-mer as given.  A record of the reverse
+ *               complement adds nothing (GFAWriterMulti looks up the normalised window only).
+ * Output, three n_graphs x n_graphs matrices (row i, column j at i * n_graphs + j) of sums modulo 2^32 over every oriented k-mer x that
+ * some record spells, where H is the set of graphs holding x (in that orientation) and d_g their depths as unsigned words:
+ *   i in H, j in H       diff and diff_alt += |d_i - d_j|, uni += max(d_i, d_j)   (i == j: uni += d_i)
+ *   i in H, j not in H   diff, diff_alt and uni += d_i
+ *   i not in H, j in H   diff and uni += d_j
+ * -- printProbability's three sums for the pair (i, j).
+ * Errors: MC_EINVAL for null pointers (hi and rec_hi at k <= 32 excepted), n_graphs == 0 or > 64, n >= 2^30, graph_offsets that
+ * decrease, and the three conditions above.  n == 0 without records is MC_OK with empty arrays and zero matrices.  *out is zeroed on an
+ * error.  Free a result with mc_env_join_free (NULL and zeroed results are fine).  mc_env_join takes host pointers, mc_env_join_dev
+ * device ones; the result is on the host in both. */
+typedef struct {
+    uint64_t n;                       /* entries */
+    uint32_t n_graphs;
+    uint64_t *member;                 /* n */
+    uint8_t  *is_gene;                /* n */
+    int64_t  *kc;                     /* n */
+    uint32_t *diff, *diff_alt, *uni;  /* n_graphs * n_graphs each */
+    double device_ms;                 /* summed device time of the passes (HIP events) */
+} mc_env_join_result;  /* (not mc_env_join: C has one name space for typedefs and functions) */
+int mc_env_join_dev(mc_ctx *ctx, const uint64_t *d_hi, const uint64_t *d_lo, uint64_t n, const uint64_t *d_rec_hi, const uint64_t *d_rec_lo,
+                    const int32_t *d_rec_depth, const uint64_t *d_graph_offsets, uint32_t n_graphs, const uint64_t *d_gene, uint64_t gene_len,
+                    mc_env_join_result *out);
+int mc_env_join(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, uint64_t n, const uint64_t *rec_hi, const uint64_t *rec_lo,
+                const int32_t *rec_depth, const uint64_t *graph_offsets, uint32_t n_graphs, const uint64_t *gene, uint64_t gene_len,
+                mc_env_join_result *out);
+void mc_env_join_free(mc_env_join_result *r);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

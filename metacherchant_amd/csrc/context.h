@@ -13,8 +13,9 @@
 //   reads_in_set.hip mc_reads_in_set*: every read's windows against a small exact set of k-mers behind a bit filter in LDS
 //   components.hip  mc_components*: the connected components of the table's k-mers that a set of sequences holds (union-find over slots)
 //   unitigs.hip     mc_unitigs*: what the reference's unitig compaction leaves of a set of k-mers, by link analysis and pointer jumping
+//   env_join.hip    mc_env_join*: the join of several graph files' records on their k-mers for environment-finder-multi (members, KC, the two Jaccard tables' sums)
 // multi_table.h is what seq_cov.hip and presence.hip share: one key's home slots in several tables, the probing behind them, and the
-// host's checks of a list of contexts; kmer_set.h what reads_in_set.hip and unitigs.hip share: the key and hash of a call's exact
+// host's checks of a list of contexts; kmer_set.h what reads_in_set.hip, unitigs.hip and env_join.hip share: the key and hash of a call's exact
 // set.  A function below the "across units" line is what one unit lends another; everything else stays static in its unit.
 #pragma once
 #include <hip/hip_runtime.h>

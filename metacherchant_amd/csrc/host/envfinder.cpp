@@ -2367,6 +2367,335 @@ MultiResult environment_finder_multi(const std::vector<std::string> &env_paths, 
     return R;
 }
 
+// ---- the packed path
+
+namespace {
+struct KmerHash {
+    size_t operator()(kmer_t key) const
+    {
+        uint64_t h = (uint64_t)key ^ ((uint64_t)(key >> 64) * 0x9E3779B97F4A7C15ull);
+        h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
+        return (size_t)h;
+    }
+};
+
+// |v - w| as int arithmetic gives it (wrapping where Java's would), as an unsigned word
+inline uint32_t abs_diff_u32(int32_t v, int32_t w)
+{
+    const int32_t d = (int32_t)((uint32_t)v - (uint32_t)w);
+    return d < 0 ? 0u - (uint32_t)d : (uint32_t)d;
+}
+}  // namespace
+
+void env_join_host(const EnvJoinInput &in, EnvJoinResult &out)
+{
+    out = EnvJoinResult{};
+    const int k = in.k;
+    const size_t n = in.entries.size(), G = in.n_graphs();
+    if (G == 0 || G > 64) throw Error("env_join_host: " + std::to_string(G) + " graphs (1 to 64)");
+    if (n >= (1ull << 30)) throw Error("env_join_host: too many entries");
+    if (in.graph_offsets[0] != 0 || in.graph_offsets[G] != in.rec_kmers.size() || in.rec_depth.size() != in.rec_kmers.size())
+        throw Error("env_join_host: graph_offsets do not fit the records");
+    std::unordered_map<kmer_t, uint32_t, KmerHash> row_of;  // both orientations of every entry
+    row_of.reserve(4 * n);
+    for (size_t e = 0; e < n; e++) {
+        const kmer_t v = in.entries[e], r = reverse_complement128(v, k);
+        const bool fresh = row_of.emplace(v, (uint32_t)(2 * e)).second && (r == v || row_of.emplace(r, (uint32_t)(2 * e + 1)).second);
+        if (!fresh) throw Error("env_join_host: two entries are the same k-mer or each other's reverse complement");
+    }
+    std::vector<uint64_t> holder(2 * n, 0);
+    std::vector<int32_t> depth(2 * n * G, 0);
+    for (size_t g = 0; g < G; g++) {
+        if (in.graph_offsets[g] > in.graph_offsets[g + 1]) throw Error("env_join_host: graph_offsets decrease");
+        for (uint64_t r = in.graph_offsets[g]; r < in.graph_offsets[g + 1]; r++) {
+            const auto it = row_of.find(in.rec_kmers[r]);
+            if (it == row_of.end()) throw Error("env_join_host: a record's k-mer is no entry, and neither is its reverse complement");
+            if (holder[it->second] >> g & 1) throw Error("env_join_host: a graph holds the same oriented k-mer twice");
+            holder[it->second] |= 1ull << g;
+            depth[(size_t)it->second * G + g] = in.rec_depth[r];
+        }
+    }
+    out.member.assign(n, 0);
+    out.is_gene.assign(n, 0);
+    out.kc.assign(n, 0);
+    out.diff.assign(G * G, 0);
+    out.diff_alt.assign(G * G, 0);
+    out.uni.assign(G * G, 0);
+    {
+        kmer_t v = 0;
+        for (uint64_t i = 0; i < in.gene_len; i++) {
+            v = ((v << 2) | ((in.gene_words[i >> 5] >> (62 - 2 * (i & 31))) & 3)) & kmer_mask(k);
+            if (i + 1 < (uint64_t)k) continue;
+            const auto it = row_of.find(v);
+            if (it != row_of.end()) out.is_gene[it->second / 2] = 1;
+        }
+    }
+    for (size_t row = 0; row < 2 * n; row++) {
+        const uint64_t H = holder[row];
+        const int32_t *d = depth.data() + row * G;
+        out.member[row / 2] |= H;
+        for (size_t i = 0; i < G; i++) {
+            if (!(H >> i & 1)) continue;
+            if (!(row & 1)) out.kc[row / 2] += d[i];
+            for (size_t j = 0; j < G; j++) {
+                if (H >> j & 1) {
+                    out.diff[i * G + j] += abs_diff_u32(d[i], d[j]);
+                    out.diff_alt[i * G + j] += abs_diff_u32(d[i], d[j]);
+                    out.uni[i * G + j] += (uint32_t)std::max(d[i], d[j]);
+                } else {
+                    out.diff[i * G + j] += (uint32_t)d[i];
+                    out.diff_alt[i * G + j] += (uint32_t)d[i];
+                    out.uni[i * G + j] += (uint32_t)d[i];
+                    out.diff[j * G + i] += (uint32_t)d[i];  // (seen from j, which does not hold the k-mer)
+                    out.uni[j * G + i] += (uint32_t)d[i];
+                }
+            }
+        }
+    }
+}
+
+namespace {
+struct PackedGraphFile {
+    std::vector<kmer_t> kmers;  // line order
+    std::vector<int> depths;
+};
+
+// DeBruijnGraphUtils.loadGraph (:13-27) with the key packed; lengths: every key's length as it comes
+PackedGraphFile load_graph_packed(const std::string &path, std::vector<size_t> *lengths)
+{
+    std::vector<std::string> lines;
+    if (!read_lines(path, &lines)) throw Error("Couldn't load graph from file " + path);
+    PackedGraphFile g;
+    for (const std::string &line : lines) {
+        if (line.empty()) continue;
+        const size_t sp = line.find(' ');
+        if (sp == std::string::npos || sp + 1 >= line.size()) throw Error("Couldn't load graph from file " + path + ": bad line '" + line + "'");
+        size_t end = line.find(' ', sp + 1);
+        const std::string num = line.substr(sp + 1, end == std::string::npos ? std::string::npos : end - sp - 1);
+        char *stop = nullptr;
+        const long v = strtol(num.c_str(), &stop, 10);
+        if (num.empty() || *stop) throw Error("Couldn't load graph from file " + path + ": bad depth '" + num + "'");
+        if (sp > 63) throw MultiUnpacked("k = " + std::to_string(sp) + " is above 63");
+        if (sp == 0) throw MultiUnpacked("an empty k-mer in " + path);
+        kmer_t key = 0;
+        for (size_t i = 0; i < sp; i++) {
+            unsigned code;
+            switch (line[i]) {
+            case 'A': code = 0; break;
+            case 'G': code = 1; break;
+            case 'C': code = 2; break;
+            case 'T': code = 3; break;
+            default: throw MultiUnpacked("a k-mer with a character outside upper-case ACGT in " + path + ": '" + line.substr(0, sp) + "'");
+            }
+            key = (key << 2) | code;
+        }
+        g.kmers.push_back(key);
+        g.depths.push_back((int)v);
+        lengths->push_back(sp);
+    }
+    return g;
+}
+}  // namespace
+
+MultiResult environment_finder_multi_packed(const std::vector<std::string> &env_paths, const std::string &seq_path, int gene_id, const Joiner &join,
+                                            const Compactor &compact, size_t *n_entries)
+{
+    MultiResult R;
+    if (env_paths.size() > 64) throw MultiUnpacked(std::to_string(env_paths.size()) + " environments are more than 64");
+    std::vector<PackedGraphFile> files;
+    std::vector<size_t> lengths;
+    for (const std::string &p : env_paths) files.push_back(load_graph_packed(p, &lengths));
+    if (files.empty()) throw Error("Zero environments given");
+    if (files[0].kmers.empty()) throw Error("The first environment is empty");
+    if (std::adjacent_find(lengths.begin(), lengths.end(), std::not_equal_to<size_t>()) != lengths.end()) {
+        // which two lengths the message names depends on the string maps' iteration order: theirs is asked (an error's path only)
+        std::vector<JavaHashMap> graphs;
+        for (const std::string &p : env_paths) graphs.push_back(load_graph(p));
+        int k0 = -1;
+        graphs[0].for_each([&](const std::string &kmer, int) { if (k0 < 0) k0 = (int)kmer.size(); });
+        for (const JavaHashMap &g : graphs)
+            g.for_each([&](const std::string &kmer, int) {
+                if ((int)kmer.size() != k0)
+                    throw Error("K-mers of different lengths encountered: " + std::to_string(k0) + " and " + std::to_string(kmer.size()));
+            });
+    }
+    const int k = (int)lengths[0];
+    const size_t G = files.size();
+    std::vector<JavaKmerMap> graphs;  // the last line of a k-mer wins; the iteration order is the HashMap's
+    for (const PackedGraphFile &f : files) {
+        graphs.emplace_back(k);
+        for (size_t i = 0; i < f.kmers.size(); i++) graphs.back().put(f.kmers[i], f.depths[i]);
+    }
+    files.clear();
+    SeedFile sf;
+    try {
+        sf = read_seed_fasta(seq_path);
+    } catch (const Error &) {
+        throw Error("Could not load sequence file");
+    }
+    if (gene_id < 1 || (size_t)gene_id > sf.dnas.size() || (size_t)gene_id > sf.comments.size())
+        throw Error("--geneid " + std::to_string(gene_id) + " is outside the sequences of " + seq_path);
+    const std::string sequence = sf.dnas[(size_t)gene_id - 1], comment = sf.comments[(size_t)gene_id - 1];
+    R.log.push_back("INFO Combining environments for sequence " +
+                    ((int)sequence.size() >= 2 * k ? sequence.substr(0, (size_t)k) + "..." + sequence.substr(sequence.size() - (size_t)k) +
+                                                         " (length=" + std::to_string(sequence.size()) + ")"
+                                                   : sequence));
+
+    // initializeStructures (MultiSequenceCalculator.java:51-100): the entries
+    EnvJoinInput in;
+    in.k = k;
+    {
+        JavaKmerMap by_kmer(k);
+        for (const JavaKmerMap &g : graphs)
+            g.for_each([&](kmer_t kmer, int, int) {
+                by_kmer.put(kmer, -1);
+                by_kmer.put(reverse_complement128(kmer, k), -1);
+            });
+        const size_t size = by_kmer.size();
+        by_kmer.for_each([&](kmer_t kmer, int, int) {
+            const kmer_t rc = reverse_complement128(kmer, k);
+            if (ascii_rank(kmer) > ascii_rank(rc)) return;
+            if (2 * in.entries.size() + 2 > size)
+                throw Error("palindromic k-mer " + unpack_kmer128(kmer, k) + ": the reference fails here (ArrayIndexOutOfBoundsException)");
+            in.entries.push_back(kmer);
+        });
+    }
+    const size_t n = in.entries.size();
+    if (n_entries) *n_entries = n;
+    in.graph_offsets.push_back(0);
+    for (const JavaKmerMap &g : graphs) {
+        g.for_each([&](kmer_t kmer, int depth, int) {
+            in.rec_kmers.push_back(kmer);
+            in.rec_depth.push_back(depth);
+        });
+        in.graph_offsets.push_back(in.rec_kmers.size());
+    }
+    graphs.clear();
+    in.gene_len = sequence.size();  // (upper-case ACGT: read_seed_fasta makes it so)
+    in.gene_words.assign((sequence.size() + 31) / 32, 0);
+    for (size_t i = 0; i < sequence.size(); i++) in.gene_words[i >> 5] |= (uint64_t)code_of(sequence[i]) << (62 - 2 * (i & 31));
+    EnvJoinResult J;
+    join(in, J);
+    if (J.member.size() != n || J.is_gene.size() != n || J.kc.size() != n || J.diff.size() != G * G || J.diff_alt.size() != G * G || J.uni.size() != G * G)
+        throw Error("environment_finder_multi_packed: the joiner's result does not fit the entries");
+    in.rec_kmers.clear();
+    in.rec_depth.clear();
+
+    // doMerge (:102-139) merges nodes of one is_gene and one set of graphs: the merge class is the pair's dense rank
+    std::vector<uint8_t> cls(n);
+    {
+        std::map<std::pair<uint8_t, uint64_t>, int> rank;
+        for (size_t e = 0; e < n; e++) rank.emplace(std::make_pair(J.is_gene[e], J.member[e]), 0);
+        if (rank.size() > 256) throw MultiUnpacked(std::to_string(rank.size()) + " merge classes (sets of graphs, with and without the gene) are more than 256");
+        int next = 0;
+        for (auto &kv : rank) kv.second = next++;
+        for (size_t e = 0; e < n; e++) cls[e] = (uint8_t)rank[std::make_pair(J.is_gene[e], J.member[e])];
+    }
+    std::vector<uint8_t> irregular(n, 0);  // entries whose nodes the loop on labels merged
+    const Compactor keep_irregular = [&](int kk, const std::vector<kmer_t> &kmers, const std::vector<uint8_t> &c, UnitigsResult &out) {
+        compact(kk, kmers, c, out);
+        for (const uint32_t e : out.irregular)
+            if (e < n) irregular[e] = 1;
+    };
+    std::vector<PictureNode> nodes = make_picture(k, in.entries, cls, &keep_irregular);
+    const size_t N = nodes.size();
+    auto node_kmer = [&](size_t i) { return (i & 1) ? reverse_complement128(in.entries[i / 2], k) : in.entries[i / 2]; };
+    // the reference lists a node's neighbours in the order of their last base, A G C T: the codes' order
+    for (PictureNode &nd : nodes)
+        std::sort(nd.neighbors.begin(), nd.neighbors.end(),
+                  [&](int a, int b) { return ((unsigned)node_kmer((size_t)a) & 3u) < ((unsigned)node_kmer((size_t)b) & 3u); });
+    auto min_id = [&](size_t i) { return (int)std::min(i, (size_t)nodes[i].rc) + 1; };
+    auto label = [&](size_t i) { return std::to_string(min_id(i)) + (J.is_gene[i / 2] ? "_start" : ""); };
+
+    // outputNodeSequences (:141-160)
+    for (size_t i = 0; i < N; i++) {
+        const PictureNode &nd = nodes[i];
+        if (nd.deleted || !((int)i < nd.rc)) continue;
+        std::set<int> ids;
+        for (int j : nd.neighbors) ids.insert(min_id((size_t)j));
+        for (int j : nodes[(size_t)nd.rc].neighbors) ids.insert(min_id((size_t)j));
+        ids.erase(min_id(i));
+        R.seqs_fasta += "> Id" + label(i) + " Length:" + std::to_string(nd.sequence.size()) + " Neighbors:[";
+        bool first = true;
+        for (int x : ids) {
+            if (!first) R.seqs_fasta += ", ";
+            R.seqs_fasta += std::to_string(x);
+            first = false;
+        }
+        R.seqs_fasta += "]\n" + nd.sequence + "\n";
+    }
+
+    // GFAWriterMulti (:37-146)
+    auto color = [&](size_t i) -> std::string {
+        if (J.is_gene[i / 2]) return "#00ff00";
+        const size_t s = (size_t)__builtin_popcountll(J.member[i / 2]);
+        if (G == 2) return s == 1 ? "#ff0000" : s == 2 ? "#0000ff" : "#000000";
+        if (G == 3) {
+            static const char *c3[] = {"#000000", "#ff0000", "#0000ff", "#ff00ff", "#ffff00", "#ffaa00", "#00ffff"};
+            return s <= 6 ? c3[s] : "#000000";
+        }
+        const int v = (int)(256 * s / G);
+        char buf[32];
+        snprintf(buf, sizeof buf, "#%02X%02X%02X", v, v, v);
+        return buf;
+    };
+    std::unordered_map<kmer_t, uint32_t, KmerHash> entry_of;  // (only when the loop on labels merged something)
+    for (size_t i = 0; i < N; i++) {
+        const PictureNode &nd = nodes[i];
+        if (nd.deleted || !((int)i < nd.rc)) continue;
+        long long coverage = 0;
+        if (!irregular[i / 2]) {
+            // a unitig's windows are its chain's entries: next(a) is the one neighbour of a ^ 1, up to the node whose twin is rc
+            size_t steps = 0;
+            for (size_t a = i;; a = (size_t)nodes[a ^ 1].neighbors[0]) {
+                coverage += J.kc[a / 2];
+                if ((int)(a ^ 1) == nd.rc) break;
+                if (nodes[a ^ 1].neighbors.size() != 1 || ++steps > N) throw Error("environment_finder_multi_packed: a merged node is no chain");
+            }
+        } else {
+            if (entry_of.empty())
+                for (size_t e = 0; e < n; e++) entry_of.emplace(in.entries[e], (uint32_t)e);
+            kmer_t fw = 0, rc = 0;
+            for (size_t p = 0; p < nd.sequence.size(); p++) {
+                const unsigned code = (unsigned)code_of(nd.sequence[p]);
+                fw = ((fw << 2) | code) & kmer_mask(k);
+                rc = (rc >> 2) | ((kmer_t)(3u - code) << (2 * (k - 1)));
+                if (p + 1 < (size_t)k) continue;
+                const auto it = entry_of.find(ascii_rank(fw) < ascii_rank(rc) ? fw : rc);
+                if (it != entry_of.end()) coverage += J.kc[it->second];
+            }
+        }
+        const std::string col = color(i);
+        R.graph_gfa += "S\t" + label(i) + "\t" + nd.sequence + "\tLN:i:" + std::to_string(nd.sequence.size()) + "\tKC:i:" + std::to_string(coverage) +
+                       "\tCL:Z:" + col + "\tC2:Z:" + col + "\n";
+    }
+    for (size_t a = 0; a < N; a++) {
+        if (nodes[a].deleted) continue;
+        for (int j : nodes[a].neighbors)
+            R.graph_gfa += "L\t" + label(a) + "\t" + ((int)a < nodes[a].rc ? "+" : "-") + "\t" + label((size_t)j) + "\t" +
+                           (j > nodes[(size_t)j].rc ? "+" : "-") + "\t" + std::to_string(k - 1) + "M\n";
+    }
+    R.gene_fasta = ">" + comment + "\n" + sequence + "\n";
+
+    // printProbability (EnvironmentFinderMultiMain.java:104-170): 32-bit sums (wrapping like Java's int), float division
+    R.jacard_sym = "The[31mWarning! symmetric <<Jaccard distance>> (1 - AB/AUB):\n\n";
+    R.jacard_alt = "The[31mWarning! alternative <<Jaccard distance>> (1 - AB/A):\n\n";
+    for (size_t i = 0; i < G; i++) {
+        R.jacard_sym += env_paths[i];
+        R.jacard_alt += env_paths[i];
+        for (size_t j = 0; j < G; j++) {
+            const uint32_t diff = J.diff[i * G + j], diff_alt = J.diff_alt[i * G + j], uni = J.uni[i * G + j];
+            const int inter = (int)(uni - diff), u = (int)uni, ua = (int)(uni - diff_alt);
+            R.jacard_sym += java_format_6_2f(1.0f - (float)inter / (float)u) + " ";
+            R.jacard_alt += java_format_6_2f(1.0f - (float)inter / (float)ua) + " ";
+        }
+        R.jacard_sym += "\n";
+        R.jacard_alt += "\n";
+    }
+    R.log.push_back("INFO Finished processing!");
+    return R;
+}
+
 void write_multi(const MultiResult &r, const std::string &output_dir)
 {
     write_file(output_dir + "/seqs.fasta", r.seqs_fasta);

@@ -15,6 +15,9 @@
 // the link analysis ("U first last_rc bases" a unitig, "I entry" an irregular entry), then the node state of the reference's loop
 // ("O id deleted rc label neighbours") and of the link analysis with the loop over the irregular entries ("N ..."); a deleted node's
 // label and rc print as "-" (they depend on the loop's scan order and are never read).
+// `mc_hosttest multi-packed <out_dir> <seq> <gene_id> <env>...`: what `multi` writes and prints, through environment_finder_multi_packed with
+// env_join_host and unitigs_by_links, and "ENTRIES <n>" behind the log lines.  An input the packed path cannot represent ends with
+// "unpacked: <reason>" on stderr and status 3.
 // `mc_hosttest placement <k>`: where the table puts a key (csrc/kmer_hash.h, the functions the kernels compile).  Reads hexadecimal
 // 64-bit words from stdin, one a line, and prints for each "fmix64 sk_order sk_bin sk_hmin_of_kmer": the hash of the word as a key, the
 // order and the bin of its low 32 bits, and the smallest order among the SK_M-mers of the word as a packed k-mer of k bases.
@@ -98,6 +101,15 @@ int main(int argc, char **argv)
             const MultiResult r = environment_finder_multi(std::vector<std::string>(argv + 5, argv + argc), argv[3], atoi(argv[4]));
             write_multi(r, argv[2]);
             for (const auto &l : r.log) printf("%s\n", l.c_str());
+            return 0;
+        }
+        if (argc >= 6 && std::string(argv[1]) == "multi-packed") {  // the same files on packed k-mers: env_join_host + unitigs_by_links
+            size_t n = 0;
+            const MultiResult r = environment_finder_multi_packed(std::vector<std::string>(argv + 5, argv + argc), argv[3], atoi(argv[4]), env_join_host,
+                                                                  unitigs_by_links, &n);
+            write_multi(r, argv[2]);
+            for (const auto &l : r.log) printf("%s\n", l.c_str());
+            printf("ENTRIES %zu\n", n);
             return 0;
         }
         if (argc == 5 && std::string(argv[1]) == "colour") {
@@ -212,7 +224,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | pointers <pos>... | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | pointers <pos>... | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);
@@ -244,6 +256,9 @@ int main(int argc, char **argv)
         }
         env.write_all(argv[3], chunk);
         return 0;
+    } catch (const MultiUnpacked &e) {
+        fprintf(stderr, "unpacked: %s\n", e.what());
+        return 3;
     } catch (const std::exception &e) {
         fprintf(stderr, "error: %s\n", e.what());
         return 1;

@@ -28,6 +28,7 @@
 
 #include "envfinder.h"
 #include "gpu_compactor.h"
+#include "gpu_joiner.h"
 #include "mcgpu.h"
 
 using namespace mch;
@@ -100,6 +101,9 @@ struct Options {
     // --compact: who compacts an environment's k-mers into unitigs (no counterpart in the reference; the files are the same)
     std::string compact = "auto";
     bool compact_given = false;
+    // --join (environment-finder-multi): who joins the graph files and compacts the result (no counterpart in the reference; the files are the same)
+    std::string join = "auto";
+    bool join_given = false;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -112,7 +116,7 @@ const OptSpec SPECS[] = {
     {"merge", nullptr, 1}, {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0},
     {"continue", "c", 1}, {"force", nullptr, 1}, {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0},
     {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"output-dir", nullptr, 0}, {"env", "e", 2}, {"geneid", "g", 0},
-    {"compact", nullptr, 0},
+    {"compact", nullptr, 0}, {"join", nullptr, 0},
 };
 
 // --tool reads-classifier: its parameters (ReadsClassifier.java:42-95) and the launch options
@@ -285,6 +289,11 @@ Options parse_args(int argc, char **argv)
         o.compact = *v;
         o.compact_given = true;
     }
+    if (auto v = val("join")) {
+        if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--join takes host, gpu or auto, not '" + *v + "'");
+        o.join = *v;
+        o.join_given = true;
+    }
     if (auto v = val("seq")) o.seq = *v;
     if (auto v = val("hicseq")) o.hicseq = *v;
     if (auto v = val("output")) o.output = *v;
@@ -347,7 +356,10 @@ void usage()
     puts("      --hash <arg>         hash function to use: poly or fnv1a (default poly)");
     puts("      --trim [<arg>]       trim all not maximal paths? (default false)");
     puts("      --merge [<arg>]      draw single environment for multiple input sequences? (default false)");
-    puts("Input parameters of --tool environment-finder-multi (CPU only): -e/--env <graph.txt files>, --seq, -o/--output, -g/--geneid (default 1)");
+    puts("Input parameters of --tool environment-finder-multi: -e/--env <graph.txt files>, --seq, -o/--output, -g/--geneid (default 1),");
+    puts("  --join host|gpu|auto (who joins the graphs and compacts the result; the files are the same.  host: on k-mer strings, as the");
+    puts("  reference does; gpu: on packed k-mers with mc_env_join and mc_unitigs on --device; auto, the default: the GPU from 100000");
+    puts("  k-mers on, the smallest size measured at which it wins, and whenever the packed form holds the input; else the host)");
     puts("Input parameters of --tool kmer-counter: -k, -i/--reads, --hash, --output-dir <dir> (default <work-dir>/kmers)");
     puts("Input parameters of --tool reads-classifier (splits the reads of -r into found / not found in the graph of -i):");
     puts("  -k, --k <arg>                  k-mer size (MANDATORY)");
@@ -598,14 +610,73 @@ int run_kmer_counter(const Options &o)
     return 0;
 }
 
-// --tool environment-finder-multi (src/tools/EnvironmentFinderMultiMain.java): no GPU involved
+// --tool environment-finder-multi (src/tools/EnvironmentFinderMultiMain.java).  --join: the join of the graph files and the compaction
+// on the host on k-mer strings (environment_finder_multi, the reference's way), on the GPU on packed k-mers (mc_env_join and mc_unitigs
+// on a context of its own with an empty table), or `auto`, the default: on the GPU from JOIN_AUTO_MIN entries on.  That is the smallest
+// size at which scripts/multi_join_bench.py has timed the whole tool faster the GPU's way than on strings (0.34 s against 1.57 s at
+// k = 31, 0.46 s against 1.77 s at k = 63, four graphs); at 10 000 entries the GPU's way took 0.27 s, as at 2 000 (a process opens the device and
+// creates a context before its first kernel), three times the string path's whole run.
+constexpr size_t JOIN_AUTO_MIN = 100000;
+struct BelowJoinAutoMin {
+    size_t n;
+};
 int run_multi(const Options &o)
 {
     if (o.env.empty()) throw Error("Parameter 'env' is mandatory");
     if (o.seq.empty()) throw Error("Parameter 'seq' is mandatory");
     if (o.output.empty()) throw Error("Parameter 'output' is mandatory");
+    if (!o.devices.empty()) throw Error("--devices is for --tool environment-finder: environment-finder-multi joins the graphs on one device (--device)");
     if (!open_work_dir(o, "seq=" + o.seq + "\noutput=" + o.output + "\n")) return 0;
-    const MultiResult r = environment_finder_multi(o.env, o.seq, o.geneid);
+    const std::string joining = "Joining " + std::to_string(o.env.size()) + " environments";
+    bool packed = o.join != "host";
+    if (o.join == "auto") {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) {
+            info(joining + " on the host (k-mer strings): no HIP device is available");
+            packed = false;
+        }
+    } else if (!packed) {
+        info(joining + " on the host (k-mer strings)");
+    }
+    MultiResult r;
+    if (packed) {
+        CtxGuard own;
+        double join_ms = 0, unitigs_ms = 0;
+        bool small = false;
+        const Joiner join = [&](const EnvJoinInput &in, EnvJoinResult &out) {
+            const size_t n = in.entries.size();
+            if (o.join == "auto" && n < JOIN_AUTO_MIN) {  // (too few for the GPU: joined here all the same, to hear whether the classes fit; then the compactor ends it)
+                small = true;
+                env_join_host(in, out);
+                return;
+            }
+            info(joining + " (" + std::to_string(n) + " k-mers) on the GPU (mc_env_join, mc_unitigs)");
+            mc_config cfg{};
+            cfg.k = in.k;
+            cfg.key_mode = MC_KEY_POLY;
+            cfg.device = o.device;
+            if (mc_create(&cfg, &own.c) != MC_OK) throw Error(std::string(mc_last_error(nullptr)));
+            gpu_joiner(own.c, &join_ms)(in, out);
+        };
+        const Compactor compact = [&](int k, const std::vector<kmer_t> &kmers, const std::vector<uint8_t> &cls, UnitigsResult &out) {
+            if (small) throw BelowJoinAutoMin{kmers.size()};
+            gpu_compactor(own.c, &unitigs_ms)(k, kmers, cls, out);
+        };
+        try {
+            r = environment_finder_multi_packed(o.env, o.seq, o.geneid, join, compact);
+            char ms[96];
+            snprintf(ms, sizeof ms, "mc_env_join %.3f ms, mc_unitigs %.3f ms on the device", join_ms, unitigs_ms);
+            logline("DEBUG", ms);
+        } catch (const MultiUnpacked &e) {
+            if (o.join == "gpu") throw Error(std::string("--join gpu: ") + e.what() + " (--join host takes such input)");
+            info(joining + " on the host (k-mer strings): " + e.what());
+            packed = false;
+        } catch (const BelowJoinAutoMin &b) {
+            info(joining + " (" + std::to_string(b.n) + " k-mers) on the host (k-mer strings)");
+            packed = false;
+        }
+    }
+    if (!packed) r = environment_finder_multi(o.env, o.seq, o.geneid);
     write_multi(r, o.output);
     for (const std::string &l : r.log) logline(l.substr(0, 4).c_str(), l.substr(5));
     write_file(o.work_dir + "/SUCCESS", "");
@@ -1710,6 +1781,7 @@ int run(const Options &o)
 {
     if (o.compact_given && (o.tool == "kmer-counter" || o.tool == "environment-finder-multi"))  // (they share environment-finder's table)
         throw Error("--compact does not apply to --tool " + o.tool);
+    if (o.join_given && o.tool != "environment-finder-multi") throw Error("--join does not apply to --tool " + o.tool);
     if (o.tool == "kmer-counter") return run_kmer_counter(o);
     if (o.tool == "environment-finder-multi") return run_multi(o);
     if (o.tool == "reads-classifier") return run_reads_classifier(o);

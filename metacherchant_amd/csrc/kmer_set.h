@@ -1,4 +1,4 @@
-// What reads_in_set.hip and unitigs.hip share: the key of a canonical k-mer in an exact open-addressing set built for one call, its
+// What reads_in_set.hip, unitigs.hip and env_join.hip share: the key of a canonical k-mer in an exact open-addressing set built for one call, its
 // hash and its home slot.  The tables themselves (what a slot holds beside the key, how it is built and probed) stay in the units.
 #pragma once
 #include <cstdint>

@@ -79,6 +79,13 @@ class _Unitigs(C.Structure):
                 ("bases", C.POINTER(C.c_uint64)), ("n_irregular", C.c_uint64), ("irregular", C.POINTER(C.c_uint32)), ("device_ms", C.c_double)]
 
 
+class _EnvJoin(C.Structure):
+    """mc_env_join_result"""
+    _fields_ = [("n", C.c_uint64), ("n_graphs", C.c_uint32), ("member", C.POINTER(C.c_uint64)), ("is_gene", C.POINTER(C.c_uint8)),
+                ("kc", C.POINTER(C.c_int64)), ("diff", C.POINTER(C.c_uint32)), ("diff_alt", C.POINTER(C.c_uint32)), ("uni", C.POINTER(C.c_uint32)),
+                ("device_ms", C.c_double)]
+
+
 READ_COV_DTYPE = np.dtype([("sum", np.int32), ("covered", np.int32), ("last", np.int16), ("found", np.uint8), ("pad", np.uint8)])
 CLASSIFY_CORRECTION = 1  # mc_classify_reads flags: findReadWithCorrection
 LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fingerprint, so distinct reads share one
@@ -101,6 +108,7 @@ EXPORTS = [
     "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev", "mc_seq_coverage", "mc_seq_coverage_dev",
     "mc_kmer_presence", "mc_kmer_presence_dev", "mc_reads_in_set", "mc_reads_in_set_dev",
     "mc_components", "mc_components_dev", "mc_components_free", "mc_unitigs", "mc_unitigs_dev", "mc_unitigs_free",
+    "mc_env_join", "mc_env_join_dev", "mc_env_join_free",
 ]
 
 _LIB = None
@@ -206,6 +214,12 @@ def load():
         L.mc_unitigs_dev.argtypes = [vp, vp, vp, vp, u64, C.POINTER(_Unitigs)]
         L.mc_unitigs_free.argtypes = [C.POINTER(_Unitigs)]
         L.mc_unitigs_free.restype = None
+    if hasattr(L, "mc_env_join"):
+        i32p = C.POINTER(C.c_int32)
+        L.mc_env_join.argtypes = [vp, u64p, u64p, u64, u64p, u64p, i32p, u64p, C.c_uint32, u64p, u64, C.POINTER(_EnvJoin)]
+        L.mc_env_join_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, C.c_uint32, vp, u64, C.POINTER(_EnvJoin)]
+        L.mc_env_join_free.argtypes = [C.POINTER(_EnvJoin)]
+        L.mc_env_join_free.restype = None
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -602,6 +616,14 @@ class Context:
         """mc_unitigs_dev: see the module's unitigs_dev()"""
         return unitigs_dev(self, d_hi, d_lo, d_cls, n)
 
+    def env_join(self, hi, lo, rec_hi, rec_lo, rec_depth, graph_offsets, gene_words=None, gene_len=0):
+        """mc_env_join: see the module's env_join()"""
+        return env_join(self, hi, lo, rec_hi, rec_lo, rec_depth, graph_offsets, gene_words, gene_len)
+
+    def env_join_dev(self, d_hi, d_lo, n, d_rec_hi, d_rec_lo, d_rec_depth, d_graph_offsets, n_graphs, d_gene=None, gene_len=0):
+        """mc_env_join_dev: see the module's env_join_dev()"""
+        return env_join_dev(self, d_hi, d_lo, n, d_rec_hi, d_rec_lo, d_rec_depth, d_graph_offsets, n_graphs, d_gene, gene_len)
+
     def synth_reads_dev(self, genome_seed, n_contigs, contig_len, read_seed, first_read, n_reads, read_len,
                         err_per_10k, d_words, d_offsets):
         self._chk(self._L.mc_synth_reads_dev(self._h, genome_seed, n_contigs, contig_len, read_seed, first_read,
@@ -761,6 +783,56 @@ def unitigs_dev(context, d_hi, d_lo, d_cls, n):
     r = _Unitigs()
     context._chk(load().mc_unitigs_dev(context._h, _dptr(d_hi), _dptr(d_lo), _dptr(d_cls), int(n), C.byref(r)))
     return _unitigs_result(r)
+
+
+def _env_join_result(r):
+    """the library's arrays as numpy arrays of our own, and the library's freed"""
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+    try:
+        n, g = int(r.n), int(r.n_graphs)
+        return {"n": n, "n_graphs": g, "member": arr(r.member, n, np.uint64), "is_gene": arr(r.is_gene, n, np.uint8), "kc": arr(r.kc, n, np.int64),
+                "diff": arr(r.diff, g * g, np.uint32).reshape(g, g), "diff_alt": arr(r.diff_alt, g * g, np.uint32).reshape(g, g),
+                "uni": arr(r.uni, g * g, np.uint32).reshape(g, g), "device_ms": float(r.device_ms)}
+    finally:
+        load().mc_env_join_free(C.byref(r))
+
+
+def env_join(context, hi, lo, rec_hi, rec_lo, rec_depth, graph_offsets, gene_words=None, gene_len=0):
+    """mc_env_join: the join of several graph files on their k-mers.  Entries: oriented packed k-mers (hi << 64 | lo; hi may be None
+    when k <= 32), entry e standing for its k-mer and the reverse complement.  Records: the files' lines one graph after another
+    (rec_hi may be None when k <= 32), rec_depth (int32) their depths, graph_offsets (n_graphs + 1) where each graph's records start.
+    gene_words: gene_len bases packed as reads are (None for no gene).  Returns a dict of numpy arrays: member (uint64, bit g: graph g
+    holds the entry in either orientation), is_gene, kc (int64: the depths of the records that spell the entry as given), the
+    n_graphs x n_graphs uint32 matrices diff, diff_alt and uni (printProbability's sums modulo 2^32), and n, n_graphs, device_ms.
+    Needs no table."""
+    lo = np.ascontiguousarray(lo, dtype=np.uint64)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64) if hi is not None else None
+    rec_lo = np.ascontiguousarray(rec_lo, dtype=np.uint64)
+    rec_hi = np.ascontiguousarray(rec_hi, dtype=np.uint64) if rec_hi is not None else None
+    rec_depth = np.ascontiguousarray(rec_depth, dtype=np.int32)
+    graph_offsets = np.ascontiguousarray(graph_offsets, dtype=np.uint64)
+    if (hi is not None and len(hi) != len(lo)) or (rec_hi is not None and len(rec_hi) != len(rec_lo)) or len(rec_depth) != len(rec_lo):
+        raise ValueError("hi and lo need one entry a k-mer; rec_hi, rec_lo and rec_depth one a record")
+    if len(graph_offsets) < 1 or (len(graph_offsets) <= 65 and int(graph_offsets[-1]) != len(rec_lo)):
+        raise ValueError("graph_offsets needs n_graphs + 1 entries, the last the number of records")
+    gene = np.ascontiguousarray(gene_words, dtype=np.uint64) if gene_words is not None else None
+    if gene_len and (gene is None or len(gene) * 32 < gene_len):
+        raise ValueError("gene_words holds fewer than gene_len bases")
+    r = _EnvJoin()
+    q = lambda a: _p(a, C.c_uint64) if a is not None else None
+    context._chk(load().mc_env_join(context._h, q(hi), q(lo), len(lo), q(rec_hi), q(rec_lo), _p(rec_depth, C.c_int32), q(graph_offsets),
+                                    len(graph_offsets) - 1, q(gene), int(gene_len), C.byref(r)))
+    return _env_join_result(r)
+
+
+def env_join_dev(context, d_hi, d_lo, n, d_rec_hi, d_rec_lo, d_rec_depth, d_graph_offsets, n_graphs, d_gene=None, gene_len=0):
+    """mc_env_join_dev: device pointers (d_hi and d_rec_hi may be None when k <= 32, d_gene when gene_len is 0); d_graph_offsets holds
+    n_graphs + 1 uint64.  The result comes back as env_join's does"""
+    r = _EnvJoin()
+    context._chk(load().mc_env_join_dev(context._h, _dptr(d_hi), _dptr(d_lo), int(n), _dptr(d_rec_hi), _dptr(d_rec_lo), _dptr(d_rec_depth),
+                                        _dptr(d_graph_offsets), int(n_graphs), _dptr(d_gene), int(gene_len), C.byref(r)))
+    return _env_join_result(r)
 
 
 def key_owner(key, n_owners):
