@@ -606,6 +606,62 @@ int mc_env_join(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, uint64_t n,
                 mc_env_join_result *out);
 void mc_env_join_free(mc_env_join_result *r);
 
+/* ---- whole reads with their qualities, tokenised on the device: what the classifying tools read their -r files with, ready for
+ * mc_classify_reads_dev, mc_reads_last_copy_dev, mc_seq_coverage_dev, mc_reads_in_set_dev and mc_components_dev.  The policy is that
+ * of readDnaQLazy (itmo!/io/ReadersUtils.java:185-215) -- reads are neither split nor dropped, unlike mc_add_reads_file's:
+ *   FASTQ (itmo!/io/readers/FastqReader.java:53-82): records of four lines, `@...`, bases, `+...`, qualities; one trailing '\r' comes
+ *          off every line.  N, n and . give base 0 with phred 0 (itmo!/dna/DnaQBuilder.java:45 unsafeAppendUnknown), any other base its
+ *          code (A0 G1 C2 T3, either case) and phred (quality char - phred_offset) & 63 (DnaQ.phredAt reads 6 bits).  A read of length 0
+ *          is a read.  phred_offset is 33 or 64 and the caller's to find (ReadersUtils.java:63-77 determineQualityFormat: 64 unless, in
+ *          the first 1000 records, a base that is not N n . has a quality char below 64 or above 126);
+ *   FASTA (FastaWithNsReader.readNextDataLine): a line that starts with '>' or ';' ends the record before it, the other lines are
+ *          concatenated, text in front of the first header is a record, empty records give nothing; phred 20
+ *          (ReadersUtils.DEFAULT_PHRED_FOR_FASTA) and 0 at N n .
+ * text holds n_bytes of a file, a whole number of records (host memory; mc_tokenize_whole_dev: device memory of at least
+ * mc_whole_text_bytes(n_bytes) bytes, whose bytes behind the text are overwritten, and last_byte = text[n_bytes - 1]).  Any context
+ * will do: its table plays no part, as with mc_reads_last_copy.  The result is device memory throughout:
+ *   d_words    the bases packed as mc_classify_reads_dev takes them, ceil(n_bases / 32) + 1 words, unknown bases as base 0;
+ *   d_offsets  n_reads + 1 base positions in d_words, d_offsets[0] == 0;
+ *   d_bad_pos  per read mc_classify_reads' bad_pos: the one position with phred < 10, -1 for none, -2 for several
+ *              (src/algo/PairFinder.java findReadWithCorrection).  An N counts, in FASTA as well;
+ *   d_codes, d_phred  with MC_WHOLE_CODES / MC_WHOLE_PHRED in flags: a byte a base, the code and the phred (what a DnaQ holds); else NULL.
+ * declined = 1 (and all else zero, nothing allocated): the text holds something whose outcome the host reader defines -- a byte that is
+ * no base and not N n ., a quality char outside [phred_offset, 126], bases and qualities of different length, a line count that is
+ * no multiple of four, a record whose first line does not start with '@' or whose third does not start with '+', a read of 2^31 - 16
+ * bases or more.  Read that text with the host parser, which gives the reference's message or its laxer reading.
+ * Two calls on the same text give the same bytes.  n_bytes == 0 gives no reads (d_offsets holds the one 0).
+ * Errors: MC_EINVAL for null pointers, a format or phred_offset that is none of the above, unknown flags.  *out is zeroed on an error.
+ * mc_whole_reads_to_host copies the arrays of a result to host memory: every pointer that is not NULL is filled, sized as above.
+ * Free a result with mc_whole_reads_free (NULL and zeroed results are fine). */
+#define MC_WHOLE_FASTA 0
+#define MC_WHOLE_FASTQ 1
+#define MC_WHOLE_CODES 1u  /* flags: also a byte a base with the code */
+#define MC_WHOLE_PHRED 2u  /* flags: also a byte a base with the phred */
+typedef struct {
+    int declined;
+    uint64_t n_reads, n_bases;
+    uint64_t *d_words;
+    uint64_t *d_offsets;
+    int32_t  *d_bad_pos;
+    uint8_t  *d_codes, *d_phred;
+    double device_ms;  /* from the first pass to the last on the context's stream (HIP events; the scans' totals are waited for in between) */
+} mc_whole_reads;
+int mc_tokenize_whole(mc_ctx *ctx, const char *text, uint64_t n_bytes, int format, int phred_offset, uint32_t flags, mc_whole_reads *out);
+int mc_tokenize_whole_dev(mc_ctx *ctx, uint8_t *d_text, uint64_t n_bytes, int last_byte, int format, int phred_offset, uint32_t flags,
+                          mc_whole_reads *out);
+uint64_t mc_whole_text_bytes(uint64_t n_bytes);
+int mc_whole_reads_to_host(mc_ctx *ctx, const mc_whole_reads *r, uint64_t *words, uint64_t *offsets, int32_t *bad_pos, uint8_t *codes, uint8_t *phred);
+void mc_whole_reads_free(mc_ctx *ctx, mc_whole_reads *r);
+/* Joins device views of packed reads into one: the n_reads reads of d_words / d_offsets (n_reads + 1 base positions in d_words; the
+ * first need not be 0, so a slice of a mc_whole_reads result will do; d_words has its pad word) go behind the dst_bases bases that
+ * d_dst_words already holds, shifted into place.  d_dst_words needs ceil((dst_bases + the new bases) / 32) + 1 words; when dst_bases
+ * is no multiple of 32, the word the old reads end in must be zero behind them (it is after an earlier call; zero the first word
+ * before the first).  The pad word behind the result is zeroed.  d_dst_offsets points at the destination's entry for the first new
+ * read: entries 0 .. n_reads are written, entry 0 being dst_bases.  For the calls that want all reads in one array
+ * (mc_reads_last_copy_dev over all pairs, mc_components_dev) when the reads come a chunk at a time.  Any context will do. */
+int mc_reads_append_dev(mc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_offsets, uint64_t n_reads, uint64_t *d_dst_words,
+                        uint64_t dst_bases, uint64_t *d_dst_offsets);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

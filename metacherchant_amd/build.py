@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libmcgpu.so")
 CLI = os.path.join(LIBDIR, "metacherchant")
 
 # the library's units (csrc/context.h says what each holds), and the host reader the read-file entry point uses
-HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip",
+HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip",
                os.path.join("host", "envfinder.cpp")]
 # every header under csrc/ makes every object stale (a stale library would travel to the GPU box unnoticed)
 HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "envfinder.h"), os.path.join("test", "bfs_old_race.h"),
@@ -100,7 +100,8 @@ def build_host(force=False, verbose=False):
     hdir = os.path.join(CSRC, "host")
     os.makedirs(LIBDIR, exist_ok=True)
     common = [os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "gpu_compactor.h"), os.path.join(hdir, "gpu_joiner.h"), os.path.join(ROOT, "include", "mcgpu.h")]
+    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "gpu_compactor.h"), os.path.join(hdir, "gpu_joiner.h"), os.path.join(hdir, "whole_reads_source.h"),
+            os.path.join(ROOT, "include", "mcgpu.h")]
     flags = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")]
     if force or _stale(HOSTTEST, common + hdrs + [os.path.join(hdir, "hosttest.cpp"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h")]):
         cmd = ["g++"] + flags + ["-o", HOSTTEST, os.path.join(hdir, "hosttest.cpp")] + common + ["-lz", "-ldl"]
@@ -136,6 +137,27 @@ def build_unitigs_bench(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     return UNITIGS_BENCH
+
+
+WHOLE_READS_BENCH = os.path.join(LIBDIR, "mc_whole_reads_bench")
+
+
+def build_whole_reads_bench(force=False, verbose=False):
+    """mc_whole_reads_bench (csrc/host/whole_reads_bench.cpp): the reader stage of the classifying tools, host against device, timed;
+    scripts/whole_reads_bench.py runs it"""
+    hdir = os.path.join(CSRC, "host")
+    srcs = [os.path.join(hdir, "whole_reads_bench.cpp"), os.path.join(hdir, "envfinder.cpp")]
+    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "whole_reads_source.h"), os.path.join(ROOT, "include", "mcgpu.h")]
+    if force or _stale(WHOLE_READS_BENCH, srcs + hdrs + [LIB]):
+        rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"), "-I",
+               os.path.join(ROOT, "include"), "-o", WHOLE_READS_BENCH] + srcs + [
+            "-L", LIBDIR, "-lmcgpu", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib"),
+            "-lpthread", "-lz", "-ldl"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return WHOLE_READS_BENCH
 
 
 def build_host_sanitized(kind, force=False, verbose=False):

@@ -14,6 +14,9 @@
 //   components.hip  mc_components*: the connected components of the table's k-mers that a set of sequences holds (union-find over slots)
 //   unitigs.hip     mc_unitigs*: what the reference's unitig compaction leaves of a set of k-mers, by link analysis and pointer jumping
 //   env_join.hip    mc_env_join*: the join of several graph files' records on their k-mers for environment-finder-multi (members, KC, the two Jaccard tables' sums)
+//   whole_reads.hip mc_tokenize_whole*: FASTA / FASTQ text into whole reads with their qualities (DnaQReader's policy) for the classifying tools,
+//                   mc_reads_append_dev: slices of such results joined into one array of packed reads;
+//                   tokenizer_device.h is what it shares with tokenizer.h, the newline pass and the scan come from reads_file.hip
 // multi_table.h is what seq_cov.hip and presence.hip share: one key's home slots in several tables, the probing behind them, and the
 // host's checks of a list of contexts; kmer_set.h what reads_in_set.hip, unitigs.hip and env_join.hip share: the key and hash of a call's exact
 // set.  A function below the "across units" line is what one unit lends another; everything else stays static in its unit.
@@ -628,6 +631,13 @@ struct TokPending {
 };
 int tokenize_chunk_locked(mc_ctx *c, const mch::PlainReadsFile &f, const char *b, const char *e, uint8_t *d_text, uint64_t *n_reads_out,
                           bool *declined, TokPending *pend = nullptr);
+// ... and what whole_reads.hip takes from it: the scan of 32-bit counts into 64-bit offsets and the newline pass
+int tok_scan(mc_ctx *c, const uint32_t *d_in, uint64_t n, unsigned long long *d_out, uint64_t *total);
+struct TokNewlines {  // the newline positions and the pass's tile buffers: the caller keeps them until its own passes are done
+    PoolBuf<uint32_t> tile_counts;
+    PoolBuf<unsigned long long> tile_off, nl;
+};
+int tok_newlines(mc_ctx *c, const uint8_t *d_text, uint64_t n, TokNewlines *b, uint64_t *n_nl, bool *too_many);
 
 // walk.hip: the walk over several ranks' tables
 struct ShardWire {  // what a mc_shard_handle holds

@@ -1257,18 +1257,20 @@ struct DnaQReader::Impl {
     Compression comp = COMP_NONE;
     bool fastq = false;
     int offset = 64;
-    std::unique_ptr<LineSource> src;
+    std::unique_ptr<LineSource> src;  // the file's lines, or ...
+    std::unique_ptr<MemLines> mem;    // ... those of a range of text in memory
     bool done = false;
     std::string line, data, qual;
+    bool getline(std::string &l) { return mem ? mem->getline(l) : src->getline(l); }
     // FastqReader.readNextDataLine: empty lines skipped, a line starting with '@' or '+', then the content line
     bool fastq_line(std::string &out)
     {
         for (;;) {
-            if (!src->getline(line)) return false;
+            if (!getline(line)) return false;
             if (!line.empty()) break;
         }
         if (line[0] != '@' && line[0] != '+') throw Error("Unknown structure of fastq file! Waiting \"@ID\" or \"+ID\" string");
-        if (!src->getline(out)) throw Error("Unexpected end of file. File is corrupted/Format mismatch.");
+        if (!getline(out)) throw Error("Unexpected end of file. File is corrupted/Format mismatch.");
         return true;
     }
     bool fastq_record()
@@ -1282,7 +1284,7 @@ struct DnaQReader::Impl {
     bool fasta_record()
     {
         data.clear();
-        while (src->getline(line)) {
+        while (getline(line)) {
             if (!line.empty() && (line[0] == '>' || line[0] == ';')) {
                 if (!data.empty()) return true;
             } else {
@@ -1323,7 +1325,18 @@ DnaQReader::DnaQReader(const std::string &path) : impl_(new Impl)
     }
 }
 
+DnaQReader::DnaQReader(const char *b, const char *e, bool fastq, int phred_offset) : impl_(new Impl)
+{
+    impl_->fastq = fastq;
+    impl_->offset = phred_offset;
+    impl_->mem.reset(new MemLines(b, e));
+}
+
 DnaQReader::~DnaQReader() { delete impl_; }
+
+bool DnaQReader::fastq() const { return impl_->fastq; }
+int DnaQReader::phred_offset() const { return impl_->offset; }
+bool DnaQReader::compressed() const { return impl_->comp != COMP_NONE; }
 
 size_t DnaQReader::read(DnaQBatch &b, size_t max_reads)
 {

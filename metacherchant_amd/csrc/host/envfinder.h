@@ -147,10 +147,39 @@ struct DnaQBatch {
     uint64_t n_reads() const { return offsets.empty() ? 0 : offsets.size() - 1; }
     void clear() { codes.clear(); phred.clear(); offsets.assign(1, 0); }
 };
+// what a tool does with a batch before mc_classify_reads and its kin: reads first .. first + n - 1 packed 32 bases a word (the pad word
+// included) with offsets that start at 0, and findReadWithCorrection's one low-quality position of each (phred < 10): -1 none, -2 several
+inline void pack_whole_reads(const DnaQBatch &b, size_t first, size_t n, std::vector<uint64_t> &words, std::vector<uint64_t> *offsets)
+{
+    const uint64_t o0 = b.offsets[first], nb = b.offsets[first + n] - o0;
+    words.assign((nb + 31) / 32 + 1, 0);
+    for (uint64_t i = 0; i < nb; i++) words[i >> 5] |= (uint64_t)(b.codes[o0 + i] & 3) << (62 - 2 * (i & 31));
+    if (offsets) {
+        offsets->resize(n + 1);
+        for (size_t r = 0; r <= n; r++) (*offsets)[r] = b.offsets[first + r] - o0;
+    }
+}
+inline std::vector<int32_t> low_quality_positions(const DnaQBatch &b, size_t first, size_t n)
+{
+    std::vector<int32_t> bad(n, -1);
+    for (size_t r = 0; r < n; r++)
+        for (uint64_t i = b.offsets[first + r]; i < b.offsets[first + r + 1]; i++)
+            if (b.phred[i] < 10) {
+                if (bad[r] != -1) { bad[r] = -2; break; }
+                bad[r] = (int32_t)(i - b.offsets[first + r]);
+            }
+    return bad;
+}
 class DnaQReader {
 public:
     explicit DnaQReader(const std::string &path);  // throws Error on a file it cannot read or whose format it cannot tell
+    // the same record functions over text in memory: [b, e) starts at a record start of a file of that format and quality offset
+    // (a chunk of a mapped file that the device tokeniser declined: the same reads, the same messages)
+    DnaQReader(const char *b, const char *e, bool fastq, int phred_offset);
     ~DnaQReader();
+    bool fastq() const;
+    int phred_offset() const;  // FASTQ: 33 or 64, as the first 1000 records say
+    bool compressed() const;
     DnaQReader(const DnaQReader &) = delete;
     DnaQReader &operator=(const DnaQReader &) = delete;
     // appends up to max_reads records to b; returns how many (0: the file is done)

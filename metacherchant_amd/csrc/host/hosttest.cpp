@@ -18,6 +18,10 @@
 // `mc_hosttest multi-packed <out_dir> <seq> <gene_id> <env>...`: what `multi` writes and prints, through environment_finder_multi_packed with
 // env_join_host and unitigs_by_links, and "ENTRIES <n>" behind the log lines.  An input the packed path cannot represent ends with
 // "unpacked: <reason>" on stderr and status 3.
+// `mc_hosttest dnaq <file>`: what DnaQReader delivers.  "fastq <0|1> offset <n>" (the quality offset it found; 0 for FASTA), then a line a
+// read: "R <length>\t<bases, N as A>\t<phreds as chars from '!'>".  `mc_hosttest dnaq-range <file> <chunk>`: the same lines from the file
+// cut at record starts every <chunk> bytes, each piece read by DnaQReader over a range of memory.  An error ends both with status 1 after
+// the reads before it.
 // `mc_hosttest placement <k>`: where the table puts a key (csrc/kmer_hash.h, the functions the kernels compile).  Reads hexadecimal
 // 64-bit words from stdin, one a line, and prints for each "fmix64 sk_order sk_bin sk_hmin_of_kmer": the hash of the word as a key, the
 // order and the bin of its low 32 bits, and the smallest order among the SK_M-mers of the word as a packed k-mer of k bases.
@@ -163,6 +167,57 @@ int main(int argc, char **argv)
             printf("%llu\n", (unsigned long long)out.kept());
             return 0;
         }
+        if ((argc == 3 && std::string(argv[1]) == "dnaq") || (argc == 4 && std::string(argv[1]) == "dnaq-range")) {
+            DnaQReader reader(argv[2]);
+            printf("fastq %d offset %d\n", reader.fastq() ? 1 : 0, reader.fastq() ? reader.phred_offset() : 0);
+            DnaQBatch b;
+            auto print = [&] {
+                std::string s, q;
+                for (size_t r = 0; r < b.n_reads(); r++) {
+                    s.clear();
+                    q.clear();
+                    for (uint64_t i = b.offsets[r]; i < b.offsets[r + 1]; i++) {
+                        s.push_back("AGCT"[b.codes[i] & 3]);
+                        q.push_back((char)(33 + b.phred[i]));
+                    }
+                    printf("R %zu\t%s\t%s\n", s.size(), s.c_str(), q.c_str());
+                }
+                fflush(stdout);  // (what was read before an error is printed)
+            };
+            auto read_some = [&](DnaQReader &r) {  // (the whole reads in front of the one that throws are printed)
+                try {
+                    return r.read(b, 7);
+                } catch (...) {
+                    print();
+                    throw;
+                }
+            };
+            if (argc == 3) {
+                for (;;) {
+                    b.clear();
+                    const size_t got = read_some(reader);
+                    print();
+                    if (got == 0) break;
+                }
+                return 0;
+            }
+            // the file cut at record starts every <chunk> bytes, each piece through the reader over a range of memory
+            const uint64_t chunk = strtoull(argv[3], nullptr, 10);
+            PlainReadsFile f;
+            if (!map_plain_reads(argv[2], &f)) throw Error("dnaq-range: not a plain FASTA / FASTQ file");
+            for (const char *p = f.p, *end = f.p + f.n; p < end;) {
+                const char *e = (uint64_t)(end - p) <= chunk + chunk / 4 ? end : plain_record_start(f, p + chunk);
+                DnaQReader part(p, e, reader.fastq(), reader.phred_offset());
+                for (;;) {
+                    b.clear();
+                    const size_t got = read_some(part);
+                    print();
+                    if (got == 0) break;
+                }
+                p = e;
+            }
+            return 0;
+        }
         if (argc == 3 && std::string(argv[1]) == "placement") {
             const int k = atoi(argv[2]);
             if (k < mc::SK_M || k > 32) throw Error("placement: k from 15 to 32");
@@ -224,7 +279,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | pointers <pos>... | cutreads <reads> <keep> <out.fasta> <index> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | pointers <pos>... | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

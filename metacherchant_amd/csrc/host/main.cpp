@@ -30,6 +30,7 @@
 #include "gpu_compactor.h"
 #include "gpu_joiner.h"
 #include "mcgpu.h"
+#include "whole_reads_source.h"
 
 using namespace mch;
 
@@ -104,6 +105,9 @@ struct Options {
     // --join (environment-finder-multi): who joins the graph files and compacts the result (no counterpart in the reference; the files are the same)
     std::string join = "auto";
     bool join_given = false;
+    // --parse: who parses the whole reads of the classifying tools (no counterpart in the reference; the files are the same)
+    std::string parse = "auto";
+    bool parse_given = false;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -116,7 +120,7 @@ const OptSpec SPECS[] = {
     {"merge", nullptr, 1}, {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0},
     {"continue", "c", 1}, {"force", nullptr, 1}, {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0},
     {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"output-dir", nullptr, 0}, {"env", "e", 2}, {"geneid", "g", 0},
-    {"compact", nullptr, 0}, {"join", nullptr, 0},
+    {"compact", nullptr, 0}, {"join", nullptr, 0}, {"parse", nullptr, 0},
 };
 
 // --tool reads-classifier: its parameters (ReadsClassifier.java:42-95) and the launch options
@@ -124,7 +128,7 @@ const OptSpec CLASSIFIER_SPECS[] = {
     {"k", "k", 0}, {"input-files", "i", 2}, {"read-files", "r", 2}, {"output-dir", "o", 0}, {"correction", "corr", 1},
     {"hash", nullptr, 0}, {"interval95", nullptr, 1}, {"found-threshold", "found", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"parse", nullptr, 0},
 };
 
 // --tool triple-reads-classifier: its parameters (TripleReadsClassifier.java:40-105) and the launch options
@@ -133,7 +137,7 @@ const OptSpec TRIPLE_SPECS[] = {
     {"output-dir", "o", 0}, {"hash", nullptr, 0}, {"correction", "corr", 1}, {"interval95", nullptr, 1}, {"found-threshold", "found", 0},
     {"half-threshold", "half", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"parse", nullptr, 0},
 };
 
 // --tool seq-cov: its parameters (SequenceCoverage.java:30-72) and the launch options
@@ -141,7 +145,7 @@ const OptSpec SEQ_COV_SPECS[] = {
     {"k", "k", 0}, {"from-before", nullptr, 2}, {"from-donor", nullptr, 2}, {"from-both", nullptr, 2}, {"itself", nullptr, 2},
     {"read-file", "r", 0}, {"output-dir", "o", 0}, {"hash", nullptr, 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"parse", nullptr, 0},
 };
 
 // --tool recipient-visualiser: its parameters (RecipientVisualiser.java:42-92) and the launch options
@@ -149,7 +153,7 @@ const OptSpec RECIPIENT_SPECS[] = {
     {"k", "k", 0}, {"after-files", "after", 2}, {"seq", "seq", 0}, {"maxkmers", nullptr, 0}, {"maxradius", nullptr, 0}, {"hash", nullptr, 0},
     {"output-dir", "o", 0}, {"input-dir", "i", 0}, {"ext", "ext", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0}, {"parse", nullptr, 0},
 };
 
 // --tool fmt-visualizer: its parameters (FMTVisualizer.java:39-85) and the launch options
@@ -157,7 +161,7 @@ const OptSpec FMT_SPECS[] = {
     {"k", "k", 0}, {"donor-files", "donor", 2}, {"before-files", "before", 2}, {"after-files", "after", 2}, {"hash", nullptr, 0},
     {"output-dir", "o", 0}, {"input-dir", "i", 0}, {"ext", "ext", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0}, {"parse", nullptr, 0},
 };
 
 // --tool environment-assembler-finder: its parameters (EnvironmentAssemblerFinder.java:33-122) and the launch options
@@ -166,7 +170,7 @@ const OptSpec ASSEMBLER_SPECS[] = {
     {"coverage", nullptr, 0}, {"bothdirs", nullptr, 1}, {"chunklength", nullptr, 0}, {"forcehash", nullptr, 1}, {"hash", nullptr, 0},
     {"threads", nullptr, 0}, {"trim", nullptr, 1}, {"procfiltration", "pf", 0}, {"assembler", nullptr, 0}, {"assemblerpath", nullptr, 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0}, {"parse", nullptr, 0},
 };
 
 struct SpecTable {
@@ -293,6 +297,11 @@ Options parse_args(int argc, char **argv)
         if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--join takes host, gpu or auto, not '" + *v + "'");
         o.join = *v;
         o.join_given = true;
+    }
+    if (auto v = val("parse")) {
+        if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--parse takes host, gpu or auto, not '" + *v + "'");
+        o.parse = *v;
+        o.parse_given = true;
     }
     if (auto v = val("seq")) o.seq = *v;
     if (auto v = val("hicseq")) o.hicseq = *v;
@@ -433,6 +442,10 @@ void usage()
     puts("                --compact host|gpu|auto (environment-finder, environment-assembler-finder, recipient-visualiser, fmt-visualizer:");
     puts("                who compacts an environment's k-mers into unitigs; the files are the same; default auto: the GPU from");
     puts("                10000 k-mers on, the smallest size measured, where it already wins; the host below)");
+    puts("                --parse host|gpu|auto (the classifiers, seq-cov, fmt-visualizer, environment-assembler-finder: who parses the whole reads of");
+    puts("                -r / --read-file / the read filter.  host: one thread reads the records and the tool packs them; gpu: the text of an");
+    puts("                uncompressed FASTA / FASTQ file is tokenised on the device and stays there for the kernels; the files are the same;");
+    puts("                default auto: gpu for an uncompressed file of 31.6 MB or more, the smallest size measured, where it already wins)");
 }
 
 #define MC_CHECK(ctx, call)                                                       \
@@ -689,6 +702,12 @@ int run_multi(const Options &o)
 
 // WritersUtils.writeDnaQsToFastqFile (itmo!/io/writers/FastqDedicatedWriter.java:39-60): "@<n>" counting from 1 (DataCounter), the
 // bases with N printed as A (the DnaQ holds base 0 there), "+", the qualities as Illumina (phred + 64, Illumina.getPhredChar)
+// MC_INGEST_DEBUG=1: the time spent in FastqOut::put (rendering a record and its fwrite), summed over the writers, for the log line
+// "[ingest] FastqOut: ..." at the end of reads-classifier -- the share of the run that DESIGN.md 3.14 reports
+const bool g_time_writers = getenv("MC_INGEST_DEBUG") != nullptr;
+double g_fastq_out_s = 0;
+unsigned long long g_fastq_out_n = 0;
+
 struct FastqOut {
     FILE *f = nullptr;
     unsigned long long n = 0;
@@ -708,6 +727,7 @@ struct FastqOut {
     void put(const uint8_t *codes, const uint8_t *phred, size_t len)
     {
         if (len == 0) throw Error("Empty DnaQ!");
+        const auto t0 = g_time_writers ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
         rec = "@" + std::to_string(++n) + "\n";
         const size_t at = rec.size();
         rec.resize(at + 2 * len + 4);
@@ -719,6 +739,7 @@ struct FastqOut {
         }
         b[len] = '\n'; b[len + 1] = '+'; b[len + 2] = '\n'; q[len] = '\n';
         if (fwrite(rec.data(), 1, rec.size(), f) != rec.size()) throw Error("Failed to write to file " + path);
+        if (g_time_writers) { g_fastq_out_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); g_fastq_out_n++; }
     }
 };
 
@@ -746,17 +767,45 @@ struct SideList {
     }
 };
 
+// --parse: who reads the whole reads of a -r file.  host: DnaQReader on one thread, then the tool packs the bases and looks for the
+// low-quality positions itself; gpu: WholeReadsSource -- the text is tokenised on the device (mc_tokenize_whole_dev) and its words,
+// offsets and positions go into the _dev entry points where they are; auto: gpu for an uncompressed file of PARSE_AUTO_MIN bytes or
+// more.  That is the smallest file scripts/whole_reads_bench.py has timed (10^5 FASTQ records of 150 bases), and there the whole
+// reads-classifier is already faster the GPU's way; below it nothing is measured, and auto is host.
+constexpr uint64_t PARSE_AUTO_MIN = 31600000;
+
+bool parse_on_gpu(const Options &o, const std::string &path)
+{
+    std::string name = path;
+    for (char &c : name) c = (char)tolower((unsigned char)c);
+    auto ends = [&](const char *suffix) { const size_t n = strlen(suffix); return name.size() >= n && name.compare(name.size() - n, n, suffix) == 0; };
+    const bool compressed = ends(".gz") || ends(".bz2");
+    if (o.parse == "gpu") {
+        if (compressed) throw Error("--parse gpu reads uncompressed FASTA and FASTQ files, and " + path + " is compressed: use --parse host");
+        return true;
+    }
+    if (o.parse == "host" || compressed) return false;
+    struct stat st;
+    return stat(path.c_str(), &st) == 0 && (uint64_t)st.st_size >= PARSE_AUTO_MIN;
+}
+
+// a file of whole reads, read one way or the other
+struct ReadsIn {
+    std::unique_ptr<DnaQReader> host;
+    std::unique_ptr<WholeReadsSource> gpu;
+    mc_ctx *ctx;
+    ReadsIn(const Options &o, mc_ctx *c, const std::string &path) : ctx(c)
+    {
+        if (parse_on_gpu(o, path)) gpu.reset(new WholeReadsSource(ctx, o.device, path));
+        else host.reset(new DnaQReader(path));
+    }
+    size_t read(DnaQBatch &b, size_t max_reads, uint64_t max_bases = ~0ull) { return gpu ? gpu->read(b, max_reads, max_bases) : host->read(b, max_reads); }
+};
+
 // findReadWithCorrection's one low-quality position of each of the first n reads: -1 for none, -2 for several (mc_classify_reads)
 std::vector<int32_t> bad_positions(const DnaQBatch &b, size_t n)
 {
-    std::vector<int32_t> bad(n, -1);
-    for (size_t r = 0; r < n; r++)
-        for (uint64_t i = b.offsets[r]; i < b.offsets[r + 1]; i++)
-            if (b.phred[i] < 10) {
-                if (bad[r] != -1) { bad[r] = -2; break; }
-                bad[r] = (int32_t)(i - b.offsets[r]);
-            }
-    return bad;
+    return low_quality_positions(b, 0, n);
 }
 
 // one batch of whole reads through mc_classify_reads: N is base 0 already (DnaQReader), bad_pos as findReadWithCorrection counts
@@ -764,13 +813,20 @@ std::vector<mc_read_cov> classify_batch(mc_ctx *ctx, const DnaQBatch &b, size_t 
 {
     std::vector<mc_read_cov> out(n);
     if (n == 0) return out;
-    const uint64_t n_bases = b.offsets[n];
-    std::vector<uint64_t> words((n_bases + 31) / 32 + 1, 0);
-    for (uint64_t i = 0; i < n_bases; i++) words[i >> 5] |= (uint64_t)(b.codes[i] & 3) << (62 - 2 * (i & 31));
+    std::vector<uint64_t> words;
+    pack_whole_reads(b, 0, n, words, nullptr);
     const std::vector<int32_t> bad = o.correction ? bad_positions(b, n) : std::vector<int32_t>();
     MC_CHECK(ctx, mc_classify_reads(ctx, words.data(), b.offsets.data(), n, o.correction ? bad.data() : nullptr, (int)o.found_threshold,
                                     o.interval95 ? 1.96 : 1.0, o.correction ? MC_CLASSIFY_CORRECTION : 0, out.data()));
     return out;
+}
+
+// ... and the first n reads of a batch WholeReadsSource delivered, from its device view (defined behind DevArray)
+std::vector<mc_read_cov> classify_segments(mc_ctx *ctx, const std::vector<WholeSegment> &segs, size_t n, const Options &o);
+
+std::vector<mc_read_cov> classify_side(mc_ctx *ctx, const ReadsIn &in, const DnaQBatch &b, size_t n, const Options &o)
+{
+    return in.gpu ? classify_segments(ctx, in.gpu->segments(), n, o) : classify_batch(ctx, b, n, o);
 }
 
 // file.getName().toLowerCase().endsWith("kmers.bin"): loadGraph reads such a file as kmer-counter's output
@@ -833,8 +889,8 @@ int run_reads_classifier(const Options &o)
 
     info("Loading reads...");
     const bool paired = o.read_files.size() == 2;
-    DnaQReader r1(o.read_files[0]);
-    std::unique_ptr<DnaQReader> r2(paired ? new DnaQReader(o.read_files[1]) : nullptr);
+    ReadsIn r1(o, ctx, o.read_files[0]);
+    std::unique_ptr<ReadsIn> r2(paired ? new ReadsIn(o, ctx, o.read_files[1]) : nullptr);
     info(o.correction ? "Searching for corrected reads in graph..." : "Searching for reads in graph...");
     FastqOut found1(out_dir + "/found_1.fastq"), found2(out_dir + "/found_2.fastq"), nf1(out_dir + "/not_found_1.fastq"),
         nf2(out_dir + "/not_found_2.fastq"), found_s(out_dir + "/found_s.fastq"), nf_s(out_dir + "/not_found_s.fastq");
@@ -848,8 +904,8 @@ int run_reads_classifier(const Options &o)
         size_t n = r1.read(b1, BATCH);
         if (paired) n = r2->read(b2, n);  // PairSource (itmo!/io/sources/PairSource.java:35-45): pairs end with the shorter file
         if (n == 0) break;
-        const std::vector<mc_read_cov> c1 = classify_batch(ctx, b1, n, o);
-        const std::vector<mc_read_cov> c2 = paired ? classify_batch(ctx, b2, n, o) : std::vector<mc_read_cov>(n);
+        const std::vector<mc_read_cov> c1 = classify_side(ctx, r1, b1, n, o);
+        const std::vector<mc_read_cov> c2 = paired ? classify_side(ctx, *r2, b2, n, o) : std::vector<mc_read_cov>(n);
         for (size_t i = 0; i < n; i++) {
             const uint8_t *s1 = b1.codes.data() + b1.offsets[i], *q1 = b1.phred.data() + b1.offsets[i];
             const size_t l1 = b1.offsets[i + 1] - b1.offsets[i];
@@ -895,6 +951,7 @@ int run_reads_classifier(const Options &o)
     nf_s_tail.append_to(nf_s);
     for (FastqOut *f : {&found1, &found2, &nf1, &nf2, &found_s, &nf_s}) f->close();
     info("Reads have been written. Finishing...");
+    if (g_time_writers) fprintf(stderr, "[ingest] FastqOut: %.3f s in put() for %llu records\n", g_fastq_out_s, g_fastq_out_n);
     write_file(o.work_dir + "/SUCCESS", "");
     return 0;
 }
@@ -944,6 +1001,22 @@ struct DevArray {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+std::vector<mc_read_cov> classify_segments(mc_ctx *ctx, const std::vector<WholeSegment> &segs, size_t n, const Options &o)
+{
+    std::vector<mc_read_cov> out(n);
+    if (n == 0) return out;
+    DevArray cov;
+    cov.reserve(n * sizeof(mc_read_cov));
+    for (const WholeSegment &g : segs) {
+        if (g.first >= n) break;  // (pairs end with the shorter file: the longer one's batch may hold more reads)
+        const uint64_t m = std::min<uint64_t>(g.n_reads, n - g.first);
+        MC_CHECK(ctx, mc_classify_reads_dev(ctx, g.d_words, g.d_offsets, m, o.correction ? g.d_bad_pos : nullptr, (int)o.found_threshold,
+                                            o.interval95 ? 1.96 : 1.0, o.correction ? MC_CLASSIFY_CORRECTION : 0, cov.as<mc_read_cov>() + g.first));
+    }
+    hip_check(hipMemcpy(out.data(), cov.p, n * sizeof(mc_read_cov), hipMemcpyDeviceToHost), "hipMemcpy");
+    return out;
+}
+
 // one side of the pairs on the device, in mc_classify_reads' layout: words (the pad word included), offsets, bad positions
 struct SideStore {
     DevArray words, offsets, bad;
@@ -973,13 +1046,49 @@ struct SideStore {
         n_reads += n;
         n_bases = end;
     }
+    // --parse gpu: the first n reads of a batch's device view, joined behind what is here on the device (mc_reads_append_dev).  A store
+    // is filled one way or the other, never both (the host's way keeps the last word here).
+    void add_dev(mc_ctx *ctx, const std::vector<WholeSegment> &segs, const DnaQBatch &b, size_t n, bool correction)
+    {
+        if (n_reads == 0 && words.size == 0) {
+            const uint64_t z = 0;
+            words.put(0, &z, 8);
+            offsets.put(0, &z, 8);
+        }
+        const uint64_t end = n_bases + b.offsets[n];
+        words.reserve(((end + 31) / 32 + 1) * 8);
+        offsets.reserve((n_reads + n + 1) * 8);
+        if (correction) bad.reserve((n_reads + n) * 4);
+        uint64_t at_reads = n_reads, at_bases = n_bases;
+        for (const WholeSegment &g : segs) {
+            if (g.first >= n) break;  // (pairs end with the shorter file)
+            const uint64_t m = std::min<uint64_t>(g.n_reads, n - g.first);
+            MC_CHECK(ctx, mc_reads_append_dev(ctx, g.d_words, g.d_offsets, m, words.as<uint64_t>(), at_bases, offsets.as<uint64_t>() + at_reads));
+            if (correction && m) hip_check(hipMemcpy(bad.p + at_reads * 4, g.d_bad_pos, m * 4, hipMemcpyDeviceToDevice), "hipMemcpy");
+            at_bases += b.offsets[g.first + m] - b.offsets[g.first];
+            at_reads += m;
+        }
+        if (at_reads != n_reads + n || at_bases != end) throw Error("internal: a batch's device view does not cover it");
+        words.size = ((end + 31) / 32 + 1) * 8;
+        offsets.size = (n_reads + n + 1) * 8;
+        if (correction) bad.size = (n_reads + n) * 4;
+        n_reads += n;
+        n_bases = end;
+    }
 };
 
 // the pairs of two DnaQ readers, batch by batch: PairSource (itmo!/io/sources/PairSource.java:35-45) ends them with the shorter file
 template <typename F>
 void for_each_pair_batch(const Options &o, F &&f)
 {
-    DnaQReader r1(o.read_files[0]), r2(o.read_files[1]);
+    Engine T;  // (--parse gpu: any context tokenises; the graphs are not loaded yet)
+    if (parse_on_gpu(o, o.read_files[0]) || parse_on_gpu(o, o.read_files[1])) {
+        mc_config cfg{};
+        cfg.k = o.k;
+        cfg.device = o.device;
+        T.open(cfg, {});
+    }
+    ReadsIn r1(o, T.c, o.read_files[0]), r2(o, T.c, o.read_files[1]);
     constexpr size_t BATCH = 1u << 20;
     DnaQBatch b1, b2;
     for (;;) {
@@ -988,7 +1097,7 @@ void for_each_pair_batch(const Options &o, F &&f)
         size_t n = r1.read(b1, BATCH);
         n = r2.read(b2, n);
         if (n == 0) break;
-        f(b1, b2, n);
+        f(b1, b2, n, r1, r2);
         if (n < BATCH) break;  // (one of the files is done)
     }
 }
@@ -1020,9 +1129,13 @@ int run_triple_reads_classifier(const Options &o)
     info("Loading reads...");
     hip_check(hipSetDevice(o.device), "hipSetDevice");
     SideStore side[2];
-    for_each_pair_batch(o, [&](const DnaQBatch &b1, const DnaQBatch &b2, size_t n) {
-        side[0].add(b1, n, o.correction);
-        side[1].add(b2, n, o.correction);
+    for_each_pair_batch(o, [&](const DnaQBatch &b1, const DnaQBatch &b2, size_t n, const ReadsIn &r1, const ReadsIn &r2) {
+        const DnaQBatch *b[2] = {&b1, &b2};
+        const ReadsIn *r[2] = {&r1, &r2};
+        for (int s = 0; s < 2; s++) {
+            if (r[s]->gpu) side[s].add_dev(r[s]->ctx, r[s]->gpu->segments(), *b[s], n, o.correction);
+            else side[s].add(*b[s], n, o.correction);
+        }
     });
     const uint64_t n = side[0].n_reads;
 
@@ -1095,7 +1208,7 @@ int run_triple_reads_classifier(const Options &o)
         found_s(out_dir + "/found_s.fastq"), half_s(out_dir + "/half_found_s.fastq"), nf_s(out_dir + "/not_found_s.fastq");
     FastqOut *pair_out[3][2] = {{&nf1, &nf2}, {&half1, &half2}, {&found1, &found2}}, *single_out[3] = {&nf_s, &half_s, &found_s};
     uint64_t at = 0;
-    for_each_pair_batch(o, [&](const DnaQBatch &b1, const DnaQBatch &b2, size_t m) {
+    for_each_pair_batch(o, [&](const DnaQBatch &b1, const DnaQBatch &b2, size_t m, const ReadsIn &, const ReadsIn &) {
         if (at + m > n) throw Error("The read files changed while they were being classified");
         for (size_t i = 0; i < m; i++, at++) {
             const DnaQBatch *b[2] = {&b1, &b2};
@@ -1122,16 +1235,24 @@ int run_triple_reads_classifier(const Options &o)
 // window).  Nothing walks these tables: no read store is kept, and a table's counting scratch goes back before the next is counted.
 struct SeqCovBin { const char *param; const std::vector<std::string> *files; };
 
-// one batch of whole sequences through mc_seq_coverage, and its rows
-void seq_cov_batch(mc_ctx *const *tables, const DnaQBatch &b, int k, FILE *out)
+// one batch of whole sequences through mc_seq_coverage, and its rows.  segs: the batch's device view (--parse gpu), else NULL
+void seq_cov_batch(mc_ctx *const *tables, const DnaQBatch &b, int k, FILE *out, const std::vector<WholeSegment> *segs = nullptr)
 {
     const size_t n = b.n_reads();
     if (n == 0) return;
-    const uint64_t n_bases = b.offsets[n];
-    std::vector<uint64_t> words((n_bases + 31) / 32 + 1, 0);
-    for (uint64_t i = 0; i < n_bases; i++) words[i >> 5] |= (uint64_t)(b.codes[i] & 3) << (62 - 2 * (i & 31));
     std::vector<mc_seq_cov> cov(n * 4);
-    MC_CHECK(tables[0], mc_seq_coverage(tables, 4, words.data(), b.offsets.data(), n, cov.data()));
+    if (segs) {
+        DevArray d_cov;
+        d_cov.reserve(n * 4 * sizeof(mc_seq_cov));
+        for (const WholeSegment &g : *segs)
+            MC_CHECK(tables[0], mc_seq_coverage_dev(tables, 4, g.d_words, g.d_offsets, g.n_reads, d_cov.as<mc_seq_cov>() + g.first * 4));
+        hip_check(hipMemcpy(cov.data(), d_cov.p, n * 4 * sizeof(mc_seq_cov), hipMemcpyDeviceToHost), "hipMemcpy");
+    } else {
+        const uint64_t n_bases = b.offsets[n];
+        std::vector<uint64_t> words((n_bases + 31) / 32 + 1, 0);
+        for (uint64_t i = 0; i < n_bases; i++) words[i >> 5] |= (uint64_t)(b.codes[i] & 3) << (62 - 2 * (i & 31));
+        MC_CHECK(tables[0], mc_seq_coverage(tables, 4, words.data(), b.offsets.data(), n, cov.data()));
+    }
     std::string line;
     for (size_t s = 0; s < n; s++) {
         const uint64_t len = b.offsets[s + 1] - b.offsets[s];
@@ -1187,7 +1308,7 @@ int run_seq_cov(const Options &o)
     }
 
     info("Calculating sequence coverage...");
-    DnaQReader reader(o.read_file);
+    ReadsIn reader(o, tables[0], o.read_file);
     FILE *out = fopen((out_dir + "/seq_cov.csv").c_str(), "w");
     if (!out) throw Error("cannot create " + out_dir + "/seq_cov.csv");
     struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{out};
@@ -1199,6 +1320,12 @@ int run_seq_cov(const Options &o)
     DnaQBatch b;
     b.clear();
     for (;;) {
+        if (reader.gpu) {  // (a batch a call: the device view is of the batch the call delivered)
+            b.clear();
+            if (reader.read(b, BATCH_SEQS, BATCH_BASES) == 0) break;
+            seq_cov_batch(tables, b, o.k, out, &reader.gpu->segments());
+            continue;
+        }
         const size_t got = reader.read(b, 1);
         if (got == 0 || b.codes.size() >= BATCH_BASES || b.n_reads() >= BATCH_SEQS) {
             seq_cov_batch(tables, b, o.k, out);
@@ -1456,8 +1583,23 @@ void fmt_phase(const Options &o, int mode, const std::string &name, const std::v
     // ReadersUtils.loadDnaQs: the phase's reads again, every record whole, N as A
     DnaQBatch seqs;
     seqs.clear();
+    // --parse gpu (every file of the phase, or none): the reads stay on the device, joined into one array for mc_components_dev
+    bool on_gpu = !files.empty();
+    for (const std::string &f : files) on_gpu = parse_on_gpu(o, f) && on_gpu;
+    SideStore dev_seqs;
     try {
         for (const std::string &f : files) {
+            if (on_gpu) {
+                WholeReadsSource src(G.c, o.device, f, false);
+                DnaQBatch b;
+                for (;;) {
+                    b.clear();
+                    const size_t got = src.read(b, 1u << 20);
+                    if (got == 0) break;
+                    dev_seqs.add_dev(G.c, src.segments(), b, got, false);
+                }
+                continue;
+            }
             DnaQReader reader(f);
             while (reader.read(seqs, 1u << 16)) {}
         }
@@ -1473,7 +1615,8 @@ void fmt_phase(const Options &o, int mode, const std::string &name, const std::v
         mc_components_result &r;
         ~ResGuard() { mc_components_free(&r); }
     } guard{res};
-    MC_CHECK(G.c, mc_components(G.c, words.data(), seqs.offsets.data(), seqs.n_reads(), &res));
+    if (on_gpu) MC_CHECK(G.c, mc_components_dev(G.c, dev_seqs.words.as<uint64_t>(), dev_seqs.offsets.as<uint64_t>(), dev_seqs.n_reads, &res));
+    else MC_CHECK(G.c, mc_components(G.c, words.data(), seqs.offsets.data(), seqs.n_reads(), &res));
     std::vector<uint8_t> mask(res.n_kmers);
     if (res.n_kmers) MC_CHECK(tables[0], mc_kmer_presence(tables, nt, res.hi, res.lo, res.n_kmers, mask.data()));
     const std::string out_dir = out_root + "/" + name;
@@ -1604,10 +1747,22 @@ void run_assembler(const Options &o, const std::string &prefix, size_t i)
 
 // one batch of whole reads through mc_reads_in_set_dev; the kept ones go to the writer
 void filter_batch(mc_ctx *ctx, const DnaQBatch &b, const DevArray &set_hi, const DevArray &set_lo, uint64_t n_set, int k, int pct, DevArray &dev,
-                  CutReadsWriter &out)
+                  CutReadsWriter &out, const std::vector<WholeSegment> *segs = nullptr)
 {
     const size_t n = b.n_reads();
     if (n == 0) return;
+    if (segs) {  // --parse gpu: the batch's device view, a segment a launch; hits and keep in one block
+        dev.size = 0;
+        dev.reserve(n * 4 + n);
+        for (const WholeSegment &g : *segs)
+            MC_CHECK(ctx, mc_reads_in_set_dev(ctx, g.d_words, g.d_offsets, g.n_reads, k > 32 ? set_hi.as<uint64_t>() : nullptr, set_lo.as<uint64_t>(), n_set, pct,
+                                              0, dev.as<uint32_t>() + g.first, reinterpret_cast<uint8_t *>(dev.p + n * 4) + g.first));
+        std::vector<uint8_t> keep(n);
+        hip_check(hipMemcpy(keep.data(), dev.p + n * 4, n, hipMemcpyDeviceToHost), "hipMemcpy");
+        for (size_t r = 0; r < n; r++)
+            if (keep[r]) out.add(b.codes.data() + b.offsets[r], (size_t)(b.offsets[r + 1] - b.offsets[r]));
+        return;
+    }
     const uint64_t n_bases = b.offsets[n];
     std::vector<uint64_t> words((n_bases + 31) / 32 + 1, 0);
     for (uint64_t i = 0; i < n_bases; i++) words[i >> 5] |= (uint64_t)(b.codes[i] & 3) << (62 - 2 * (i & 31));
@@ -1723,10 +1878,16 @@ bool assembler_finder_phase(const Options &o, int k, int coverage, const std::ve
     constexpr size_t BATCH_READS = 1u << 22;
     for (size_t i = 0; i < reads.size(); i++) {
         CutReadsWriter out(prefix + "cutReads" + std::to_string(i) + ".fasta", (int)i);
-        DnaQReader reader(reads[i]);
+        ReadsIn reader(o, E.c, reads[i]);
         DnaQBatch b;
         b.clear();
         for (;;) {
+            if (reader.gpu) {  // (a batch a call: the device view is of the batch the call delivered)
+                b.clear();
+                if (reader.read(b, BATCH_READS, BATCH_BASES) == 0) break;
+                filter_batch(E.c, b, set_hi, set_lo, members.size(), k, (int)o.procfiltration, dev, out, &reader.gpu->segments());
+                continue;
+            }
             const size_t got = reader.read(b, 1u << 14);
             if (got == 0 || b.codes.size() >= BATCH_BASES || b.n_reads() >= BATCH_READS) {
                 filter_batch(E.c, b, set_hi, set_lo, members.size(), k, (int)o.procfiltration, dev, out);
@@ -1782,6 +1943,9 @@ int run(const Options &o)
     if (o.compact_given && (o.tool == "kmer-counter" || o.tool == "environment-finder-multi"))  // (they share environment-finder's table)
         throw Error("--compact does not apply to --tool " + o.tool);
     if (o.join_given && o.tool != "environment-finder-multi") throw Error("--join does not apply to --tool " + o.tool);
+    if (o.parse_given && o.tool != "reads-classifier" && o.tool != "triple-reads-classifier" && o.tool != "seq-cov" && o.tool != "fmt-visualizer" &&
+        o.tool != "environment-assembler-finder")
+        throw Error("--parse does not apply to --tool " + o.tool);
     if (o.tool == "kmer-counter") return run_kmer_counter(o);
     if (o.tool == "environment-finder-multi") return run_multi(o);
     if (o.tool == "reads-classifier") return run_reads_classifier(o);

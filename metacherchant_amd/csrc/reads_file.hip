@@ -8,7 +8,7 @@
 #include "host/envfinder.h"
 
 // exclusive scan of n 32-bit counts into 64-bit offsets; *total on the host
-static int tok_scan(mc_ctx *c, const uint32_t *d_in, uint64_t n, unsigned long long *d_out, uint64_t *total)
+int tok_scan(mc_ctx *c, const uint32_t *d_in, uint64_t n, unsigned long long *d_out, uint64_t *total)
 {
     const uint64_t m = std::max<uint64_t>((n + tok::SCAN_TILE - 1) / tok::SCAN_TILE, 1);
     PoolBuf<unsigned long long> sums;
@@ -21,6 +21,24 @@ static int tok_scan(mc_ctx *c, const uint32_t *d_in, uint64_t n, unsigned long l
     HIPCHK(c, hipMemcpyAsync(&t, sums.p + m, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *total = t;
+    return MC_OK;
+}
+
+// pass 1 of both tokenisers: the positions of the n_nl newlines of d_text[0, n), which is padded with zero bytes to whole tiles
+int tok_newlines(mc_ctx *c, const uint8_t *d_text, uint64_t n, TokNewlines *b, uint64_t *n_nl, bool *too_many)
+{
+    *too_many = false;
+    *n_nl = 0;
+    const uint64_t n_tiles = (n + tok::T_TILE - 1) / tok::T_TILE;
+    if (n_tiles > 0x7FFFFFFFull) { *too_many = true; return MC_OK; }
+    HIPCHK(c, b->tile_counts.alloc(&c->tok_pool, n_tiles));
+    HIPCHK(c, b->tile_off.alloc(&c->tok_pool, n_tiles));
+    hipLaunchKernelGGL(tok::k_nl_count, dim3((unsigned)n_tiles), dim3(tok::T_THREADS), 0, c->stream, d_text, b->tile_counts.p);
+    int rc = tok_scan(c, b->tile_counts.p, n_tiles, b->tile_off.p, n_nl);
+    if (rc) return rc;
+    HIPCHK(c, b->nl.alloc(&c->tok_pool, *n_nl));
+    hipLaunchKernelGGL(tok::k_nl_write, dim3((unsigned)n_tiles), dim3(tok::T_THREADS), 0, c->stream, d_text, b->tile_off.p, b->nl.p);
+    HIPCHK(c, hipGetLastError());
     return MC_OK;
 }
 
@@ -59,19 +77,13 @@ int tokenize_chunk_locked(mc_ctx *c, const mch::PlainReadsFile &f, const char *b
     HIPCHK(c, flags.alloc(&c->tok_pool, 1));
     HIPCHK(c, hipMemsetAsync(flags.p, 0, 4, c->stream));
     // pass 1: newline positions
-    const uint64_t n_tiles = (n + tok::T_TILE - 1) / tok::T_TILE;
-    if (n_tiles > 0x7FFFFFFFull) { *declined = true; return MC_OK; }
-    PoolBuf<uint32_t> tile_counts;
-    PoolBuf<unsigned long long> tile_off, nl;
-    HIPCHK(c, tile_counts.alloc(&c->tok_pool, n_tiles));
-    HIPCHK(c, tile_off.alloc(&c->tok_pool, n_tiles));
-    hipLaunchKernelGGL(tok::k_nl_count, dim3((unsigned)n_tiles), dim3(tok::T_THREADS), 0, c->stream, text.p, tile_counts.p);
+    TokNewlines nlb;  // (as before: the pass's buffers live as long as this call, and nothing waits for the pass here)
+    PoolBuf<unsigned long long> &nl = nlb.nl;
     uint64_t n_nl = 0;
-    rc = tok_scan(c, tile_counts.p, n_tiles, tile_off.p, &n_nl);
+    bool too_many = false;
+    rc = tok_newlines(c, text.p, n, &nlb, &n_nl, &too_many);
     if (rc) return rc;
-    HIPCHK(c, nl.alloc(&c->tok_pool, n_nl));
-    hipLaunchKernelGGL(tok::k_nl_write, dim3((unsigned)n_tiles), dim3(tok::T_THREADS), 0, c->stream, text.p, tile_off.p, nl.p);
-    HIPCHK(c, hipGetLastError());
+    if (too_many) { *declined = true; return MC_OK; }
     const uint64_t n_lines = n_nl + (e[-1] != '\n' ? 1 : 0);
     if (n_lines >= 0xFFFFFFF0ull) { *declined = true; return MC_OK; }
 

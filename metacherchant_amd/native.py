@@ -86,6 +86,14 @@ class _EnvJoin(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+class _WholeReads(C.Structure):
+    """mc_whole_reads"""
+    _fields_ = [("declined", C.c_int), ("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("d_words", C.c_void_p), ("d_offsets", C.c_void_p),
+                ("d_bad_pos", C.c_void_p), ("d_codes", C.c_void_p), ("d_phred", C.c_void_p), ("device_ms", C.c_double)]
+
+
+WHOLE_FASTA, WHOLE_FASTQ = 0, 1  # mc_tokenize_whole format
+WHOLE_CODES, WHOLE_PHRED = 1, 2  # mc_tokenize_whole flags
 READ_COV_DTYPE = np.dtype([("sum", np.int32), ("covered", np.int32), ("last", np.int16), ("found", np.uint8), ("pad", np.uint8)])
 CLASSIFY_CORRECTION = 1  # mc_classify_reads flags: findReadWithCorrection
 LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fingerprint, so distinct reads share one
@@ -109,6 +117,7 @@ EXPORTS = [
     "mc_kmer_presence", "mc_kmer_presence_dev", "mc_reads_in_set", "mc_reads_in_set_dev",
     "mc_components", "mc_components_dev", "mc_components_free", "mc_unitigs", "mc_unitigs_dev", "mc_unitigs_free",
     "mc_env_join", "mc_env_join_dev", "mc_env_join_free",
+    "mc_tokenize_whole", "mc_tokenize_whole_dev", "mc_whole_text_bytes", "mc_whole_reads_to_host", "mc_whole_reads_free", "mc_reads_append_dev",
 ]
 
 _LIB = None
@@ -220,6 +229,16 @@ def load():
         L.mc_env_join_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, C.c_uint32, vp, u64, C.POINTER(_EnvJoin)]
         L.mc_env_join_free.argtypes = [C.POINTER(_EnvJoin)]
         L.mc_env_join_free.restype = None
+    if hasattr(L, "mc_tokenize_whole"):
+        wr = C.POINTER(_WholeReads)
+        L.mc_tokenize_whole.argtypes = [vp, C.c_char_p, u64, i32, i32, C.c_uint32, wr]
+        L.mc_tokenize_whole_dev.argtypes = [vp, vp, u64, i32, i32, i32, C.c_uint32, wr]
+        L.mc_whole_text_bytes.argtypes = [u64]
+        L.mc_whole_text_bytes.restype = u64
+        L.mc_whole_reads_to_host.argtypes = [vp, wr, vp, vp, vp, vp, vp]
+        L.mc_whole_reads_free.argtypes = [vp, wr]
+        L.mc_whole_reads_free.restype = None
+        L.mc_reads_append_dev.argtypes = [vp, vp, vp, u64, vp, u64, vp]
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -833,6 +852,80 @@ def env_join_dev(context, d_hi, d_lo, n, d_rec_hi, d_rec_lo, d_rec_depth, d_grap
     context._chk(load().mc_env_join_dev(context._h, _dptr(d_hi), _dptr(d_lo), int(n), _dptr(d_rec_hi), _dptr(d_rec_lo), _dptr(d_rec_depth),
                                         _dptr(d_graph_offsets), int(n_graphs), _dptr(d_gene), int(gene_len), C.byref(r)))
     return _env_join_result(r)
+
+
+class WholeReadsDev:
+    """A result of mc_tokenize_whole in device memory: n_reads, n_bases, device_ms and the device pointers (ints) d_words, d_offsets,
+    d_bad_pos, d_codes, d_phred (0 when not asked for), ready for the *_dev calls.  free() -- or leaving a `with` block -- gives the
+    memory back; to_host() returns numpy copies."""
+
+    def __init__(self, context, res):
+        self._context, self._res = context, res
+        self.n_reads, self.n_bases, self.device_ms = int(res.n_reads), int(res.n_bases), float(res.device_ms)
+
+    d_words = property(lambda self: self._res.d_words or 0)
+    d_offsets = property(lambda self: self._res.d_offsets or 0)
+    d_bad_pos = property(lambda self: self._res.d_bad_pos or 0)
+    d_codes = property(lambda self: self._res.d_codes or 0)
+    d_phred = property(lambda self: self._res.d_phred or 0)
+
+    def to_host(self):
+        """dict of numpy arrays: words (with the pad word), offsets, bad_pos, and codes / phred (None when not asked for)"""
+        nr, nb = self.n_reads, self.n_bases
+        out = {"words": np.zeros((nb + 31) // 32 + 1, dtype=np.uint64), "offsets": np.zeros(nr + 1, dtype=np.uint64),
+               "bad_pos": np.zeros(nr, dtype=np.int32), "codes": np.zeros(nb, dtype=np.uint8) if self._res.d_codes else None,
+               "phred": np.zeros(nb, dtype=np.uint8) if self._res.d_phred else None}
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        self._context._chk(load().mc_whole_reads_to_host(self._context._h, C.byref(self._res), ptr(out["words"]), ptr(out["offsets"]),
+                                                         ptr(out["bad_pos"]), ptr(out["codes"]), ptr(out["phred"])))
+        return out
+
+    def free(self):
+        if self._res is not None and getattr(self._context, "_h", None):
+            load().mc_whole_reads_free(self._context._h, C.byref(self._res))
+        self._res = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # (interpreter shutdown)
+            pass
+
+
+def reads_append_dev(context, d_words, d_offsets, n_reads, d_dst_words, dst_bases, d_dst_offsets):
+    """mc_reads_append_dev: n_reads reads of a device view (d_offsets: n_reads + 1 base positions in d_words, the first need not be 0) go
+    behind the dst_bases bases of d_dst_words; d_dst_offsets (the destination's entry of the first new read) gets n_reads + 1 entries"""
+    context._chk(load().mc_reads_append_dev(context._h, _dptr(d_words), _dptr(d_offsets), int(n_reads), _dptr(d_dst_words), int(dst_bases),
+                                            _dptr(d_dst_offsets)))
+
+
+def tokenize_whole_dev(context, text, fastq, phred_offset=33, codes=True, phred=True):
+    """mc_tokenize_whole: the whole reads of FASTQ (fastq=True; phred_offset 33 or 64) or FASTA text (bytes: a whole number of
+    records) with DnaQReader's policy, left in device memory.  Returns a WholeReadsDev, or None when the device declined the text (the
+    host reader defines what such a text gives).  Any context will do: its table plays no part."""
+    text = bytes(text)
+    r = _WholeReads()
+    context._chk(load().mc_tokenize_whole(context._h, text, len(text), WHOLE_FASTQ if fastq else WHOLE_FASTA, int(phred_offset),
+                                          (WHOLE_CODES if codes else 0) | (WHOLE_PHRED if phred else 0), C.byref(r)))
+    return None if r.declined else WholeReadsDev(context, r)
+
+
+def tokenize_whole(context, text, fastq, phred_offset=33, codes=True, phred=True):
+    """tokenize_whole_dev, copied back: a dict of numpy arrays words, offsets, bad_pos, codes, phred (the last two None when not asked
+    for) and n_reads, n_bases, device_ms; or None when the device declined the text."""
+    d = tokenize_whole_dev(context, text, fastq, phred_offset, codes, phred)
+    if d is None:
+        return None
+    with d:
+        out = d.to_host()
+        out.update(n_reads=d.n_reads, n_bases=d.n_bases, device_ms=d.device_ms)
+        return out
 
 
 def key_owner(key, n_owners):
