@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_skl_extract(
     uint64_t cap, uint4 *out_recs, SklSpill sp, uint32_t chunk_tiles, uint32_t two)
 {   // two: the bin word from the two smallest hashes of a window (skl_word2)
     __shared__ Sk1lLds L;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = p1w_wave(tid);
     for (uint32_t i = tid; i < PT_MAX_BUCKETS1_SK; i += P1W_THREADS) L.wcur[i] = 0;
     uint32_t *starts = L.starts[wv];
     uint32_t *brkw = L.brk[wv];
@@ -252,8 +252,8 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_skl_extract(
         }
 
         // ---- which of my positions start a window, and where runs of equal minimizers break
-        uint32_t valid_bits = 0;
-        if (lane < P1L_LANES && p0 + (uint64_t)k <= n_bases) {
+        uint32_t valid_bits;
+        {
             // window j lies inside one read iff no read starts at p0 + j + 1 .. p0 + j + k - 1: bit j of the OR of S >> 0 .. k - 2
             auto shr_or = [&](uint32_t n) {
                 if (n == 0) return;
@@ -263,42 +263,28 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_skl_extract(
             uint32_t width = 1;
             for (; 2 * width <= (uint32_t)k - 1; width *= 2) shr_or(width);  // (uniform: five or six rounds)
             shr_or((uint32_t)k - 1 - width);
-            const uint64_t jmax = n_bases - (uint64_t)k - p0;  // last j with p0 + j + k <= n_bases
-            const uint32_t jm = jmax < 7 ? (uint32_t)jmax : 7u;
-            const uint32_t j0 = p0 >= base_lo ? 0u : (base_lo - p0 < 8 ? (uint32_t)(base_lo - p0) : 8u);  // first j with p0 + j >= base_lo
-            valid_bits = ~(uint32_t)S_lo & ((2u << jm) - 1u) & ~((1u << j0) - 1u) & 0xFFu;
-        }
-        uint32_t brk_bits = 0;  // bit j: my window j breaks the run of equal minimizers (or is no window)
-        {
-            const uint32_t last = (valid_bits >> (PT_ITEMS - 1)) & 1u ? hmin[PT_ITEMS - 1] : SK_NONE;
-            uint32_t prev = __shfl_up(last, 1);
-            if (lane == 0) prev = SK_NONE;  // a tile always starts a run
-            uint32_t bits = 0;
-#pragma unroll
-            for (int j = 0; j < PT_ITEMS; j++) {
-                const bool v = (valid_bits >> j) & 1u;
-                if (!v || prev == SK_NONE || prev != hmin[j]) bits |= 1u << j;
-                prev = v ? hmin[j] : SK_NONE;
+            // which of my positions lie in [base_lo, n_bases - k]: all of them unless this is the first or the last tile of a run
+            uint32_t edge = lane < P1L_LANES ? 0xFFu : 0u;
+            if (lo < base_lo || lo + P1L_TILE + (uint64_t)k > n_bases + 1) {
+                edge = 0;
+                if (lane < P1L_LANES && p0 + (uint64_t)k <= n_bases) {
+                    const uint64_t jmax = n_bases - (uint64_t)k - p0;  // last j with p0 + j + k <= n_bases
+                    const uint32_t jm = jmax < 7 ? (uint32_t)jmax : 7u;
+                    const uint32_t j0 = p0 >= base_lo ? 0u : (base_lo - p0 < 8 ? (uint32_t)(base_lo - p0) : 8u);  // first j with p0 + j >= base_lo
+                    edge = ((2u << jm) - 1u) & ~((1u << j0) - 1u) & 0xFFu;
+                }
             }
-            brkb[2 + lane] = (uint8_t)bits;  // window i of the tile <-> bit 16 + i of the wave's break bitmap
-            brk_bits = bits;
+            valid_bits = ~(uint32_t)S_lo & edge;
         }
+        // bit j: my window j breaks the run of equal minimizers (or is no window); a window starts a record when it breaks the run
+        // or sits a multiple of 32 windows behind the run's first (count_pipeline.h sk_break_bits, sk_start_bits)
+        const uint32_t last = (valid_bits >> (PT_ITEMS - 1)) & 1u ? hmin[PT_ITEMS - 1] : SK_NONE;
+        const uint32_t prev = wave_from_prev(last, SK_NONE);  // (a tile always starts a run)
+        const uint32_t brk_bits = two ? sk_break_bits<PT_ITEMS, true>(hmin, valid_bits, prev) : sk_break_bits<PT_ITEMS, false>(hmin, valid_bits, prev);
+        brkb[2 + lane] = (uint8_t)brk_bits;  // window i of the tile <-> bit 16 + i of the wave's break bitmap
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        uint32_t start_bits = 0;  // a window starts a record when it breaks the run or sits a multiple of 32 windows behind the run's first
-        {
-            const unsigned long long holders = __ballot(brk_bits != 0);  // (lane 0 is one: a tile always starts a run)
-            const unsigned long long below = holders & ((1ull << lane) - 1ull);
-            const uint32_t P = below ? 63u - (uint32_t)__builtin_clzll(below) : 0u;
-            const uint32_t bp = (uint32_t)__shfl((int)brk_bits, (int)P);
-            uint32_t cur = P * PT_ITEMS + (31u - (uint32_t)__builtin_clz(bp | 1u));
-#pragma unroll
-            for (int j = 0; j < PT_ITEMS; j++) {
-                const uint32_t pos = lane * PT_ITEMS + (uint32_t)j;
-                cur = (brk_bits >> j) & 1u ? pos : cur;
-                if (((valid_bits >> j) & 1u) && ((pos - cur) % SKL_MAX_WINDOWS) == 0) start_bits |= 1u << j;
-            }
-        }
+        const uint32_t start_bits = sk_start_bits<PT_ITEMS, SKL_MAX_WINDOWS>(lane, valid_bits, brk_bits);
 
         // ---- records: the tile's starts lined up, lane i builds the i-th record (k_sk1w_extract says why)
         {

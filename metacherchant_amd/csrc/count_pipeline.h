@@ -602,6 +602,54 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v)
     return v;
 }
 
+// Run bookkeeping of the extract kernels (k_sk1w_extract here, k_skl_extract in count_long.h), as mask arithmetic on a lane's N
+// windows instead of a predicated block a window.  `valid`: bit j <-> my window j is a window of one read; `prev`: the minimizer
+// hash of the window before my first one, SK_NONE when that is no window (lane 0: a tile always starts a run).
+//
+// Break bits: window j breaks the run of equal minimizers when it or the window before it is no window or their hashes differ.
+// sk_order never gives SK_NONE for an SK_M-mer (kmer_hash.h), so "the window before is none" needs no test of its own at
+// bit 0 -- prev == SK_NONE differs from every window's hash --; CAN_BE_NONE: the hash is a mixed word that may be SK_NONE
+// (count_long.h skl_word2), and a window behind such a one breaks the run as it always has.
+template <int N, bool CAN_BE_NONE>
+__device__ __forceinline__ uint32_t sk_break_bits(const uint32_t (&hmin)[N], uint32_t valid, uint32_t prev)
+{
+    uint32_t ne = 0;  // bit j: the hash of window j is not that of window j - 1
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const uint32_t before = j ? hmin[j > 0 ? j - 1 : 0] : prev;  // (the inner test keeps the index in range for j = 0)
+        bool d = before != hmin[j];
+        if (CAN_BE_NONE) d |= before == SK_NONE;
+        ne |= (uint32_t)d << j;
+    }
+    return (~valid | ~((valid << 1) | 1u) | ne) & ((1u << N) - 1u);
+}
+
+// Start bits: a window starts a record when it breaks the run or sits a multiple of MAXW windows behind the run's first window.
+// Where did the run start?  The last lane below mine that holds a break is a ballot and a count of leading zeros away, its break
+// bits one cross-lane read: `cur` = the tile window of the last break before my first window.  Behind a break of my own a
+// window is fewer than N <= MAXW windows from it, so it starts a record only by being a break; in front of my first break
+// exactly one window index is a multiple of MAXW from cur, (cur - lane * N) mod MAXW, and it counts when it lies there.
+// (Lane 0 always holds break bit 0, so nothing lies in front of its first break and its cur is not used.)
+// tests/test_extract_bookkeeping_model.py holds this against the rule stated window by window.
+template <int N, uint32_t MAXW>
+__device__ __forceinline__ uint32_t sk_start_bits(uint32_t lane, uint32_t valid, uint32_t brk)
+{
+    static_assert(N <= 16 && N <= (int)MAXW && (MAXW & (MAXW - 1)) == 0 && MAXW <= 32, "one deep start a lane at most");
+    const unsigned long long holders = __ballot(brk != 0);
+    const unsigned long long below = holders & ((1ull << lane) - 1ull);
+    const uint32_t P = below ? 63u - (uint32_t)__builtin_clzll(below) : 0u;
+    const uint32_t bp = (uint32_t)__shfl((int)brk, (int)P);
+    const uint32_t cur = P * N + (31u - (uint32_t)__builtin_clz(bp | 1u));
+    const uint32_t low = (brk & (0u - brk)) - 1u;  // the bits below my first break (all of them when I hold none)
+    const uint32_t deep = (1u << ((cur - lane * N) & (MAXW - 1u))) & low;
+    return valid & (brk | deep);
+}
+
+// the wave's number in its workgroup, in a scalar register: the compiler then knows that the tile, its bounds, its first read and
+// the tile-edge test are the same for all lanes and keeps them in scalar registers and on the scalar unit (of a plain tid >> 6
+// it does not: 28 vector instructions and 9 vector registers more in k_sk1w_extract, 3.21 ms against 3.05 ms on configs[1])
+__device__ __forceinline__ uint32_t p1w_wave(uint32_t tid) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)); }
+
 struct alignas(16) Sk1wLds {
     uint32_t wcur[PT_MAX_BUCKETS1_SK];  // this workgroup's fill level of every bucket
     uint32_t starts[P1W_WAVES][24];    // per wave: bit b <-> "a read starts at position lo - 64 + b" (704 bits used)
@@ -613,9 +661,16 @@ struct alignas(16) Sk1wLds {
 #endif
 };
 
+// Moves between neighbouring lanes of the wave as DPP wave shifts: one vector move each.  (As __shfl_down / __shfl_up they were
+// ds_bpermute_b32, 18 a tile through the LDS port with an address register and a wait each: the extract kernel took 3.05 ms
+// with them and 2.97 ms without on configs[1], HISTORY.md.)
 __device__ __forceinline__ uint32_t wave_from_next(uint32_t x)
-{  // lane i <- lane i + 1 (lane 63: unspecified)
-    return __shfl_down(x, 1);
+{  // lane i <- lane i + 1 (lane 63 <- 0)
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x130, 0xF, 0xF, true);  // wave_shl:1
+}
+__device__ __forceinline__ uint32_t wave_from_prev(uint32_t x, uint32_t first)
+{  // lane i <- lane i - 1, lane 0 <- first
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)first, (int)x, 0x138, 0xF, 0xF, false);  // wave_shr:1 (lane 0 has no source and keeps `first`)
 }
 
 // 64 bits starting at bit 2*q of the 192-bit string W0:W1:W2 (q <= 64); bits past W2 read as zero
@@ -654,7 +709,7 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
     static_assert(!BINNED || OWNERS, "fine buckets are the owners' business");
     __shared__ Sk1wLds L;
     __shared__ Sk1wFine<BINNED> F;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = p1w_wave(tid);
     for (uint32_t i = tid; i < PT_MAX_BUCKETS1_SK; i += P1W_THREADS) L.wcur[i] = 0;
     if (BINNED) {
         for (uint32_t i = tid; i < np1 * bn.fine; i += P1W_THREADS) F.h[i] = 0;
@@ -784,8 +839,8 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
 #undef SK_CASE
 
         // ---- which of my positions start a window, and where runs of equal minimizers break
-        uint32_t valid_bits = 0;
-        if (lane < 62 && p0 + (uint64_t)k <= n_bases) {
+        uint32_t valid_bits;
+        {
             // the window [p, p+k) lies inside one read iff no read starts at p+1 .. p+k-1: bit j of S = OR of the read-start bits
             // of p0 + j + 1 .. p0 + j + k - 1, for all eight windows at once (doubling shifts; round 3 tested the eight apart,
             // each behind 64-bit range checks: 90 instructions for what takes 30)
@@ -793,49 +848,32 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
             uint32_t width = 1;
             for (; 2 * width <= (uint32_t)k - 1; width *= 2) S |= S >> width;  // (uniform: k - 1 is 22 .. 30, four rounds)
             S |= S >> ((uint32_t)k - 1 - width);
-            const uint64_t jmax = n_bases - (uint64_t)k - p0;  // last j with p0 + j + k <= n_bases
-            const uint32_t jm = jmax < 7 ? (uint32_t)jmax : 7u;
-            const uint32_t j0 = p0 >= base_lo ? 0u : (base_lo - p0 < 8 ? (uint32_t)(base_lo - p0) : 8u);  // first j with p0 + j >= base_lo
-            valid_bits = ~(uint32_t)S & ((2u << jm) - 1u) & ~((1u << j0) - 1u) & 0xFFu;
-        }
-        uint32_t brk_bits = 0;  // bit j: my window j breaks the run of equal minimizers (or is no window)
-        {
-            const uint32_t last = (valid_bits >> (PT_ITEMS - 1)) & 1u ? hmin[PT_ITEMS - 1] : SK_NONE;
-            uint32_t prev = __shfl_up(last, 1);
-            if (lane == 0) prev = SK_NONE;  // a tile always starts a run
-            uint32_t bits = 0;
-#pragma unroll
-            for (int j = 0; j < PT_ITEMS; j++) {
-                const bool v = (valid_bits >> j) & 1u;
-                if (!v || prev == SK_NONE || prev != hmin[j]) bits |= 1u << j;
-                prev = v ? hmin[j] : SK_NONE;
+            // which of my positions lie in [base_lo, n_bases - k]: all of them in a tile that lies wholly inside (one test a
+            // wave); only the first and the last tile of a run go through the 64-bit arithmetic a lane
+            uint32_t edge = lane < 62 ? 0xFFu : 0u;
+            if (lo < base_lo || lo + P1W_TILE + (uint64_t)k > n_bases + 1) {
+                edge = 0;
+                if (lane < 62 && p0 + (uint64_t)k <= n_bases) {
+                    const uint64_t jmax = n_bases - (uint64_t)k - p0;  // last j with p0 + j + k <= n_bases
+                    const uint32_t jm = jmax < 7 ? (uint32_t)jmax : 7u;
+                    const uint32_t j0 = p0 >= base_lo ? 0u : (base_lo - p0 < 8 ? (uint32_t)(base_lo - p0) : 8u);  // first j with p0 + j >= base_lo
+                    edge = ((2u << jm) - 1u) & ~((1u << j0) - 1u) & 0xFFu;
+                }
             }
-            brkb[2 + lane] = (uint8_t)bits;  // window i of the tile <-> bit 16 + i of the wave's break bitmap
-            brk_bits = bits;
+            valid_bits = ~(uint32_t)S & edge;
         }
+        // bit j: my window j breaks the run of equal minimizers (or is no window)
+        const uint32_t last = (valid_bits >> (PT_ITEMS - 1)) & 1u ? hmin[PT_ITEMS - 1] : SK_NONE;
+        const uint32_t prev = wave_from_prev(last, SK_NONE);  // (a tile always starts a run)
+        const uint32_t brk_bits = sk_break_bits<PT_ITEMS, false>(hmin, valid_bits, prev);
+        brkb[2 + lane] = (uint8_t)brk_bits;  // window i of the tile <-> bit 16 + i of the wave's break bitmap
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        // A window starts a record when it breaks the run of equal minimizers or sits a multiple of SK_MAX_WINDOWS behind the
-        // run's first window.  Where did the run start?  The last lane below mine that holds a break is a ballot and a count of
-        // leading zeros away, its break bits one cross-lane read; from there the run start is carried along my 8 windows.
-        // (Round 3 looked the start up in the wave's bitmap only for windows of runs of 16 and more -- a branch with a loop over
-        // LDS words in it, for each of the 8 windows apart.  One window in seven is that deep in its run, so every one of the
-        // eight branches ran in nearly every tile with a handful of lanes in it: 330 of the kernel's 556 vector instructions
-        // per tile.)
-        uint32_t start_bits = 0;
-        {
-            const unsigned long long holders = __ballot(brk_bits != 0);  // (lane 0 is one: a tile always starts a run)
-            const unsigned long long below = holders & ((1ull << lane) - 1ull);
-            const uint32_t P = below ? 63u - (uint32_t)__builtin_clzll(below) : 0u;
-            const uint32_t bp = (uint32_t)__shfl((int)brk_bits, (int)P);
-            uint32_t cur = P * PT_ITEMS + (31u - (uint32_t)__builtin_clz(bp | 1u));  // tile window of the last break before my first one (lane 0: unused)
-#pragma unroll
-            for (int j = 0; j < PT_ITEMS; j++) {
-                const uint32_t pos = lane * PT_ITEMS + (uint32_t)j;
-                cur = (brk_bits >> j) & 1u ? pos : cur;
-                if (((valid_bits >> j) & 1u) && ((pos - cur) % SK_MAX_WINDOWS) == 0) start_bits |= 1u << j;
-            }
-        }
+        // (Round 3 looked the run's start up in the wave's bitmap for windows of runs of 16 and more, a branch with a loop over
+        // LDS words for each of the 8 windows apart: 330 of the kernel's 556 vector instructions per tile.  Round 4 carried the
+        // start along the 8 windows behind a predicated block each: with the break bits decided window by window, some 260 of
+        // the tile's 620 instructions.  As masks, sk_break_bits and sk_start_bits, the section is about 90.)
+        const uint32_t start_bits = sk_start_bits<PT_ITEMS, SK_MAX_WINDOWS>(lane, valid_bits, brk_bits);
 
         // ---- records: a run is cut every SK_MAX_WINDOWS windows, counted from its first window
 #if MC_P1W_COMPACT
