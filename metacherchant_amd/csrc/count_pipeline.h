@@ -560,13 +560,16 @@ __device__ __forceinline__ void sk_emit(SkCursors &C, uint32_t d, const uint4 &r
 // ---------------------------------------------------------------------------------------------------------------
 // SK-P1, wave-autonomous form (the one the host launches).  The kernel above synchronises 16 waves six times per tile
 // of 8192 positions and ran at 4 waves per SIMD with half its wave-cycles parked on barriers; here a WAVE owns a tile
-// of P1W_TILE = 62 x 8 positions and nothing but the bucket fill levels is shared by the workgroup:
-//   * a lane loads the three 64-bit words that hold bases p0-7 .. p0+59 around its 8 positions straight from global
+// of 62 x NI positions (p1w_tile) and nothing but the bucket fill levels is shared by the workgroup.  NI = 16 on one GPU: what a
+// tile pays once -- the prefetch, the read-start scan, the neighbours' hashes, the ballot and the prefix sum of the run
+// bookkeeping, the staging -- is paid once per 992 positions; NI = 8 in the OWNERS forms, whose BINNED histogram leaves the
+// staging of 16 positions no room in LDS.
+//   * a lane loads the three 64-bit words that hold bases p0-7 .. p0+59 around its NI positions straight from global
 //     memory (the next tile's words, read offsets and first read are requested one tile ahead);
-//   * every 15-mer is hashed once: a lane hashes the 8 that start at its positions and takes the 16 that follow from the
-//     next two lanes (lanes 62 and 63 own no window: they only supply those hashes, so a tile needs nothing from outside
-//     its wave);
-//   * read starts and run breaks live in a 176-byte piece of LDS per wave, ordered by wave-level fences only;
+//   * every 15-mer is hashed once: a lane hashes the NI that start at its positions and takes the 16 that follow from the
+//     next lane (NI = 8: the next two lanes; lanes 62 and 63 own no window: they only supply those hashes, so a tile needs
+//     nothing from outside its wave);
+//   * read starts and run breaks live in two bitmaps of 2 NI + 4 words per wave in LDS, ordered by wave-level fences only;
 //   * a record goes out with one LDS atomic on the workgroup's fill level of its bucket and two scattered stores
 //     (the record, and the read pointer of its first window: base ptr_base + position in the read store; ptr_base
 //     == ~0: the context keeps no read store and the pointers are 0).
@@ -585,7 +588,9 @@ __device__ __forceinline__ void sk_emit(SkCursors &C, uint32_t d, const uint4 &r
 #endif
 constexpr int P1W_THREADS = MC_P1W_THREADS;
 constexpr int P1W_WAVES = P1W_THREADS / 64;
-constexpr uint32_t P1W_TILE = 62 * PT_ITEMS;   // base positions per wave tile
+// positions a lane, and base positions a wave tile, of the form of k_sk1w_extract that a host path launches (the kernel's NI)
+constexpr int p1w_items(bool owners) { return owners || !MC_P1W_COMPACT ? PT_ITEMS : 16; }
+constexpr uint32_t p1w_tile(bool owners) { return 62u * (uint32_t)p1w_items(owners); }
 constexpr int P1W_SEGMENTS = 1024;             // workgroups of the launch = segments of every level-1 bucket
 static_assert(PT_MAX_LEAVES2 <= PT_THREADS && PT_MAX_BUCKETS_KEYS <= PT_THREADS, "one thread per leaf cursor");
 static_assert(P1W_SEGMENTS <= PT_THREADS && P1W_SEGMENTS >= PT_SEGMENTS, "k_sk2_scatter scans one segment count per thread");
@@ -650,16 +655,74 @@ __device__ __forceinline__ uint32_t sk_start_bits(uint32_t lane, uint32_t valid,
 // it does not: 28 vector instructions and 9 vector registers more in k_sk1w_extract, 3.21 ms against 3.05 ms on configs[1])
 __device__ __forceinline__ uint32_t p1w_wave(uint32_t tid) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)); }
 
-struct alignas(16) Sk1wLds {
+template <int NI> struct alignas(16) Sk1wLds {  // (NI = 16: 110 KB a workgroup)
+    static constexpr int AUX = 2 * NI + 4;  // words that hold a bit a position of the 64 lanes, and 128 bits more
     uint32_t wcur[PT_MAX_BUCKETS1_SK];  // this workgroup's fill level of every bucket
-    uint32_t starts[P1W_WAVES][24];    // per wave: bit b <-> "a read starts at position lo - 64 + b" (704 bits used)
-    uint32_t brk[P1W_WAVES][20];       // per wave, as bytes: byte 2 + lane = that lane's 8 break bits; bytes 0,1 = 0; bytes 66.. = 0xFF
+    uint32_t starts[P1W_WAVES][AUX];   // per wave: bit b <-> "a read starts at position lo - 64 + b", for lo - 64 .. lo + 64 NI + 63
+    uint32_t brk[P1W_WAVES][AUX];      // per wave: bit 16 + i <-> window i of the tile breaks its run (a lane stores its NI bits in one piece); bits 0 .. 15 = 0, bits 16 + 64 NI .. = 1
 #if MC_P1W_COMPACT
-    uint64_t wst[P1W_WAVES][24];       // per wave: the tile's words (word 0 holds base lo - 7)
-    uint32_t hst[P1W_WAVES][64 * PT_ITEMS];  // per wave: minimizer hash of every window of the tile
-    uint16_t squeue[P1W_WAVES][64 * PT_ITEMS];  // per wave: the windows that start a record, in order
+    uint64_t wst[P1W_WAVES][AUX];      // per wave: the tile's words (word 0 holds base lo - 7) and the 46 bases a record may take behind it
+    uint32_t hst[P1W_WAVES][64 * NI];  // per wave: minimizer hash of every window of the tile
+    uint16_t squeue[P1W_WAVES][64 * NI];  // per wave: the windows that start a record, in order
 #endif
 };
+
+// Minimizer hash of the 8 windows B .. B+7 of a lane, window j = min hh[j .. j + W - 1], from the 32 hashes hh (the lane's own and
+// those that follow in the next lanes): all eight ranges hold the core hh[B+7 .. B+W-1]; what differs is a suffix of
+// hh[B .. B+6] and a prefix of hh[B+W .. B+W+6].
+template <int W, int B, int N>
+__device__ __forceinline__ void sk_core_minima8(const uint32_t (&hh)[32], uint32_t (&hmin)[N])
+{
+    static_assert(W >= 9 && W <= 17 && B + 8 <= N && B + W + 6 < 32, "windows of 9 .. 17 hashes");
+    uint32_t core = hh[B + 7];
+#pragma unroll
+    for (int i = 8; i < W; i++) core = min(core, hh[B + i]);
+    uint32_t suf = SK_NONE;
+    hmin[B + 7] = core;
+#pragma unroll
+    for (int j = 6; j >= 0; j--) { suf = min(suf, hh[B + j]); hmin[B + j] = min(suf, core); }
+    uint32_t pre = SK_NONE;
+#pragma unroll
+    for (int j = 1; j < 8; j++) { pre = min(pre, hh[B + W + j - 1]); hmin[B + j] = min(hmin[B + j], pre); }
+}
+
+// ... of a lane's 16 windows at once, for W >= 15.  The hashes are taken in blocks of W (van Herk, Gil-Werman): block 0 =
+// hh[0 .. W-1], block 1 = hh[W .. 2W-1].  Window 0 is block 0, a window behind it a suffix of block 0 joined with a prefix of
+// block 1, and window W = 15 is block 1.  What the compiler issues for it (v_min_u32 + v_min3_u32) is 42, 43, 44 minima for
+// W = 15, 16, 17 against 46, 46, 48 for the core scheme on either half of the 16 windows.  Below W = 15 windows begin inside
+// block 1 as well, which then needs its suffixes and block 2 its prefixes: that came to 39 40 41 42 43 46 for W = 9 .. 14 against
+// the core scheme's 38 38 40 40 42 44 (it joins more of its minima into three-operand ones), so the core scheme serves those.
+template <int W>
+__device__ __forceinline__ void sk_block_minima16(const uint32_t (&hh)[32], uint32_t (&hmin)[16])
+{
+    static_assert(W >= 15 && W <= 17, "no window begins behind the first of block 1");
+    constexpr int A = W < 16 ? W : 16;        // windows 0 .. A-1 begin inside block 0
+    constexpr int NP1 = W == 15 ? W : A - 1;  // prefix minima of block 1 in use: p1[0 .. NP1-1] (all of the block where window W exists)
+    uint32_t s0[W], p1[W];                    // s0[i] = min hh[i .. W-1], p1[i] = min hh[W .. W+i]
+    s0[W - 1] = hh[W - 1];
+#pragma unroll
+    for (int i = W - 2; i >= 0; i--) s0[i] = min(s0[i + 1], hh[i]);
+    p1[0] = hh[W];
+#pragma unroll
+    for (int i = 1; i < NP1; i++) p1[i] = min(p1[i - 1], hh[W + i]);
+    hmin[0] = s0[0];
+#pragma unroll
+    for (int j = 1; j < A; j++) hmin[j] = min(s0[j], p1[j - 1]);
+    if constexpr (W == 15) hmin[W] = p1[W - 1];
+}
+
+// ... of a lane's N = 8 or 16 windows, by whichever of the two issues fewer minima (tests/test_extract_minima_model.py holds both,
+// index for index, against the minimum taken window by window)
+template <int W, int N>
+__device__ __forceinline__ void sk_window_minima(const uint32_t (&hh)[32], uint32_t (&hmin)[N])
+{
+    static_assert(N == 8 || N == 16, "8 or 16 positions a lane");
+    if constexpr (N == 16 && W >= 15) sk_block_minima16<W>(hh, hmin);
+    else {
+        sk_core_minima8<W, 0>(hh, hmin);
+        if constexpr (N == 16) sk_core_minima8<W, 8>(hh, hmin);
+    }
+}
 
 // Moves between neighbouring lanes of the wave as DPP wave shifts: one vector move each.  (As __shfl_down / __shfl_up they were
 // ds_bpermute_b32, 18 a tile through the LDS port with an address register and a wait each: the extract kernel took 3.05 ms
@@ -685,7 +748,7 @@ __device__ __forceinline__ uint64_t p1w_bits(uint64_t W0, uint64_t W1, uint64_t 
 // COMPACT: a record leaves as ONE 16-byte unit whose first word holds, instead of the bin word, what the second level needs of
 // it -- the leaf inside the level-1 bucket (10 bits, `m2` leaves per bucket) -- and the position of its first window RELATIVE to
 // the first base of the workgroup's tiles (22 bits): a workgroup then takes `chunk_tiles` CONSECUTIVE tiles (chunk_tiles x
-// P1W_TILE <= 2^22), and the reader (k_sk2_scatter_compact) knows the segment = workgroup of every record.  out_ptrs is not
+// p1w_tile(false) <= 2^22), and the reader (k_sk2_scatter_compact) knows the segment = workgroup of every record.  out_ptrs is not
 // written.  The 16-byte and 4-byte stores of the two-array form reach HBM as two partly filled sectors per record (the lines
 // of 512 buckets x 1024 segments do not live in the L2 until they are full): 9.2 GB written for 2.7 GB on configs[1].
 constexpr uint32_t SKC_REL_BITS = 22;
@@ -698,7 +761,7 @@ constexpr uint32_t SKC_REL_BITS = 22;
 constexpr uint32_t SKB_MAX_CELLS = 16384;  // owners x fine buckets at most (64 KB of LDS beside the kernel's 62)
 template <bool ON> struct Sk1wFine { uint32_t h[ON ? SKB_MAX_CELLS : 1]; uint32_t win[ON ? PT_MAX_BUCKETS : 1]; };
 struct SkBinned { uint32_t sub, fine; uint32_t *fine_rows; unsigned long long *owner_windows; };
-template <bool OWNERS, bool COMPACT = false, bool BINNED = false>
+template <bool OWNERS, bool COMPACT = false, bool BINNED = false, int NI = p1w_items(OWNERS)>
 __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
     const uint64_t *__restrict__ words, const uint64_t *__restrict__ offsets, uint64_t n_reads, uint64_t base_lo,
     uint64_t n_bases, uint64_t n_tiles, const uint32_t *__restrict__ first_read, int k, uint32_t np1, uint32_t *seg_counts,
@@ -707,7 +770,10 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
 {
     static_assert(!(OWNERS && COMPACT), "the compact form is for the single-GPU pipeline");
     static_assert(!BINNED || OWNERS, "fine buckets are the owners' business");
-    __shared__ Sk1wLds L;
+    static_assert(NI == 8 || (NI == 16 && MC_P1W_COMPACT), "8 or 16 positions a lane");
+    constexpr uint32_t P1W_TILE = 62u * NI;  // (= p1w_tile(OWNERS) where the host launches it)
+    constexpr uint32_t AUX = Sk1wLds<NI>::AUX;
+    __shared__ Sk1wLds<NI> L;
     __shared__ Sk1wFine<BINNED> F;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = p1w_wave(tid);
     for (uint32_t i = tid; i < PT_MAX_BUCKETS1_SK; i += P1W_THREADS) L.wcur[i] = 0;
@@ -727,14 +793,13 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
     };
     uint32_t *starts = L.starts[wv];
     uint32_t *brkw = L.brk[wv];
-    uint8_t *brkb = reinterpret_cast<uint8_t *>(brkw);
 #if MC_P1W_COMPACT
     uint64_t *wst = L.wst[wv];
     uint32_t *hst = L.hst[wv];
     uint16_t *squeue = L.squeue[wv];
-    if (lane < 24) wst[lane] = 0;
+    if (lane < AUX) wst[lane] = 0;
 #endif
-    if (lane < 20) brkw[lane] = lane == 0 ? 0u : 0xFFFFFFFFu;  // (bytes 2 .. 65 are rewritten by every tile)
+    if (lane < AUX) brkw[lane] = lane == 0 ? 0u : 0xFFFFFFFFu;  // (bits 16 .. 16 + 64 NI - 1 are rewritten by every tile)
     __syncthreads();
     const int w = k - SK_M + 1;                       // SK_M-mers per window (9 .. 17)
     const uint64_t last_word = (n_bases + 31) / 32;   // the pad word
@@ -744,7 +809,7 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
     uint64_t pfW0 = 0, pfW1 = 0, pfW2 = 0, pf_off = ~0ull;
     uint32_t pf_first = 0;
     auto load_words = [&](uint64_t tile) {
-        const int64_t p0 = (int64_t)(tile * P1W_TILE) + (int64_t)lane * PT_ITEMS;
+        const int64_t p0 = (int64_t)(tile * P1W_TILE) + (int64_t)lane * NI;
         const int64_t wi0 = (p0 - 7) >> 5;  // (-1 for the first lane of tile 0: that word reads as zero)
         pfW0 = wi0 >= 0 ? words[min((uint64_t)wi0, last_word)] : 0ull;
         pfW1 = words[min((uint64_t)(wi0 + 1), last_word)];
@@ -766,17 +831,17 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
     for (uint64_t tile = tile0; tile < tile_end; tile += tile_step) {
         const uint64_t lo = tile * (uint64_t)P1W_TILE;
         const int64_t bm_lo = (int64_t)lo - 64;
-        const uint64_t bm_hi = lo + 640;
+        const uint64_t bm_hi = (uint64_t)(bm_lo + 32 * (int64_t)AUX);  // (the last lane's windows end before lo + 64 NI + 31)
         if (!MC_P1W_PREFETCH_WORDS) load_words(tile);
         const uint64_t W0 = pfW0, W1 = pfW1, W2 = pfW2;
         uint64_t s = pf_off;
         const uint32_t my_first = pf_first;
         prefetch(tile + tile_step);
-        const uint64_t p0 = lo + (uint64_t)lane * PT_ITEMS;
-        const uint32_t off0 = (uint32_t)((int64_t)p0 - 32 * (((int64_t)p0 - 7) >> 5));  // base p0 inside W0:W1:W2 (8, 16, 24 or 32)
+        const uint64_t p0 = lo + (uint64_t)lane * NI;
+        const uint32_t off0 = (uint32_t)((int64_t)p0 - 32 * (((int64_t)p0 - 7) >> 5));  // base p0 inside W0:W1:W2 (NI = 8: 8, 16, 24 or 32; NI = 16: 16 or 32)
 
         // ---- read starts of this tile's neighbourhood
-        if (lane < 24) starts[lane] = 0;
+        if (lane < AUX) starts[lane] = 0;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         for (uint64_t r = (uint64_t)my_first + lane;; r += 64) {
@@ -790,95 +855,92 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        uint32_t ws[4];  // bit b of ws[0..3] <-> a read starts at position p0 - 8 + b
+        uint32_t ws[2];  // bit b of ws[0..1] <-> a read starts at position p0 - 8 + b
         {
-            const uint32_t bit0 = lane * 8 + 56, wd = bit0 >> 5, sh = bit0 & 31;
-            const uint32_t d0 = starts[wd], d1 = starts[wd + 1], d2 = starts[wd + 2], d3 = starts[wd + 3], d4 = starts[wd + 4];
+            const uint32_t bit0 = lane * NI + 56, wd = bit0 >> 5, sh = bit0 & 31;
+            const uint32_t d0 = starts[wd], d1 = starts[wd + 1], d2 = starts[wd + 2];
             ws[0] = __builtin_amdgcn_alignbit(d1, d0, sh);
             ws[1] = __builtin_amdgcn_alignbit(d2, d1, sh);
-            ws[2] = __builtin_amdgcn_alignbit(d3, d2, sh);
-            ws[3] = __builtin_amdgcn_alignbit(d4, d3, sh);
         }
 
-        // ---- sk_order of the canonical SK_M-mers at my 8 positions, then of the 16 after them
-        uint32_t hh[24];
+        // ---- sk_order of the canonical SK_M-mers at my NI positions, then of the 16 after them
+        uint32_t hh[32];  // (NI = 8: 24 of them)
         {
             const uint64_t A = p1w_bits(W0, W1, W2, off0);
             uint32_t f = (uint32_t)(A >> (64 - 2 * SK_M)), r = sk_rc_mmer(f);
             hh[0] = sk_order(f < r ? f : r);
 #pragma unroll
-            for (int i = 1; i < 8; i++) {
+            for (int i = 1; i < NI; i++) {
                 const uint32_t nb = (uint32_t)(A >> (62 - 2 * (i + SK_M - 1))) & 3u;  // the base that enters
                 f = ((f << 2) | nb) & SK_MMASK;
                 r = (r >> 2) | ((3u - nb) << (2 * (SK_M - 1)));
                 hh[i] = sk_order(f < r ? f : r);
             }
 #pragma unroll
-            for (int i = 0; i < 8; i++) hh[8 + i] = wave_from_next(hh[i]);
+            for (int i = 0; i < NI; i++) hh[NI + i] = wave_from_next(hh[i]);
+            if constexpr (NI == 8) {
 #pragma unroll
-            for (int i = 0; i < 8; i++) hh[16 + i] = wave_from_next(hh[8 + i]);
+                for (int i = 0; i < 8; i++) hh[16 + i] = wave_from_next(hh[8 + i]);
+            }
         }
-        // minimizer hash of my 8 windows: window j = min hh[j .. j+w-1].  All eight ranges hold hh[7 .. w-1]; what differs
-        // is a suffix of hh[0 .. 6] and a prefix of hh[w .. w+6].
-        uint32_t hmin[PT_ITEMS];
-#define SK_CASE(W)                                                                             \
-    case W: {                                                                                  \
-        uint32_t core = hh[7];                                                                 \
-        _Pragma("unroll") for (int i = 8; i < W; i++) core = min(core, hh[i]);                 \
-        uint32_t suf = SK_NONE;                                                                \
-        hmin[7] = core;                                                                        \
-        _Pragma("unroll") for (int j = 6; j >= 0; j--) { suf = min(suf, hh[j]); hmin[j] = min(suf, core); } \
-        uint32_t pre = SK_NONE;                                                                \
-        _Pragma("unroll") for (int j = 1; j < PT_ITEMS; j++) { pre = min(pre, hh[W + j - 1]); hmin[j] = min(hmin[j], pre); } \
-    } break;
+        // minimizer hash of my NI windows: window j = min hh[j .. j+w-1] (one case a w, so that every index is a constant)
+        uint32_t hmin[NI];
         switch (w) {
-            SK_CASE(9) SK_CASE(10) SK_CASE(11) SK_CASE(12) SK_CASE(13) SK_CASE(14) SK_CASE(15) SK_CASE(16)
-        default:
-            SK_CASE(17)
+        case 9: sk_window_minima<9>(hh, hmin); break;
+        case 10: sk_window_minima<10>(hh, hmin); break;
+        case 11: sk_window_minima<11>(hh, hmin); break;
+        case 12: sk_window_minima<12>(hh, hmin); break;
+        case 13: sk_window_minima<13>(hh, hmin); break;
+        case 14: sk_window_minima<14>(hh, hmin); break;
+        case 15: sk_window_minima<15>(hh, hmin); break;
+        case 16: sk_window_minima<16>(hh, hmin); break;
+        default: sk_window_minima<17>(hh, hmin); break;
         }
-#undef SK_CASE
 
         // ---- which of my positions start a window, and where runs of equal minimizers break
         uint32_t valid_bits;
         {
             // the window [p, p+k) lies inside one read iff no read starts at p+1 .. p+k-1: bit j of S = OR of the read-start bits
-            // of p0 + j + 1 .. p0 + j + k - 1, for all eight windows at once (doubling shifts; round 3 tested the eight apart,
+            // of p0 + j + 1 .. p0 + j + k - 1, for all NI windows at once (doubling shifts; round 3 tested the eight apart,
             // each behind 64-bit range checks: 90 instructions for what takes 30)
-            uint64_t S = ((((uint64_t)ws[1]) << 32) | ws[0]) >> 9;  // bit b <-> a read starts at p0 + 1 + b
+            uint64_t S = ((((uint64_t)ws[1]) << 32) | ws[0]) >> 9;  // bit b <-> a read starts at p0 + 1 + b (55 bits; NI - 1 + k - 1 <= 45 are used)
             uint32_t width = 1;
             for (; 2 * width <= (uint32_t)k - 1; width *= 2) S |= S >> width;  // (uniform: k - 1 is 22 .. 30, four rounds)
             S |= S >> ((uint32_t)k - 1 - width);
             // which of my positions lie in [base_lo, n_bases - k]: all of them in a tile that lies wholly inside (one test a
             // wave); only the first and the last tile of a run go through the 64-bit arithmetic a lane
-            uint32_t edge = lane < 62 ? 0xFFu : 0u;
+            constexpr uint32_t ALL = (1u << NI) - 1u;
+            uint32_t edge = lane < 62 ? ALL : 0u;
             if (lo < base_lo || lo + P1W_TILE + (uint64_t)k > n_bases + 1) {
                 edge = 0;
                 if (lane < 62 && p0 + (uint64_t)k <= n_bases) {
                     const uint64_t jmax = n_bases - (uint64_t)k - p0;  // last j with p0 + j + k <= n_bases
-                    const uint32_t jm = jmax < 7 ? (uint32_t)jmax : 7u;
-                    const uint32_t j0 = p0 >= base_lo ? 0u : (base_lo - p0 < 8 ? (uint32_t)(base_lo - p0) : 8u);  // first j with p0 + j >= base_lo
-                    edge = ((2u << jm) - 1u) & ~((1u << j0) - 1u) & 0xFFu;
+                    const uint32_t jm = jmax < (uint64_t)(NI - 1) ? (uint32_t)jmax : (uint32_t)(NI - 1);
+                    const uint32_t j0 = p0 >= base_lo ? 0u : (base_lo - p0 < (uint64_t)NI ? (uint32_t)(base_lo - p0) : (uint32_t)NI);  // first j with p0 + j >= base_lo
+                    edge = ((2u << jm) - 1u) & ~((1u << j0) - 1u) & ALL;
                 }
             }
             valid_bits = ~(uint32_t)S & edge;
         }
         // bit j: my window j breaks the run of equal minimizers (or is no window)
-        const uint32_t last = (valid_bits >> (PT_ITEMS - 1)) & 1u ? hmin[PT_ITEMS - 1] : SK_NONE;
+        const uint32_t last = (valid_bits >> (NI - 1)) & 1u ? hmin[NI - 1] : SK_NONE;
         const uint32_t prev = wave_from_prev(last, SK_NONE);  // (a tile always starts a run)
-        const uint32_t brk_bits = sk_break_bits<PT_ITEMS, false>(hmin, valid_bits, prev);
-        brkb[2 + lane] = (uint8_t)brk_bits;  // window i of the tile <-> bit 16 + i of the wave's break bitmap
+        const uint32_t brk_bits = sk_break_bits<NI, false>(hmin, valid_bits, prev);
+        // window i of the tile <-> bit 16 + i of the wave's break bitmap
+        if constexpr (NI == 8) reinterpret_cast<uint8_t *>(brkw)[2 + lane] = (uint8_t)brk_bits;
+        else reinterpret_cast<uint16_t *>(brkw)[1 + lane] = (uint16_t)brk_bits;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // (Round 3 looked the run's start up in the wave's bitmap for windows of runs of 16 and more, a branch with a loop over
         // LDS words for each of the 8 windows apart: 330 of the kernel's 556 vector instructions per tile.  Round 4 carried the
         // start along the 8 windows behind a predicated block each: with the break bits decided window by window, some 260 of
         // the tile's 620 instructions.  As masks, sk_break_bits and sk_start_bits, the section is about 90.)
-        const uint32_t start_bits = sk_start_bits<PT_ITEMS, SK_MAX_WINDOWS>(lane, valid_bits, brk_bits);
+        const uint32_t start_bits = sk_start_bits<NI, SK_MAX_WINDOWS>(lane, valid_bits, brk_bits);
 
         // ---- records: a run is cut every SK_MAX_WINDOWS windows, counted from its first window
 #if MC_P1W_COMPACT
-        // A lane holds 0-4 record starts among its 8 positions, and a loop over them runs as long as the busiest lane's
-        // (about 4 rounds of ~70 instructions for 0.9 records per lane).  Instead the tile's ~55 starts are lined up --
+        // A lane holds 0-4 record starts among 8 positions, and a loop over them runs as long as the busiest lane's
+        // (about 4 rounds of ~70 instructions for 0.9 records per lane).  Instead the tile's starts (~55 in 496 positions) are lined up --
         // a lane writes the window numbers of its starts into the wave's queue at its prefix count -- and lane i builds
         // the i-th record of the tile from what the wave put in LDS for that: the tile's words, the minimizer hash of
         // every window, the break bitmap.
@@ -887,12 +949,12 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
             const uint32_t incl = wave_incl_sum(cnt);  // (six DPP additions; as six cross-lane reads through the LDS port it was 24 instructions)
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             uint32_t at = incl - cnt;
-            for (uint32_t todo = start_bits; todo; todo &= todo - 1) squeue[at++] = (uint16_t)(lane * PT_ITEMS + (uint32_t)__builtin_ctz(todo));
+            for (uint32_t todo = start_bits; todo; todo &= todo - 1) squeue[at++] = (uint16_t)(lane * NI + (uint32_t)__builtin_ctz(todo));
             const uint32_t r7 = (uint32_t)(((int64_t)lo - 7) & 31);             // (lo - 7) = 32 * wbase + r7
-            const uint32_t idx0 = (r7 + lane * PT_ITEMS) >> 5;                  // my W0 is word wbase + idx0
+            const uint32_t idx0 = (r7 + lane * NI) >> 5;                        // my W0 is word wbase + idx0 (<= 2 NI + 1)
             wst[idx0] = W0; wst[idx0 + 1] = W1; wst[idx0 + 2] = W2;              // (lanes that hold the same word write the same value)
-            *reinterpret_cast<uint4 *>(&hst[lane * PT_ITEMS]) = make_uint4(hmin[0], hmin[1], hmin[2], hmin[3]);
-            *reinterpret_cast<uint4 *>(&hst[lane * PT_ITEMS + 4]) = make_uint4(hmin[4], hmin[5], hmin[6], hmin[7]);
+#pragma unroll
+            for (int j = 0; j < NI; j += 4) *reinterpret_cast<uint4 *>(&hst[lane * NI + j]) = make_uint4(hmin[j], hmin[j + 1], hmin[j + 2], hmin[j + 3]);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             for (uint32_t i = lane; i < total; i += 64) {
@@ -954,7 +1016,7 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
             hi |= (uint64_t)(n - 1) << 60;
             uint32_t hsel = hmin[0];
 #pragma unroll
-            for (int qq = 1; qq < PT_ITEMS; qq++) hsel = j == (uint32_t)qq ? hmin[qq] : hsel;
+            for (int qq = 1; qq < NI; qq++) hsel = j == (uint32_t)qq ? hmin[qq] : hsel;
             const uint32_t bin = sk_bin(hsel);
             const uint32_t d = bucket_of(hsel, bin, n);
             uint4 rec;
@@ -963,7 +1025,7 @@ __global__ void __launch_bounds__(P1W_THREADS, MC_P1W_MIN_WAVES) k_sk1w_extract(
             if (dst < cap) {
                 const uint64_t at = seg_base + (uint64_t)d * bucket_stride + dst;
                 if (COMPACT) {
-                    const uint32_t rel = (uint32_t)(tile - chunk_lo) * P1W_TILE + lane * PT_ITEMS + j;
+                    const uint32_t rel = (uint32_t)(tile - chunk_lo) * P1W_TILE + lane * NI + j;
                     rec.x = rel | ((mulhi32(bin, np1 * m2) - d * m2) << SKC_REL_BITS);
                     out_recs[at] = rec;
                 } else {
@@ -1409,7 +1471,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_sk2_scatter_staged(const uint4 *
 // << 22): the same staging as k_sk2_scatter_staged, and what leaves is again ONE 16-byte unit per record -- first word = the
 // read pointer of the record's first window, which only now, with the segment known, becomes absolute.  No pointer array on
 // either side: 16 bytes in and 16 out per record against 20 and 20, and the staging area (72 KB) leaves room for two
-// workgroups on a CU.  pos0 = position of segment 0's first base, seg_bases = bases per segment (chunk_tiles x P1W_TILE).
+// workgroups on a CU.  pos0 = position of segment 0's first base, seg_bases = bases per segment (chunk_tiles x p1w_tile(false)).
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): per-thread arrays indexed only by these stay in registers (a
 // `#pragma unroll` loop with a data-dependent inner loop left them in scratch / LDS: 48 KB of the staged kernel's LDS were that)
 template <class F, int... I>

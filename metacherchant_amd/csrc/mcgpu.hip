@@ -1247,10 +1247,10 @@ static int pipe_prepare(mc_ctx *c, uint64_t wb, PipePlan *pl, uint64_t n_records
         // (not where pipe_resize_by_sample may replace the table between the two levels: the leaf numbers inside the records
         // are those of the table the first level saw)
         pl->compact = compact_tiles && c->sw.sk_compact && pl->sk && pl->b2 > 1 && pl->b2 <= (1u << (32 - SKC_REL_BITS)) && g == 0 &&
-                      chunk * P1W_TILE <= (1ull << SKC_REL_BITS) && !(pl->guessed && c->virgin);
+                      chunk * p1w_tile(false) <= (1ull << SKC_REL_BITS) && !(pl->guessed && c->virgin);
         // ... unless the table can be given a power of two of regions once the batch's size is known: 512 buckets of 2 .. 1024 leaves
         pl->vleaf = false;
-        if (!pl->compact && !lng && c->sw.sk_vleaf && !c->no_vleaf && compact_tiles && c->sw.sk_compact && pl->sk && g == 0 && chunk * P1W_TILE <= (1ull << SKC_REL_BITS) &&
+        if (!pl->compact && !lng && c->sw.sk_vleaf && !c->no_vleaf && compact_tiles && c->sw.sk_compact && pl->sk && g == 0 && chunk * p1w_tile(false) <= (1ull << SKC_REL_BITS) &&
             pl->guessed && c->virgin && c->mm_k > 0 && np1 == PT_MAX_BUCKETS && c->n_regions <= (uint64_t)PT_MAX_BUCKETS * 1024) {
             uint64_t r2 = 2 * PT_MAX_BUCKETS;
             while (r2 < c->n_regions) r2 *= 2;
@@ -1520,7 +1520,7 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
         else if (pl.sk && pl.compact && !pl.listed)
             hipLaunchKernelGGL(k_sk2_scatter_compact<MC_SK2C_ITEMS>, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, pl.cap1,
                                P.seg_counts1, (uint32_t)np1, pl.b2, P.cursors2, pl.cap2, P.b_recs, pl.sks, pl.nseg1, c->cur_ptr_base, pl.pos0,
-                               (uint64_t)pl.chunk_tiles * P1W_TILE, pl.vleaf ? 10u - (uint32_t)__builtin_ctz(pl.b2) : 0u);
+                               (uint64_t)pl.chunk_tiles * p1w_tile(false), pl.vleaf ? 10u - (uint32_t)__builtin_ctz(pl.b2) : 0u);
         else if (pl.listed)
             hipLaunchKernelGGL((k_sk2_scatter_staged<MC_SK2_ITEMS, true, false>), dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, pl.in_recs, pl.in_ptrs, (uint64_t)0,
                                P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_recs, nullptr, pl.sks, pl.nseg1, P.skb_seg_start, nullptr);
@@ -1911,14 +1911,15 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
     // the same scratch and the whole table is rewritten half as often (max_run_bases).
     // (only where the memory is needed: at 0.9 G windows two pieces cost 55 ms against 35 ms in one)
     // (super-k-mer records go in one piece)
+    constexpr uint32_t sk_tile = p1w_tile(false);  // k_sk1w_extract<false, ..>, both forms
     int rc = pipe_prepare(c, wb, &pl, n_records, n_records ? (uint32_t)P1W_SEGMENTS : (uint32_t)PT_SEGMENTS,
                           n_records || wb < (3ull << 29) ? 1u : (uint32_t)std::min<uint64_t>(8, (wb + (1ull << 30) - 1) >> 30), false,
-                          n_records ? (end_abs + P1W_TILE - 1) / P1W_TILE - base0 / P1W_TILE : 0);
+                          n_records ? (end_abs + sk_tile - 1) / sk_tile - base0 / sk_tile : 0);
     if (rc) return rc;
     const uint32_t pieces = pl.pieces;
     const uint64_t *offs = d_off + r0;
     // tiles are cut over the absolute base positions [0, end_abs); the ones before base0 hold no read of ours
-    const uint32_t tile_size = pl.sk ? P1W_TILE : (uint32_t)PT_TILE;
+    const uint32_t tile_size = pl.sk ? sk_tile : (uint32_t)PT_TILE;
     const uint64_t n_tiles_abs = (end_abs + tile_size - 1) / tile_size;
     rc = ensure_buf(c, &P.tile_first, &P.tiles1_cap, n_tiles_abs);
     if (rc) return rc;
@@ -1957,7 +1958,7 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
         HIPCHK(c, hipEventRecord(c->ev_t[0], c->stream));  // (no wait here: pipe_finish enqueues P2 and P3 right behind)
         launch_tile_first(c, offs, nr, n_tiles_abs, P.tile_first, tile_size);
         if (pl.sk && pl.compact) {
-            pl.pos0 = base0 / P1W_TILE * P1W_TILE;
+            pl.pos0 = base0 / sk_tile * sk_tile;
             if (c->sw.ingest_debug)
                 fprintf(stderr, "[count] compact records: %u buckets x %u leaves%s, %u tiles a segment from base %llu\n", pl.b1, pl.vleaf ? 1024u : pl.b2,
                         pl.vleaf ? " (whatever the table: it is sized behind the first level)" : "", pl.chunk_tiles, (unsigned long long)pl.pos0);
@@ -3037,16 +3038,17 @@ int mc_extract_superkmers_dev(mc_ctx *c, const uint64_t *d_words, const uint64_t
     // windows <= bases: capacity of the (owner, segment) pieces from the same bound the caller sized its buffer with
     const uint64_t bound = sk_records_bound(c, n_bases - first_off, n_reads);
     const uint32_t nseg = P1W_SEGMENTS;
+    constexpr uint32_t own_tile = p1w_tile(true);  // k_sk1w_extract<true>
     uint64_t seg_cap = (uint64_t)((double)bound / (double)n_owners / (double)nseg * 1.25) + 64;
     {   // a workgroup (= segment) takes whole tiles, one per wave and round: with few tiles some segments get more than others, or any at all
         const uint64_t n_waves = (uint64_t)nseg * P1W_WAVES;
-        const uint64_t tiles = (last_off - first_off + P1W_TILE - 1) / P1W_TILE + 1, per_wg = (tiles + n_waves - 1) / n_waves * P1W_WAVES;
+        const uint64_t tiles = (last_off - first_off + own_tile - 1) / own_tile + 1, per_wg = (tiles + n_waves - 1) / n_waves * P1W_WAVES;
         const double per_tile = (double)bound / (double)std::max<uint64_t>(tiles - 1, 1);
         seg_cap = std::max<uint64_t>(seg_cap, (uint64_t)((double)per_wg * per_tile / (double)n_owners * 1.3) + 64);
     }
     if ((uint64_t)n_owners * nseg * seg_cap >= 0xFFFFFFFFull)
         return fail(c, MC_EINVAL, "mc_extract_superkmers_dev: batch too large (split the reads)");
-    const uint64_t n_tiles_abs = (last_off + P1W_TILE - 1) / P1W_TILE;
+    const uint64_t n_tiles_abs = (last_off + own_tile - 1) / own_tile;
     int rc = ensure_buf(c, &P.tile_first, &P.tiles1_cap, n_tiles_abs);
     if (!rc) rc = ensure_buf(c, &P.a_recs, &P.a_recs_cap, (uint64_t)n_owners * nseg * seg_cap);
     if (!rc) rc = ensure_buf(c, &P.a_hints, &P.a_hints_cap, (uint64_t)n_owners * nseg * seg_cap);
@@ -3061,7 +3063,7 @@ int mc_extract_superkmers_dev(mc_ctx *c, const uint64_t *d_words, const uint64_t
     HIPCHK(c, d_piece.alloc((uint64_t)n_owners * nseg));
     HIPCHK(c, d_owner.alloc(n_owners + 1));
     const SkSpill none{nullptr, P.spill_count, 0, P.flags};  // no spill list: an overflow is reported
-    launch_tile_first(c, d_off, n_reads, n_tiles_abs, P.tile_first, P1W_TILE);
+    launch_tile_first(c, d_off, n_reads, n_tiles_abs, P.tile_first, own_tile);
     hipLaunchKernelGGL(k_sk1w_extract<true>, dim3(nseg), dim3(P1W_THREADS), 0, c->stream, d_words, d_off, n_reads, first_off,
                        last_off, n_tiles_abs, P.tile_first, c->cfg.k, n_owners, P.seg_counts1, seg_cap, P.a_recs, P.a_hints, none, c->cur_ptr_base);
     hipLaunchKernelGGL(k_sk_pack_offsets, dim3(1), dim3(1024), 0, c->stream, P.seg_counts1, n_owners, d_piece.p, d_owner.p, nseg);
@@ -3140,16 +3142,17 @@ int mc_extract_superkmers_binned_dev(mc_ctx *c, const uint64_t *d_words, const u
     c->solid_list_fresh = false;  // (the pieces go into pipe.a_recs: mc_extract_superkmers_dev says what that ends)
     const uint64_t bound = sk_records_bound(c, n_bases - first_off, n_reads);
     const uint32_t nseg = P1W_SEGMENTS, n_buckets = n_owners * sub;
+    constexpr uint32_t own_tile = p1w_tile(true);  // k_sk1w_extract<true, false, true>
     uint64_t seg_cap = (uint64_t)((double)bound / (double)n_buckets / (double)nseg * 1.25) + 64;
     {   // a workgroup (= segment) takes whole tiles, one per wave and round: with few tiles some segments get more than others, or any at all
         const uint64_t n_waves = (uint64_t)nseg * P1W_WAVES;
-        const uint64_t tiles = (last_off - first_off + P1W_TILE - 1) / P1W_TILE + 1, per_wg = (tiles + n_waves - 1) / n_waves * P1W_WAVES;
+        const uint64_t tiles = (last_off - first_off + own_tile - 1) / own_tile + 1, per_wg = (tiles + n_waves - 1) / n_waves * P1W_WAVES;
         const double per_tile = (double)bound / (double)std::max<uint64_t>(tiles - 1, 1);
         seg_cap = std::max<uint64_t>(seg_cap, (uint64_t)((double)per_wg * per_tile / (double)n_buckets * 1.3) + 64);
     }
     if ((uint64_t)n_buckets * nseg * seg_cap >= 0xFFFFFFFFull)
         return fail(c, MC_EINVAL, "mc_extract_superkmers_binned_dev: batch too large (split the reads)");
-    const uint64_t n_tiles_abs = (last_off + P1W_TILE - 1) / P1W_TILE;
+    const uint64_t n_tiles_abs = (last_off + own_tile - 1) / own_tile;
     int rc = ensure_buf(c, &P.tile_first, &P.tiles1_cap, n_tiles_abs);
     if (!rc) rc = ensure_buf(c, &P.a_recs, &P.a_recs_cap, (uint64_t)n_buckets * nseg * seg_cap);
     if (!rc) rc = ensure_buf(c, &P.a_hints, &P.a_hints_cap, (uint64_t)n_buckets * nseg * seg_cap);
@@ -3166,7 +3169,7 @@ int mc_extract_superkmers_binned_dev(mc_ctx *c, const uint64_t *d_words, const u
     unsigned long long *d_owner = P.skb_small, *d_win = P.skb_small + n_owners + 1;  // owner offsets (n_owners + 1), owner windows (n_owners)
     HIPCHK(c, hipMemsetAsync(d_win, 0, n_owners * sizeof(unsigned long long), c->stream));
     const SkSpill none{nullptr, P.spill_count, 0, P.flags};  // no spill list: an overflow is reported
-    launch_tile_first(c, d_off, n_reads, n_tiles_abs, P.tile_first, P1W_TILE);
+    launch_tile_first(c, d_off, n_reads, n_tiles_abs, P.tile_first, own_tile);
     hipLaunchKernelGGL((k_sk1w_extract<true, false, true>), dim3(nseg), dim3(P1W_THREADS), 0, c->stream, d_words, d_off, n_reads, first_off,
                        last_off, n_tiles_abs, P.tile_first, c->cfg.k, n_owners, P.seg_counts1, seg_cap, P.a_recs, P.a_hints, none, c->cur_ptr_base,
                        0u, 0u, SkBinned{sub, n_fine, P.skb_rows, d_win});
