@@ -2093,14 +2093,7 @@ constexpr uint32_t DD_MAX_CAP = 4096;    // records per leaf: 32767 + 4096 * 16 
                                          // error-free reads, whose table is small, hold ~2650 and all went to the general kernel)
 constexpr uint32_t DD_NONE = 0xFFFFFFFFu, DD_OWNER = 0x80000000u;
 
-__device__ __forceinline__ uint32_t dd_hash(uint32_t y, uint32_t z, uint32_t w)
-{
-    uint32_t h = (y ^ (z * 0x9E3779B1u));
-    h = (h ^ (h >> 15)) * 0x85EBCA6Bu;
-    h ^= w * 0xC2B2AE35u;
-    h = (h ^ (h >> 13)) * 0x27D4EB2Fu;
-    return h ^ (h >> 16);
-}
+// (dd_hash, the hash a record takes its fingerprint and its home place in the record table from: kmer_hash.h)
 
 // Round 5: the kernel rebuilt around what round 4's counters and its ISA showed (the round-4 kernel: a window cost a byte-table read,
 // FIVE cross-lane reads (ds_bpermute: 24 ticks of the SIMD's LDS port each), 21 vector instructions for its two strands

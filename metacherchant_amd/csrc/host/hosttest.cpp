@@ -28,6 +28,9 @@
 // `mc_hosttest pointers <pos>...`: the code of a read pointer (csrc/read_ptr.h, the functions the kernels compile).  For every store
 // position (decimal) one line: ptr_encode(pos), ptr_decode of that code and its span (0 0 for no pointer), ptr_advance(code, j) for
 // j = 0 .. 15 and ptr_advance_long(code, j) for j = 0 .. 31.
+// `mc_hosttest dedup-tags <file>`: where the merge kernel's record table puts a super-k-mer record (csrc/kmer_hash.h dd_hash, the function
+// the kernel compiles).  file: a record a line as two hexadecimal 64-bit words "lo hi" (csrc/count_pipeline.h has the layout).  Prints for
+// each "hash tag place": dd_hash of the record's three words of bases, the tag (hash & 0xFFFF0000) | 0x8000 and the home place hash & 1023.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -227,6 +230,17 @@ int main(int argc, char **argv)
                        mc::sk_hmin_of_kmer(k < 32 ? w & ((1ull << (2 * k)) - 1) : w, k));
             return 0;
         }
+        if (argc == 3 && std::string(argv[1]) == "dedup-tags") {
+            FILE *f = fopen(argv[2], "r");
+            if (!f) throw Error("cannot open the records file");
+            unsigned long long lo, hi;
+            while (fscanf(f, "%llx %llx", &lo, &hi) == 2) {
+                const uint32_t h = mc::dd_hash((uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+                printf("%x %x %u\n", h, (h & 0xFFFF0000u) | 0x8000u, h & 1023u);
+            }
+            fclose(f);
+            return 0;
+        }
         if (argc >= 3 && std::string(argv[1]) == "pointers") {
             for (int a = 2; a < argc; a++) {
                 const uint64_t pos = strtoull(argv[a], nullptr, 10);
@@ -279,7 +293,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | pointers <pos>... | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | pointers <pos>... | dedup-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

@@ -79,6 +79,18 @@ __host__ __device__ inline uint32_t sk_hmin_of_kmer(uint64_t fw, int k)
     return best;
 }
 
+// The hash of a super-k-mer record's three words of bases (count_pipeline.h k_p3_dedup): its top 16 bits are the record's fingerprint
+// in the merge kernel's record table, its low bits the record's home place there.  `mc_hosttest dedup-tags` prints it, which pins
+// tests/dedup_leaves.py's restatement to this code.
+__host__ __device__ __forceinline__ uint32_t dd_hash(uint32_t y, uint32_t z, uint32_t w)
+{
+    uint32_t h = (y ^ (z * 0x9E3779B1u));
+    h = (h ^ (h >> 15)) * 0x85EBCA6Bu;
+    h ^= w * 0xC2B2AE35u;
+    h = (h ^ (h >> 13)) * 0x27D4EB2Fu;
+    return h ^ (h >> 16);
+}
+
 }  // namespace mc
 
 #ifdef MC_KMER_HASH_OWN_WORDS

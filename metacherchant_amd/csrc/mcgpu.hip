@@ -1468,6 +1468,16 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
                 (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, emit, c->ptr_tries, P.flags
 #define P3D_ARGS static_cast<const uint4 *>(lk), lh, lc, lcap, leaves, c->view(), P.leaf_state, P.leaf_new, P.flags + 1, \
                  (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, emit, c->ptr_tries, P.flags
+        if (c->sw.ingest_debug) {  // (every run of the merge stage: which kernel takes the leaves)
+            const bool dedup = !pl.lng && pl.sk && pl.g == 0 && lseg == 1 && c->sw.p3_dedup;
+            const bool one_gpu = c->ptr_tries == 1 && (emit.recs == nullptr || !(c->solid_tracked && c->cov_hint > 0));
+            char name[64];
+            if (pl.lng) snprintf(name, sizeof name, "k_p3_long");
+            else if (dedup) snprintf(name, sizeof name, "k_p3_dedup<%d, %d, %d>", virgin ? 1 : 0, one_gpu ? 1 : 0, virgin && one_gpu && k == 31 ? 1 : 0);
+            else snprintf(name, sizeof name, "k_p3_merge<%s>", pl.sk ? "true" : "false");
+            fprintf(stderr, "[count] merge: %s over %u leaves, lcap %llu, ptr_tries %u, general kernel behind it: %s\n", name, leaves,
+                    (unsigned long long)lcap, c->ptr_tries, dedup && lcap > DD_MAX_CAP ? "yes" : "no");
+        }
         if (pl.lng) {
 #define P3L_ARGS static_cast<const uint4 *>(lk), lc, lcap, leaves, c->view(), virgin, P.leaf_state, P.leaf_new, P.flags + 1, \
                  (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, emit, P.flags, c->dup_l1_view()

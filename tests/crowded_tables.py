@@ -26,7 +26,7 @@ SK_MMASK = (1 << (2 * SK_M)) - 1
 # canonical 15-mers of very small sk_order (the one of order 0 is poly-A: not used)
 M_INTERIOR = 0x0e8b2f51  # sk_order 1, sk_bin 0x688990c0: an interior region
 M_LAST = 0x356ca2e4      # sk_order 1467272, sk_bin 0xfffff483: the last region for every n_regions up to 2^20
-LOCUS_FLANK = 16
+LOCUS_FLANK = 16         # (k = 31; loci() takes any k from 23 on: locus_flank)
 LOCUS_LEN = 2 * LOCUS_FLANK + SK_M   # 47 bases
 LOCUS_WINDOWS = LOCUS_LEN - 31 + 1   # 17 windows at k = 31
 
@@ -145,23 +145,31 @@ def store_windows(codes, off, k):
 
 
 # ---------------------------------------------------------------------------------------------------- minimizer bins, k = 31
+def locus_flank(k):
+    """bases either side of the 15-mer of a locus: k - 15, so that every one of its k - 14 windows holds the 15-mer"""
+    return k - SK_M
+
+
 def loci(rng, m, n, k=31):
     """n loci around the 15-mer m, every window of which has m for its minimizer (a locus with a still smaller 15-mer in a flank is
-    dropped and another drawn), no two sharing a canonical k-mer: uint8 [n, 47]"""
+    dropped and another drawn), no two sharing a canonical k-mer: uint8 [n, 2 (k - 15) + 15], k - 14 windows a locus (k = 31: 47
+    bases, 17 windows)"""
+    flank = locus_flank(k)
+    length, windows = 2 * flank + SK_M, flank + 1
     target = int(sk_order(np.array([min(m, int(rc_mmer(np.array([m]))[0]))]))[0])
     core = mmer_codes(m)
     out, seen = [], set()
     while len(out) < n:
-        cand = rng.integers(0, 4, (n, LOCUS_LEN)).astype(np.uint8)
-        cand[:, LOCUS_FLANK:LOCUS_FLANK + SK_M] = core
+        cand = rng.integers(0, 4, (n, length)).astype(np.uint8)
+        cand[:, flank:flank + SK_M] = core
         flat = cand.reshape(-1)
         _, lo = pack_windows(flat, k)
-        starts = (np.arange(n)[:, None] * LOCUS_LEN + np.arange(LOCUS_WINDOWS)[None, :])
-        ok = (sk_hmin_of_kmer(lo[starts.reshape(-1)], k).reshape(n, LOCUS_WINDOWS) == target).all(axis=1)
+        starts = (np.arange(n)[:, None] * length + np.arange(windows)[None, :])
+        ok = (sk_hmin_of_kmer(lo[starts.reshape(-1)], k).reshape(n, windows) == target).all(axis=1)
         keys = sm.window_keys(flat, k, 0)[starts]
         for i in np.nonzero(ok)[0]:
             ks = set(keys[i].tolist())
-            if len(ks) == LOCUS_WINDOWS and not (ks & seen) and len(out) < n:
+            if len(ks) == windows and not (ks & seen) and len(out) < n:
                 seen |= ks
                 out.append(cand[i])
     return np.stack(out)

@@ -71,3 +71,20 @@ def holds(hint, pos):
     lo, span = ptr_range(hint)
     pos = _i64(pos)
     return (lo <= pos) & (pos < lo + span)
+
+
+def not_found(keys, hints, at, wk, valid, n_bases):
+    """Indices of the (key, hint) pairs with a hint whose range holds no store position where a window with that key starts; an
+    exact hint's range is one position.  The batch lies at store position `at` and is n_bases long; wk[q] = the key of the window
+    at batch position q, valid[q] = that window lies inside one read.  No range may begin at or past the end of the code's range,
+    and every range meets the batch."""
+    some = np.nonzero(hints != 0)[0]
+    lo, span = ptr_range(hints[some])
+    assert (lo < END).all() and (lo + span > at).all() and (lo < at + n_bases).all()
+    found = np.zeros(len(some), dtype=bool)
+    n = len(wk)
+    for o in range(int(span.max()) if len(some) else 0):
+        q = lo - at + o
+        qq = np.clip(q, 0, n - 1)
+        found |= (o < span) & (q >= 0) & (q < n) & valid[qq] & (wk[qq] == keys[some])
+    return some[~found]

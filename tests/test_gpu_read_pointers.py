@@ -125,18 +125,8 @@ def host_side(k, mode):
 
 
 def not_found(keys, hints, at, H):
-    """(a): indices of the (key, hint) pairs with a hint whose range holds no store position where a window with that key starts;
-    an exact hint's range is one position.  No range may begin at or past the end of the code's range."""
-    some = np.nonzero(hints != 0)[0]
-    lo, span = rp.ptr_range(hints[some])
-    assert (lo < rp.END).all() and (lo + span > at).all() and (lo < at + BASES).all()
-    found = np.zeros(len(some), dtype=bool)
-    n = len(H["wk"])
-    for o in range(int(span.max()) if len(some) else 0):
-        q = lo - at + o
-        qq = np.clip(q, 0, n - 1)
-        found |= (o < span) & (q >= 0) & (q < n) & H["valid"][qq] & (H["wk"][qq] == keys[some])
-    return some[~found]
+    """(a): tests/read_pointers.py not_found over this batch"""
+    return rp.not_found(keys, hints, at, H["wk"], H["valid"], BASES)
 
 
 def _copy_walk(r):
