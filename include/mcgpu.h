@@ -186,7 +186,7 @@ int mc_kmer_keys(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, uint64_t n
  *
  * The result lists the entries of distanceToKmer in insertion order (= BFS discovery order, seeds
  * first, duplicates once): the oriented k-mer, its distance, reads.get(key) and whether the vertex
- * is in lastKmers (needed by runTrimPaths, :241-262, which the host applies).  Arrays are
+ * is in lastKmers (needed by runTrimPaths, :241-262, which the host applies, or mc_trim_paths below).  Arrays are
  * malloc()ed by the library; release with mc_bfs_result_free. */
 typedef struct {
     uint64_t n;
@@ -561,6 +561,27 @@ typedef struct {
 int mc_unitigs_dev(mc_ctx *ctx, const uint64_t *d_hi, const uint64_t *d_lo, const uint8_t *d_cls, uint64_t n, mc_unitigs_result *out);
 int mc_unitigs(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint8_t *cls, uint64_t n, mc_unitigs_result *out);
 void mc_unitigs_free(mc_unitigs_result *r);
+
+/* ---- the trim: which entries of one BFS pass runTrimPaths keeps (src/algo/OneSequenceCalculator.java:241-262: the walk from every
+ * lastKmers vertex through getNeighborsByDir(-dir) inside distanceToKmer, and retainAll of what it visited).  k is the context's; its
+ * key mode and its table play no part, and the call is allowed before mc_finalize_counts.
+ * Input: the result of one pass as mc_bfs_result holds it: n distinct oriented packed k-mers (hi may be NULL when k <= 32; bits above
+ * the k-mer are dropped), last[i] (0, or anything else for 1), and the pass's dir in -1, 0, +1.
+ * Neighbours are StringUtils', on oriented strings with no canonical form: the left neighbour of x with base c is
+ * (c << 2(k-1)) | (x >> 2), the right one ((x << 2) & mask) | c.  x and its reverse complement are two unrelated entries.
+ * Output: kept[i] = 1 iff the walk visits entry i, 0 otherwise.  That is:
+ *   dir = +1   i reaches a `last` entry through right-neighbour steps inside the set (no step is a way too: a `last` entry is kept);
+ *   dir = -1   the same through left-neighbour steps;
+ *   dir =  0   through any of the eight neighbours: i's connected component holds a `last` entry.
+ * With no `last` entry nothing is kept.  The result is a set, a function of the input alone.  The order-dependent half of the trim,
+ * retainAll's removals from the replayed HashMap, stays with the caller (csrc/host/envfinder.cpp Environment::add_pass takes the mask).
+ * Errors: MC_EINVAL for null pointers (hi at k <= 32 and device_ms excepted), dir outside -1..1, n >= 2^31, or two entries that are the
+ * same oriented k-mer (distanceToKmer is a map).  n == 0 is MC_OK.  *device_ms (may be NULL): the device time of the call, HIP events.
+ * mc_trim_paths takes host pointers, mc_trim_paths_dev device ones, kept included. */
+int mc_trim_paths(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint8_t *last, uint64_t n, int dir, uint8_t *kept,
+                  double *device_ms);
+int mc_trim_paths_dev(mc_ctx *ctx, const uint64_t *d_hi, const uint64_t *d_lo, const uint8_t *d_last, uint64_t n, int dir,
+                      uint8_t *d_kept, double *device_ms);
 
 /* ---- the environment join: what environment-finder-multi takes from several graph.txt files at once (initializeStructures of
  * src/algo/MultiSequenceCalculator.java:51-100, the KC column of src/io/writers/GFAWriterMulti.java, printProbability of

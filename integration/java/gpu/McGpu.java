@@ -38,6 +38,11 @@ public final class McGpu implements AutoCloseable {
      *  Results in distanceToKmer insertion order (src/algo/OneSequenceCalculator.java:154-214). */
     public native BfsResult[] bfsBatch(long[][] seedHi, long[][] seedLo, int[] dir, int minCov, long maxKmers, long maxRadius);
 
+    /** runTrimPaths' answer for one pass (src/algo/OneSequenceCalculator.java:241-262): hi / lo / last as a BfsResult holds them,
+     *  dir the pass's.  out[i] != 0: the walk from lastKmers through getNeighborsByDir(-dir) visits entry i, so retainAll keeps
+     *  it; the caller removes the others from distanceToKmer in its own iteration order. */
+    public native byte[] trimPaths(long[] hi, long[] lo, byte[] last, int dir);
+
     @Override public native void close();
 
     private static native long create(int k, int keyMode, int device, long capacityHint);

@@ -99,6 +99,29 @@ JNIEXPORT jshortArray JNICALL Java_gpu_McGpu_get(JNIEnv *env, jobject self, jlon
     return out;
 }
 
+JNIEXPORT jbyteArray JNICALL Java_gpu_McGpu_trimPaths(JNIEnv *env, jobject self, jlongArray hi, jlongArray lo, jbyteArray last, jint dir)
+{
+    mc_ctx *ctx = ctx_of(env, self);
+    const jsize n = (*env)->GetArrayLength(env, lo);
+    if ((*env)->GetArrayLength(env, hi) != n || (*env)->GetArrayLength(env, last) != n) {
+        throw_failed(env, "trimPaths: hi, lo and last need one entry a k-mer");
+        return NULL;
+    }
+    jbyteArray out = (*env)->NewByteArray(env, n);
+    if (!out) return NULL;
+    jlong *h = (*env)->GetLongArrayElements(env, hi, 0), *l = (*env)->GetLongArrayElements(env, lo, 0);
+    jbyte *t = (*env)->GetByteArrayElements(env, last, 0);
+    uint8_t *kept = (uint8_t *)malloc((size_t)(n > 0 ? n : 1));
+    int rc = (h && l && t && kept) ? mc_trim_paths(ctx, (const uint64_t *)h, (const uint64_t *)l, (const uint8_t *)t, (uint64_t)n, dir, kept, NULL) : MC_ENOMEM;
+    if (t) (*env)->ReleaseByteArrayElements(env, last, t, JNI_ABORT);
+    if (l) (*env)->ReleaseLongArrayElements(env, lo, l, JNI_ABORT);
+    if (h) (*env)->ReleaseLongArrayElements(env, hi, h, JNI_ABORT);
+    if (rc == MC_OK) (*env)->SetByteArrayRegion(env, out, 0, n, (const jbyte *)kept);
+    free(kept);
+    if (rc != MC_OK) { throw_failed(env, mc_last_error(ctx)); return NULL; }
+    return out;
+}
+
 /* one BfsResult object from one mc_bfs_result (NULL when the job found no solid seed k-mer) */
 static jobject make_result(JNIEnv *env, jclass rcls, const mc_bfs_result *r)
 {

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libmcgpu.so")
 CLI = os.path.join(LIBDIR, "metacherchant")
 
 # the library's units (csrc/context.h says what each holds), and the host reader the read-file entry point uses
-HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip",
+HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip", "trim_paths.hip",
                os.path.join("host", "envfinder.cpp")]
 # every header under csrc/ makes every object stale (a stale library would travel to the GPU box unnoticed)
 HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "envfinder.h"), os.path.join("test", "bfs_old_race.h"),
@@ -137,6 +137,26 @@ def build_unitigs_bench(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     return UNITIGS_BENCH
+
+
+TRIM_PATHS_BENCH = os.path.join(LIBDIR, "mc_trim_paths_bench")
+
+
+def build_trim_paths_bench(force=False, verbose=False):
+    """mc_trim_paths_bench (csrc/host/trim_paths_bench.cpp): the trim of one pass, the host's walk against mc_trim_paths, timed;
+    scripts/trim_paths_bench.py runs it"""
+    hdir = os.path.join(CSRC, "host")
+    srcs = [os.path.join(hdir, "trim_paths_bench.cpp"), os.path.join(hdir, "envfinder.cpp")]
+    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(ROOT, "include", "mcgpu.h")]
+    if force or _stale(TRIM_PATHS_BENCH, srcs + hdrs + [LIB]):
+        rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-o", TRIM_PATHS_BENCH] + srcs + [
+            "-L", LIBDIR, "-lmcgpu", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib"),
+            "-lpthread", "-lz", "-ldl"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return TRIM_PATHS_BENCH
 
 
 WHOLE_READS_BENCH = os.path.join(LIBDIR, "mc_whole_reads_bench")

@@ -1637,17 +1637,13 @@ Environment::Environment(int k, std::vector<std::string> gene_sequences) : k_(k)
     gene_kmers_.erase(std::unique(gene_kmers_.begin(), gene_kmers_.end()), gene_kmers_.end());
 }
 
-void Environment::add_pass(const BfsPass &p, bool trim)
+// runTrimPaths (:241-262) on distanceToKmer `d`, the map of pass p's k-mers
+void trim_pass(JavaKmerMap &d, const BfsPass &p, int k, const std::vector<uint8_t> *kept)
 {
-    JavaKmerMap d(k_);  // distanceToKmer
-    std::vector<int16_t> cov;  // by entry of d
-    cov.reserve(p.kmers.size());
-    for (size_t i = 0; i < p.kmers.size(); i++) {
-        const size_t e = (size_t)d.put(p.kmers[i], p.dist[i]);
-        if (e >= cov.size()) cov.resize(e + 1);
-        cov[e] = p.cov[i];
-    }
-    if (trim) {
+    if (kept) {
+        for (size_t i = 0; i < p.kmers.size(); i++)  // keySet().retainAll(visitedKmers), the walk's answer given
+            if (!(*kept)[i] && d.find_entry(p.kmers[i]) >= 0) d.remove(p.kmers[i]);
+    } else {
         // runTrimPaths: reverse BFS from lastKmers through getNeighborsByDir(-dir) inside distanceToKmer
         std::vector<kmer_t> queue;
         std::vector<uint8_t> visited(d.n_entries(), 0);
@@ -1656,14 +1652,14 @@ void Environment::add_pass(const BfsPass &p, bool trim)
             if (p.last[i] && !visited[(size_t)e]) { visited[(size_t)e] = 1; queue.push_back(p.kmers[i]); }
         }
         const int dir = -p.dir;
-        const int top = 2 * (k_ - 1);
+        const int top = 2 * (k - 1);
         for (size_t head = 0; head < queue.size(); head++) {
             const kmer_t kmer = queue[head];
             for (unsigned c = 0; c < 4; c++) {  // A, G, C, T; dir 0 interleaves left and right
                 kmer_t nb[2];
                 int n = 0;
                 if (dir != 1) nb[n++] = ((kmer_t)c << top) | (kmer >> 2);
-                if (dir != -1) nb[n++] = ((kmer << 2) & kmer_mask(k_)) | c;
+                if (dir != -1) nb[n++] = ((kmer << 2) & kmer_mask(k)) | c;
                 for (int j = 0; j < n; j++) {
                     const int e = d.find_entry(nb[j]);
                     if (e >= 0 && !visited[(size_t)e]) { visited[(size_t)e] = 1; queue.push_back(nb[j]); }
@@ -1675,6 +1671,20 @@ void Environment::add_pass(const BfsPass &p, bool trim)
             if (e >= 0 && !visited[(size_t)e]) d.remove(s);
         }
     }
+}
+
+void Environment::add_pass(const BfsPass &p, bool trim, const std::vector<uint8_t> *kept)
+{
+    if (kept && kept->size() != p.kmers.size()) throw Error("Environment::add_pass: the mask needs one byte a k-mer of the pass");
+    JavaKmerMap d(k_);  // distanceToKmer
+    std::vector<int16_t> cov;  // by entry of d
+    cov.reserve(p.kmers.size());
+    for (size_t i = 0; i < p.kmers.size(); i++) {
+        const size_t e = (size_t)d.put(p.kmers[i], p.dist[i]);
+        if (e >= cov.size()) cov.resize(e + 1);
+        cov[e] = p.cov[i];
+    }
+    if (trim) trim_pass(d, p, k_, kept);
     d.for_each([&](kmer_t kmer, int, int e) { subgraph_.put(normalize128(kmer, k_), cov[(size_t)e]); });
     if (d.treeified()) d_treeified_ = true;  // (a removal from a treeified bin of distanceToKmer: runTrimPaths)
 }

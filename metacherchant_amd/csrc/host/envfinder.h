@@ -274,6 +274,12 @@ std::vector<PictureNode> make_picture(int k, const std::vector<kmer_t> &kmers, c
 
 // ---- src/algo/OneSequenceCalculator.java (after the BFS) + src/algo/SingleNode.java +
 // src/io/writers/GFAWriter.java + src/io/writers/TSVWriter.java; with set_colours, src/algo/SeqEnvCalculator.java (after its BFS)
+// runTrimPaths (src/algo/OneSequenceCalculator.java:241-262) on `d`, distanceToKmer holding the k-mers of pass p: the walk from the
+// `last` k-mers through getNeighborsByDir(-dir) inside d, then keySet().retainAll(visited), entry by entry in p's order.  kept: the
+// walk's answer, one byte a k-mer of p (mc_trim_paths makes it): only the removals are done then.  (What Environment::add_pass
+// does with trim, and what scripts/trim_paths_bench.py times.)
+void trim_pass(JavaKmerMap &d, const BfsPass &p, int k, const std::vector<uint8_t> *kept = nullptr);
+
 class Environment {
 public:
     Environment(int k, std::vector<std::string> gene_sequences);
@@ -294,7 +300,9 @@ public:
     Outside outside_neighbours() const;
     static size_t extensions(const Outside &o, const uint8_t *in_graph);
     // :217-219 (+ runTrimPaths :241-262 when trim): distanceToKmer -> subgraph
-    void add_pass(const BfsPass &p, bool trim);
+    // kept (with trim): one byte an entry of p, whether runTrimPaths' walk visits it (mc_trim_paths makes it); the walk is then left
+    // out and only retainAll's removals are done, in the same order
+    void add_pass(const BfsPass &p, bool trim, const std::vector<uint8_t> *kept = nullptr);
     // The fmt-visualizer's subgraph (src/algo/KmerEnvCalculator.java:87-89): subgraph.put(normalizeDna(kmer), value) for every entry,
     // in the order given -- the walk's pops, a k-mer popped again overwriting its value where it is.  With no gene sequences the
     // nodes are not gene nodes and seqs_fasta's header is KmerEnvCalculator's `Id<n>`; colours as set_colours gives them.

@@ -108,6 +108,9 @@ struct Options {
     // --parse: who parses the whole reads of the classifying tools (no counterpart in the reference; the files are the same)
     std::string parse = "auto";
     bool parse_given = false;
+    // --trim-on: who works out which k-mers --trim keeps (no counterpart in the reference; the files are the same)
+    std::string trim_on = "auto";
+    bool trim_on_given = false;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -120,7 +123,7 @@ const OptSpec SPECS[] = {
     {"merge", nullptr, 1}, {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0},
     {"continue", "c", 1}, {"force", nullptr, 1}, {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0},
     {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"output-dir", nullptr, 0}, {"env", "e", 2}, {"geneid", "g", 0},
-    {"compact", nullptr, 0}, {"join", nullptr, 0}, {"parse", nullptr, 0},
+    {"compact", nullptr, 0}, {"join", nullptr, 0}, {"parse", nullptr, 0}, {"trim-on", nullptr, 0},
 };
 
 // --tool reads-classifier: its parameters (ReadsClassifier.java:42-95) and the launch options
@@ -170,7 +173,7 @@ const OptSpec ASSEMBLER_SPECS[] = {
     {"coverage", nullptr, 0}, {"bothdirs", nullptr, 1}, {"chunklength", nullptr, 0}, {"forcehash", nullptr, 1}, {"hash", nullptr, 0},
     {"threads", nullptr, 0}, {"trim", nullptr, 1}, {"procfiltration", "pf", 0}, {"assembler", nullptr, 0}, {"assemblerpath", nullptr, 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
-    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0}, {"parse", nullptr, 0},
+    {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0}, {"parse", nullptr, 0}, {"trim-on", nullptr, 0},
 };
 
 struct SpecTable {
@@ -302,6 +305,11 @@ Options parse_args(int argc, char **argv)
         if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--parse takes host, gpu or auto, not '" + *v + "'");
         o.parse = *v;
         o.parse_given = true;
+    }
+    if (auto v = val("trim-on")) {
+        if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--trim-on takes host, gpu or auto, not '" + *v + "'");
+        o.trim_on = *v;
+        o.trim_on_given = true;
     }
     if (auto v = val("seq")) o.seq = *v;
     if (auto v = val("hicseq")) o.hicseq = *v;
@@ -442,6 +450,10 @@ void usage()
     puts("                --compact host|gpu|auto (environment-finder, environment-assembler-finder, recipient-visualiser, fmt-visualizer:");
     puts("                who compacts an environment's k-mers into unitigs; the files are the same; default auto: the GPU from");
     puts("                10000 k-mers on, the smallest size measured, where it already wins; the host below)");
+    puts("                --trim-on host|gpu|auto (environment-finder, environment-assembler-finder: who works out which k-mers --trim keeps.");
+    puts("                host: the reverse walk over the pass's hash map; gpu: mc_trim_paths on the tool's context, every pass; the files are");
+    puts("                the same; default auto: the GPU for a pass of 10000 k-mers or more, the smallest size measured, where it already wins;");
+    puts("                it does nothing without --trim; with --devices auto is host and gpu is refused)");
     puts("                --parse host|gpu|auto (the classifiers, seq-cov, fmt-visualizer, environment-assembler-finder: who parses the whole reads of");
     puts("                -r / --read-file / the read filter.  host: one thread reads the records and the tool packs them; gpu: the text of an");
     puts("                uncompressed FASTA / FASTQ file is tokenised on the device and stays there for the kernels; the files are the same;");
@@ -542,6 +554,33 @@ struct Compaction {
             gpu = gpu_compactor(ctx);
         }
         return &gpu;
+    }
+};
+
+// --trim-on: which k-mers of a pass --trim keeps, by the host's reverse walk (Environment::add_pass) or by mc_trim_paths on the tool's
+// context; `auto`, the default, takes the GPU from TRIM_AUTO_MIN k-mers in a pass on.
+// That is the smallest size scripts/trim_paths_bench.py has timed (10^4 to 10^7 k-mers, k = 31 and 63, dir +1 and 0, medians of 5):
+// there the GPU's way -- the call with its copies, then the removals by its mask -- takes 0.28 .. 0.41 ms against the host walk's
+// 1.9 .. 6.1 ms, and the gap only widens (10^6: 2.0 .. 18 ms against 0.41 .. 1.04 s), each time by far more than the host figures'
+// own spread.  Nobody has measured below it, so the host keeps those; with --devices (no single context) auto is host.
+constexpr size_t TRIM_AUTO_MIN = 10000;
+struct Trimmer {
+    const Options &o;
+    mc_ctx *ctx;  // (NULL: a group)
+    Trimmer(const Options &o, const Engine &e) : o(o), ctx(e.c) {}
+    // add_pass with the pass's mask where the GPU makes it
+    void add_pass(Environment &env, const BfsPass &p, const mc_bfs_result &r) const
+    {
+        const bool on_gpu = o.trim && ctx && (o.trim_on == "gpu" || (o.trim_on == "auto" && r.n >= TRIM_AUTO_MIN));
+        if (!on_gpu) {
+            env.add_pass(p, o.trim);
+            return;
+        }
+        std::vector<uint8_t> kept(r.n);
+        double ms = 0;
+        MC_CHECK(ctx, mc_trim_paths(ctx, r.hi, r.lo, r.last, r.n, p.dir, kept.data(), &ms));
+        info("Trimmed a pass of " + std::to_string(r.n) + " k-mers on the GPU (mc_trim_paths)");
+        env.add_pass(p, true, &kept);
     }
 };
 
@@ -1802,6 +1841,7 @@ bool assembler_finder_phase(const Options &o, int k, int coverage, const std::ve
     Engine E;
     E.open(cfg, {});
     Compaction compaction(o, E, k);
+    const Trimmer trimmer(o, E);
     E.set_coverage_hint(coverage);
     load_reads(reads, E);
 
@@ -1852,7 +1892,7 @@ bool assembler_finder_phase(const Options &o, int k, int coverage, const std::ve
         p.dist.assign(r.dist, r.dist + r.n);
         p.cov.assign(r.cov, r.cov + r.n);
         p.last.assign(r.last, r.last + r.n);
-        env.add_pass(p, o.trim);
+        trimmer.add_pass(env, p, r);
     }
     std::vector<kmer_t> members;
     if (fail) {  // (the calculator stops there: no graph files, and an empty subgraph for the filter)
@@ -1942,6 +1982,9 @@ int run(const Options &o)
 {
     if (o.compact_given && (o.tool == "kmer-counter" || o.tool == "environment-finder-multi"))  // (they share environment-finder's table)
         throw Error("--compact does not apply to --tool " + o.tool);
+    if (o.trim_on_given && (o.tool == "kmer-counter" || o.tool == "environment-finder-multi")) throw Error("--trim-on does not apply to --tool " + o.tool);
+    if (o.trim && o.trim_on == "gpu" && !o.devices.empty())  // (a group has no single context to run mc_trim_paths on)
+        throw Error("--trim-on gpu does not go with --devices: the trim of a group's walk runs on the host (--trim-on host or auto)");
     if (o.join_given && o.tool != "environment-finder-multi") throw Error("--join does not apply to --tool " + o.tool);
     if (o.parse_given && o.tool != "reads-classifier" && o.tool != "triple-reads-classifier" && o.tool != "seq-cov" && o.tool != "fmt-visualizer" &&
         o.tool != "environment-assembler-finder")
@@ -1989,6 +2032,7 @@ int run(const Options &o)
     Engine E;
     E.open(cfg, o.devices);
     Compaction compaction(o, E, o.k);
+    const Trimmer trimmer(o, E);
     if (!o.devices.empty()) info("Counting on " + std::to_string(o.devices.size()) + " devices");
     E.set_coverage_hint(o.coverage);
 
@@ -2080,7 +2124,7 @@ int run(const Options &o)
                 p.dist.assign(r.dist, r.dist + r.n);
                 p.cov.assign(r.cov, r.cov + r.n);
                 p.last.assign(r.last, r.last + r.n);
-                env.add_pass(p, o.trim);
+                trimmer.add_pass(env, p, r);
             }
             if (fail) {
                 info("Could not find any k-mers of the target gene in the input, halting.");

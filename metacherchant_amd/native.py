@@ -116,7 +116,7 @@ EXPORTS = [
     "mc_reads_last_copy", "mc_reads_last_copy_dev", "mc_triple_classes", "mc_triple_classes_dev", "mc_seq_coverage", "mc_seq_coverage_dev",
     "mc_kmer_presence", "mc_kmer_presence_dev", "mc_reads_in_set", "mc_reads_in_set_dev",
     "mc_components", "mc_components_dev", "mc_components_free", "mc_unitigs", "mc_unitigs_dev", "mc_unitigs_free",
-    "mc_env_join", "mc_env_join_dev", "mc_env_join_free",
+    "mc_env_join", "mc_env_join_dev", "mc_env_join_free", "mc_trim_paths", "mc_trim_paths_dev",
     "mc_tokenize_whole", "mc_tokenize_whole_dev", "mc_whole_text_bytes", "mc_whole_reads_to_host", "mc_whole_reads_free", "mc_reads_append_dev",
 ]
 
@@ -229,6 +229,9 @@ def load():
         L.mc_env_join_dev.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, C.c_uint32, vp, u64, C.POINTER(_EnvJoin)]
         L.mc_env_join_free.argtypes = [C.POINTER(_EnvJoin)]
         L.mc_env_join_free.restype = None
+    if hasattr(L, "mc_trim_paths"):
+        L.mc_trim_paths.argtypes = [vp, u64p, u64p, C.POINTER(C.c_uint8), u64, i32, C.POINTER(C.c_uint8), C.POINTER(C.c_double)]
+        L.mc_trim_paths_dev.argtypes = [vp, vp, vp, vp, u64, i32, vp, C.POINTER(C.c_double)]
     if hasattr(L, "mc_tokenize_whole"):
         wr = C.POINTER(_WholeReads)
         L.mc_tokenize_whole.argtypes = [vp, C.c_char_p, u64, i32, i32, C.c_uint32, wr]
@@ -635,6 +638,14 @@ class Context:
         """mc_unitigs_dev: see the module's unitigs_dev()"""
         return unitigs_dev(self, d_hi, d_lo, d_cls, n)
 
+    def trim_paths(self, hi, lo, last, dir):
+        """mc_trim_paths: see the module's trim_paths()"""
+        return trim_paths(self, hi, lo, last, dir)
+
+    def trim_paths_dev(self, d_hi, d_lo, d_last, n, dir, d_kept):
+        """mc_trim_paths_dev: see the module's trim_paths_dev()"""
+        return trim_paths_dev(self, d_hi, d_lo, d_last, n, dir, d_kept)
+
     def env_join(self, hi, lo, rec_hi, rec_lo, rec_depth, graph_offsets, gene_words=None, gene_len=0):
         """mc_env_join: see the module's env_join()"""
         return env_join(self, hi, lo, rec_hi, rec_lo, rec_depth, graph_offsets, gene_words, gene_len)
@@ -802,6 +813,29 @@ def unitigs_dev(context, d_hi, d_lo, d_cls, n):
     r = _Unitigs()
     context._chk(load().mc_unitigs_dev(context._h, _dptr(d_hi), _dptr(d_lo), _dptr(d_cls), int(n), C.byref(r)))
     return _unitigs_result(r)
+
+
+def trim_paths(context, hi, lo, last, dir):
+    """mc_trim_paths: which entries of one BFS pass runTrimPaths keeps.  hi, lo: the pass's distinct oriented packed k-mers (hi << 64 | lo;
+    hi may be None when k <= 32), last: uint8, whether the entry is in lastKmers, dir: the pass's (-1, 0, +1).  Returns np.uint8[n]:
+    1 where the entry reaches a `last` entry through neighbours on the side of dir (both sides for 0) inside the set.  Needs no table."""
+    lo = np.ascontiguousarray(lo, dtype=np.uint64)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64) if hi is not None else None
+    last = np.ascontiguousarray(last, dtype=np.uint8)
+    if (hi is not None and len(hi) != len(lo)) or len(last) != len(lo):
+        raise ValueError("hi, lo and last need one entry a k-mer")
+    kept = np.zeros(len(lo), dtype=np.uint8)
+    context._chk(load().mc_trim_paths(context._h, _p(hi, C.c_uint64) if hi is not None else None, _p(lo, C.c_uint64), _p(last, C.c_uint8), len(lo),
+                                      int(dir), _p(kept, C.c_uint8), None))
+    return kept
+
+
+def trim_paths_dev(context, d_hi, d_lo, d_last, n, dir, d_kept):
+    """mc_trim_paths_dev: d_hi (may be None when k <= 32) and d_lo hold n uint64 each, d_last and d_kept n bytes; d_kept is written.
+    Returns the device time in ms"""
+    ms = C.c_double(0)
+    context._chk(load().mc_trim_paths_dev(context._h, _dptr(d_hi), _dptr(d_lo), _dptr(d_last), int(n), int(dir), _dptr(d_kept), C.byref(ms)))
+    return float(ms.value)
 
 
 def _env_join_result(r):
