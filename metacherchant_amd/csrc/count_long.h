@@ -31,16 +31,13 @@ constexpr uint32_t P1L_TILE = P1L_LANES * PT_ITEMS;     // 456 base positions pe
 constexpr int SKL_MIN_K = 33, SKL_MAX_K = 63;           // (two-word k-mers; mc_create takes hash keys up to k = 63)
 static_assert((SKL_MAX_K - SK_M) / 8 + 1 <= 64 - (int)P1L_LANES, "k_skl_extract: a window reaches at most that many lanes up");
 
-// the bin word of a hash key's minimizer: sk_bin with its low byte cleared (see the record's second word)
-__host__ __device__ __forceinline__ uint32_t skl_bin(uint32_t hmin) { return sk_bin(hmin) & 0xFFFFFF00u; }
-
 // TWO SMALLEST (TableView::mm_k < 0, mcgpu.hip mc_create): the word that picks a key's bin is made of the two smallest sk_order
 // values among the window's canonical SK_M-mers (as a multiset: a value that occurs twice is both) instead of the smallest alone.
 // Runs of windows that share it are two thirds as long, and a region holds the k-mers of half again as many, smaller stretches of
 // the genome: scripts/bin_model.py -- at load 0.53 the fullest of 4 200 regions is 87 % full (116 % with the smallest alone, 1.6 % of
 // the regions above 90 %), which is what lets configs[2] at FULL size (4.6 G keys in the 2^21 regions the merge kernel takes) travel
 // as long records at all.  Either strand of a k-mer holds the same multiset, so the word is a function of the key.
-__host__ __device__ __forceinline__ uint32_t skl_word2(uint32_t lo, uint32_t hi) { return lo ^ (hi * 0x85EBCA6Bu); }
+// (skl_bin, the bin word of a hash key's minimizer, and skl_word2, the word of the two smallest, are in kmer_hash.h.)
 // (lo, hi) <- the two smallest of (lo, hi) and (blo, bhi)
 __device__ __forceinline__ void skl_merge2(uint32_t &lo, uint32_t &hi, uint32_t blo, uint32_t bhi)
 {
@@ -458,12 +455,7 @@ __global__ void __launch_bounds__(P3_THREADS) k_p3_long(const uint4 *__restrict_
             const uint32_t nw_own = have ? (q0.y & 0xFFu) + 1u : 0u;
             uint32_t cand = 0xFFFFFFFFu;  // the record mine may be a copy of
             if (have) {
-                uint32_t h = q0.z * 0x9E3779B1u ^ q0.w;
-                h = (h ^ (h >> 15)) * 0x85EBCA6Bu ^ q1.x;
-                h = (h ^ (h >> 13)) * 0xC2B2AE35u ^ q1.y;
-                h = (h ^ (h >> 16)) * 0x27D4EB2Fu ^ q1.z;
-                h = (h ^ (h >> 15)) * 0x165667B1u ^ q1.w ^ nw_own;
-                h ^= h >> 16;
+                const uint32_t h = skl_rec_hash(q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, nw_own);
                 const uint32_t mine_e = (h & 0xFFFF0000u) | (tid + 1u);
                 uint32_t sl = h & (SKL_DTAB - 1u);
 #pragma unroll

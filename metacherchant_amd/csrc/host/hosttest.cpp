@@ -25,12 +25,19 @@
 // `mc_hosttest placement <k>`: where the table puts a key (csrc/kmer_hash.h, the functions the kernels compile).  Reads hexadecimal
 // 64-bit words from stdin, one a line, and prints for each "fmix64 sk_order sk_bin sk_hmin_of_kmer": the hash of the word as a key, the
 // order and the bin of its low 32 bits, and the smallest order among the SK_M-mers of the word as a packed k-mer of k bases.
+// `mc_hosttest placement <k> poly`, k from 15 to 63: the same for a polynomial key in minimizer bins (csrc/count_long.h).  Reads a k-mer a
+// line as two hexadecimal words "hi lo" (2k bits right-aligned in 128, first base on top) and prints "key hmin bin word2 bin2 home": the
+// polynomial key, then under the smallest-hash rule sk_hmin_of_kmer2 and skl_bin of it, under the two-smallest rule the word of the two
+// smallest and skl_bin of it, and sk_home(key), the key's home slot inside its bin.
 // `mc_hosttest pointers <pos>...`: the code of a read pointer (csrc/read_ptr.h, the functions the kernels compile).  For every store
 // position (decimal) one line: ptr_encode(pos), ptr_decode of that code and its span (0 0 for no pointer), ptr_advance(code, j) for
 // j = 0 .. 15 and ptr_advance_long(code, j) for j = 0 .. 31.
 // `mc_hosttest dedup-tags <file>`: where the merge kernel's record table puts a super-k-mer record (csrc/kmer_hash.h dd_hash, the function
 // the kernel compiles).  file: a record a line as two hexadecimal 64-bit words "lo hi" (csrc/count_pipeline.h has the layout).  Prints for
 // each "hash tag place": dd_hash of the record's three words of bases, the tag (hash & 0xFFFF0000) | 0x8000 and the home place hash & 1023.
+// `mc_hosttest long-tags <file>`: where k_p3_long's table of equal records puts a long record (csrc/kmer_hash.h skl_rec_hash, the function
+// the kernel compiles).  file: a record a line as "windows X0 X1 X2", the window count in decimal and the three words of bases in
+// hexadecimal (csrc/count_long.h has the layout).  Prints for each "hash tag slot": the hash, hash >> 16 and hash & 1023.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -230,6 +237,30 @@ int main(int argc, char **argv)
                        mc::sk_hmin_of_kmer(k < 32 ? w & ((1ull << (2 * k)) - 1) : w, k));
             return 0;
         }
+        if (argc == 4 && std::string(argv[1]) == "placement" && std::string(argv[3]) == "poly") {
+            const int k = atoi(argv[2]);
+            if (k < mc::SK_M || k > 63) throw Error("placement poly: k from 15 to 63");
+            unsigned long long hi, lo;
+            while (scanf("%llx %llx", &hi, &lo) == 2) {
+                const mc::Kmer v{hi, lo};
+                const uint64_t key = (uint64_t)mc::key_poly_plain(v, k);
+                const uint32_t h1 = mc::sk_hmin_of_kmer2(v, k, false), h2 = mc::sk_hmin_of_kmer2(v, k, true);
+                printf("%llx %x %x %x %x %u\n", (unsigned long long)key, h1, mc::skl_bin(h1), h2, mc::skl_bin(h2), mc::sk_home(key));
+            }
+            return 0;
+        }
+        if (argc == 3 && std::string(argv[1]) == "long-tags") {
+            FILE *f = fopen(argv[2], "r");
+            if (!f) throw Error("cannot open the records file");
+            unsigned nw;
+            unsigned long long x0, x1, x2;
+            while (fscanf(f, "%u %llx %llx %llx", &nw, &x0, &x1, &x2) == 4) {
+                const uint32_t h = mc::skl_rec_hash((uint32_t)x0, (uint32_t)(x0 >> 32), (uint32_t)x1, (uint32_t)(x1 >> 32), (uint32_t)x2, (uint32_t)(x2 >> 32), nw);
+                printf("%x %x %u\n", h, h >> 16, h & 1023u);
+            }
+            fclose(f);
+            return 0;
+        }
         if (argc == 3 && std::string(argv[1]) == "dedup-tags") {
             FILE *f = fopen(argv[2], "r");
             if (!f) throw Error("cannot open the records file");
@@ -293,7 +324,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> | pointers <pos>... | dedup-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> [poly] | pointers <pos>... | dedup-tags <records> | long-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

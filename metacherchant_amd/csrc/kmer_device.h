@@ -5,17 +5,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kmer_hash.h"  // fmix64, rc_packed, sk_order, sk_bin, sk_hmin_of_kmer: the part a host compiler can read too
+#include "kmer_hash.h"  // Kmer, fmix64, rc_packed, key_poly_plain, sk_order, sk_bin, sk_hmin_of_kmer(2), sk_home: the part a host compiler can read too
 #include "read_ptr.h"   // ptr_encode, ptr_decode, ptr_advance, ptr_advance_long: likewise
 
 namespace mc {
 
 constexpr int KEY_PACKED = 0, KEY_POLY = 1, KEY_FNV1A = 2;
 constexpr uint64_t EMPTY_KEY = 0xFFFFFFFFFFFFFFFFull;  // never a packed key (those are < 2^62)
-
-struct Kmer {  // oriented k-mer, 2k bits right-aligned in 128, first base most significant
-    uint64_t hi, lo;
-};
 
 // SplitMix64, n-th output of the generator seeded with `seed` (DESIGN.md "Synthetic workload")
 __host__ __device__ __forceinline__ uint64_t splitmix(uint64_t seed, uint64_t n)
@@ -24,12 +20,6 @@ __host__ __device__ __forceinline__ uint64_t splitmix(uint64_t seed, uint64_t n)
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
-}
-
-__host__ __device__ __forceinline__ uint32_t base_at(const Kmer &v, int k, int i)
-{  // i-th base, 0 = first
-    const int sh = 2 * (k - 1 - i);
-    return (uint32_t)((sh >= 64 ? (v.hi >> (sh - 64)) : (v.lo >> sh)) & 3);
 }
 
 // All key functions also report `flipped`: whether the reverse-complement strand supplied the key
@@ -122,19 +112,6 @@ __host__ __device__ inline uint64_t poly_hash_r_tabled(const Kmer &v, int k, con
     }
     return hr;
 }
-// src/utils/PolynomialHash.java:19-28
-__host__ __device__ inline int64_t key_poly_plain(const Kmer &v, int k, bool *flipped = nullptr)
-{
-    uint64_t fw = 1, rc = 1;
-    for (int i = 0; i < k; i++) {
-        fw = fw * 5 + base_at(v, k, i);
-        rc = rc * 5 + (3u ^ base_at(v, k, k - 1 - i));
-    }
-    const int64_t a = (int64_t)fw, b = (int64_t)rc;
-    if (flipped) *flipped = b < a;
-    return a < b ? a : b;  // Math.min on signed longs
-}
-
 // The two 256-entry tables of poly_hashes_tabled as constants of the code object: a key worked out from scratch on the device --
 // every node of a round of the walk at k > 31, every window of the direct kernel -- takes k / 4 look-ups a strand instead of k
 // multiply-adds with a base extraction each (~1 400 instructions a key at k = 63: most of what a round of the walk computed).
@@ -325,37 +302,13 @@ struct Slot {
 // minimizer, which is what lets the counting pipeline move "super-k-mers" (a run of windows in one
 // 16-byte record) instead of one record per window (count_pipeline.h).  Nothing of this reaches a
 // result: it only decides where in the table a key lives.
-// (SK_M and its constants, sk_order, sk_bin and sk_hmin_of_kmer are in kmer_hash.h.)
+// (SK_M and its constants, sk_order, sk_bin, sk_hmin_of_kmer, sk_hmin_of_kmer2, sk_home_mix and sk_home are in kmer_hash.h.)
 // owner rank of everything that shares a minimizer (multi-GPU split): mixed differently from sk_bin, so that
 // the keys one rank owns still spread over all regions of its table
 __host__ __device__ __forceinline__ uint32_t sk_owner(uint32_t hmin, uint32_t n_owners)
 {
     return sk_bin(hmin ^ 0x5BD1E995u) % n_owners;
 }
-// ... of a k-mer of up to 64 bases (hi:lo, right-aligned).  Hash keys say nothing about their bases: where such keys live in
-// minimizer bins (k > 32 with polynomial keys, count_pipeline.h "long records") every look-up brings the k-mer itself.
-__host__ __device__ inline uint32_t sk_hmin_of_kmer2(const Kmer &v, int k, bool two = false)
-{   // two: the word made of the TWO smallest values, as a multiset (count_long.h skl_word2) -- tables with mm_k < 0
-    // (the bases are taken from the k-mer's END -- two bits off the bottom of hi:lo a step --: the set of SK_M-mers is the same from
-    // either side, and base_at's two variable 64-bit shifts a base were a third of what a look-up of the walk computed)
-    uint64_t lo = v.lo, hi = v.hi;
-    uint32_t f = 0, r = 0, best = SK_NONE, second = SK_NONE;
-    for (int i = 0; i < k; i++) {
-        const uint32_t b = (uint32_t)lo & 3u;
-        lo = (lo >> 2) | (hi << 62);
-        hi >>= 2;
-        f = (f >> 2) | (b << (2 * (SK_M - 1)));   // the SK_M-mer that STARTS at this base, first base on top
-        r = ((r << 2) | (3u - b)) & SK_MMASK;     // ... and its reverse complement
-        if (i >= SK_M - 1) {
-            const uint32_t h = sk_order(f < r ? f : r);
-            const uint32_t t = h > best ? h : best;
-            best = h < best ? h : best;
-            second = t < second ? t : second;
-        }
-    }
-    return two ? best ^ (second * 0x85EBCA6Bu) : best;
-}
-
 struct TableView {
     Slot *slots;
     uint32_t shift;   // 64 - (rb + sb)
@@ -375,19 +328,6 @@ struct TableView {
     // committed after all are dropped when the list is drained (0xFFFFFFFF: an entry of table_add's own, always kept).
     uint32_t *ovf_leaf;
 };
-
-// home slot inside a minimizer-bin region: 12 well-mixed bits of the key, cheaper than fmix64 (the
-// merge kernel of the counting pipeline computes it once per k-mer occurrence)
-#ifndef MC_REGION_LG
-#define MC_REGION_LG 12   // log2 of the slots of a table region = of the merge kernel's LDS image (tuning builds override it)
-#endif
-__host__ __device__ __forceinline__ uint32_t sk_home_mix(uint64_t key)
-{   // (the home slot is the top MC_REGION_LG bits; the merge kernel takes two more bits below them for its pointer rule)
-    uint32_t x = (uint32_t)key * 0x9E3779B1u + (uint32_t)(key >> 32) * 0x85EBCA6Bu;
-    x ^= x >> 15; x *= 0xC2B2AE35u;
-    return x;
-}
-__host__ __device__ __forceinline__ uint32_t sk_home(uint64_t key) { return sk_home_mix(key) >> (32 - MC_REGION_LG); }
 
 // 32 bits whose TOP bits number the region of a key (and, in the counting pipeline, its buckets)
 __host__ __device__ __forceinline__ uint32_t bin32_of(uint64_t key, int mm_k)

@@ -1,5 +1,6 @@
-// The placement arithmetic of a key that needs nothing of HIP: fmix64, the reverse complement of a packed k-mer, and the minimizer
-// order and bin of kmer_device.h "Minimizer bins".  kmer_device.h includes it for the kernels; mc_hosttest (csrc/host/hosttest.cpp
+// The placement arithmetic of a key that needs nothing of HIP: fmix64, the reverse complement of a packed k-mer, the polynomial key of
+// a k-mer of up to 64 bases, the minimizer order and bin of kmer_device.h "Minimizer bins", the home slot inside a bin, and the bin words
+// and the record hash of long records (count_long.h).  kmer_device.h includes it for the kernels; mc_hosttest (csrc/host/hosttest.cpp
 // `placement`) includes it alone and prints the values, which pins tests/crowded_tables.py's restatement to this code.
 #pragma once
 #include <stdint.h>
@@ -12,6 +13,29 @@
 #endif
 
 namespace mc {
+
+struct Kmer {  // oriented k-mer, 2k bits right-aligned in 128, first base most significant
+    uint64_t hi, lo;
+};
+
+__host__ __device__ __forceinline__ uint32_t base_at(const Kmer &v, int k, int i)
+{  // i-th base, 0 = first
+    const int sh = 2 * (k - 1 - i);
+    return (uint32_t)((sh >= 64 ? (v.hi >> (sh - 64)) : (v.lo >> sh)) & 3);
+}
+
+// src/utils/PolynomialHash.java:19-28
+__host__ __device__ inline int64_t key_poly_plain(const Kmer &v, int k, bool *flipped = nullptr)
+{
+    uint64_t fw = 1, rc = 1;
+    for (int i = 0; i < k; i++) {
+        fw = fw * 5 + base_at(v, k, i);
+        rc = rc * 5 + (3u ^ base_at(v, k, k - 1 - i));
+    }
+    const int64_t a = (int64_t)fw, b = (int64_t)rc;
+    if (flipped) *flipped = b < a;
+    return a < b ? a : b;  // Math.min on signed longs
+}
 
 __host__ __device__ constexpr __forceinline__ uint64_t fmix64(uint64_t x)
 {
@@ -77,6 +101,61 @@ __host__ __device__ inline uint32_t sk_hmin_of_kmer(uint64_t fw, int k)
         best = h < best ? h : best;
     }
     return best;
+}
+
+// ... of a k-mer of up to 64 bases (hi:lo, right-aligned).  Hash keys say nothing about their bases: where such keys live in
+// minimizer bins (k > 32 with polynomial keys, count_pipeline.h "long records") every look-up brings the k-mer itself.
+__host__ __device__ inline uint32_t sk_hmin_of_kmer2(const Kmer &v, int k, bool two = false)
+{   // two: the word made of the TWO smallest values, as a multiset (skl_word2 below) -- tables with mm_k < 0
+    // (the bases are taken from the k-mer's END -- two bits off the bottom of hi:lo a step --: the set of SK_M-mers is the same from
+    // either side, and base_at's two variable 64-bit shifts a base were a third of what a look-up of the walk computed)
+    uint64_t lo = v.lo, hi = v.hi;
+    uint32_t f = 0, r = 0, best = SK_NONE, second = SK_NONE;
+    for (int i = 0; i < k; i++) {
+        const uint32_t b = (uint32_t)lo & 3u;
+        lo = (lo >> 2) | (hi << 62);
+        hi >>= 2;
+        f = (f >> 2) | (b << (2 * (SK_M - 1)));   // the SK_M-mer that STARTS at this base, first base on top
+        r = ((r << 2) | (3u - b)) & SK_MMASK;     // ... and its reverse complement
+        if (i >= SK_M - 1) {
+            const uint32_t h = sk_order(f < r ? f : r);
+            const uint32_t t = h > best ? h : best;
+            best = h < best ? h : best;
+            second = t < second ? t : second;
+        }
+    }
+    return two ? best ^ (second * 0x85EBCA6Bu) : best;
+}
+
+// home slot inside a minimizer-bin region: 12 well-mixed bits of the key, cheaper than fmix64 (the
+// merge kernel of the counting pipeline computes it once per k-mer occurrence)
+#ifndef MC_REGION_LG
+#define MC_REGION_LG 12   // log2 of the slots of a table region = of the merge kernel's LDS image (tuning builds override it)
+#endif
+__host__ __device__ __forceinline__ uint32_t sk_home_mix(uint64_t key)
+{   // (the home slot is the top MC_REGION_LG bits; the merge kernel takes two more bits below them for its pointer rule)
+    uint32_t x = (uint32_t)key * 0x9E3779B1u + (uint32_t)(key >> 32) * 0x85EBCA6Bu;
+    x ^= x >> 15; x *= 0xC2B2AE35u;
+    return x;
+}
+__host__ __device__ __forceinline__ uint32_t sk_home(uint64_t key) { return sk_home_mix(key) >> (32 - MC_REGION_LG); }
+
+// Long records (count_long.h).  The bin word of a hash key's minimizer: sk_bin with its low byte cleared (see the record's second word)
+__host__ __device__ __forceinline__ uint32_t skl_bin(uint32_t hmin) { return sk_bin(hmin) & 0xFFFFFF00u; }
+// ... and the word made of a window's two smallest sk_order values (count_long.h "TWO SMALLEST")
+__host__ __device__ __forceinline__ uint32_t skl_word2(uint32_t lo, uint32_t hi) { return lo ^ (hi * 0x85EBCA6Bu); }
+// The hash of a long record's six words of bases and its window count (count_long.h k_p3_long): its top 16 bits are the record's
+// fingerprint in the merge kernel's table of equal records, its low 10 bits the record's home slot there.  `mc_hosttest long-tags`
+// prints it, which pins tests/long_loci.py's restatement to this code.
+__host__ __device__ __forceinline__ uint32_t skl_rec_hash(uint32_t z0, uint32_t w0, uint32_t x1, uint32_t y1, uint32_t z1, uint32_t w1, uint32_t n_windows)
+{
+    uint32_t h = z0 * 0x9E3779B1u ^ w0;
+    h = (h ^ (h >> 15)) * 0x85EBCA6Bu ^ x1;
+    h = (h ^ (h >> 13)) * 0xC2B2AE35u ^ y1;
+    h = (h ^ (h >> 16)) * 0x27D4EB2Fu ^ z1;
+    h = (h ^ (h >> 15)) * 0x165667B1u ^ w1 ^ n_windows;
+    h ^= h >> 16;
+    return h;
 }
 
 // The hash of a super-k-mer record's three words of bases (count_pipeline.h k_p3_dedup): its top 16 bits are the record's fingerprint
