@@ -593,13 +593,16 @@ static int table_alloc(mc_ctx *c, uint64_t n_regions)
 // the direct kernels, lookups and exports need real (EMPTY-initialised) slots
 // The table is about to hold other counts (or to move: growing and rehashing give the old block back to the pool): results
 // read before are void, and so is a walker's view of the ranks' tables (mc_shard_attach) -- it names this table's block
-// and geometry as they were.  ADVICE r4: the attachment used to survive, and the next walk read a freed block.
+// and geometry as they were.  ADVICE r4: the attachment used to survive, and the next walk read a freed block.  The solid
+// table built from the counts is stale with them.
 static inline void counts_changed(mc_ctx *c)
 {
     if (c->d_shards) { shard_detach_locked(c); c->shards_dropped = true; }
     c->finalized = false;
     c->dup.checked = false;
     c->dup.l2_valid = false;
+    c->solid_cov = -1;
+    c->solid_external = false;
 }
 
 int materialize(mc_ctx *c)
@@ -1113,6 +1116,25 @@ int ensure_dups(mc_ctx *c)
     return MC_OK;
 }
 
+// What a function of the counting driver (from here to add_records_binned, and the run-cutting loops behind it) may return
+// besides MC_OK and the negative MC_* errors.  Each function's comment lists the ones it returns; a caller handles each by name,
+// and none leaves through the C ABI (abi_result).
+enum RunOutcome : int {
+    RUN_LOST_RECORDS = 1,      // the streams lost records and nothing was merged: the caller counts the batch another way
+    RUN_NOT_BINNED = 2,        // the table's level-1 buckets are not unions of the fine ones: the caller takes the flat stream
+    RUN_BATCH_AGAIN = 3,       // the (empty) table was too small and has been replaced by one of the right size: the batch once more
+    RUN_NOT_LONG = 4,          // not as long records: the caller takes the per-window form
+    RUN_BEYOND_LEAF_BITS = 5,  // the wanted table is beyond the reach of the records' ten leaf bits: the first level again, two arrays
+    RUN_RESPLIT = 6,           // the run must be cut again: the table has left its minimizer bins under it and takes one record a window now
+};
+static const char *const RUN_OUTCOME_NAMES[] = {"ok", "lost records", "not binned", "batch again", "not as long records", "beyond the leaf bits", "cut the run again"};
+
+// a driver result on its way out through the C ABI: every outcome has been handled by then
+static int abi_result(mc_ctx *c, int rc)
+{
+    return rc > 0 ? fail(c, MC_EINVAL, "internal: the counting driver's outcome %d (%s) was left unhandled", rc, rc <= RUN_RESPLIT ? RUN_OUTCOME_NAMES[rc] : "unknown") : rc;
+}
+
 struct PipePlan {
     uint32_t b1 = 0, b2 = 1, g = 0;  // b1 level-1 buckets of b2 leaves each (counts, not bits); a leaf covers 2^g regions
     uint64_t np1 = 0, n_leaves = 0, cap1 = 0, cap2 = 0, spill_cap = 0, wb = 0;
@@ -1137,6 +1159,33 @@ struct PipePlan {
     const uint32_t *in_ptrs = nullptr;
     SpillView sp{};
     SkSpill sks{};
+    // What the caller of pipe_finish has done already, and what it can do afterwards:
+    double ms1 = 0;           // time of the level-1 scatter that filled the a_* buckets, where the caller waited for it
+    // p1_pending: the caller recorded ev_t[0], enqueued P1 and did not wait: P2 and P3 follow on the stream at once and
+    // the host hears of all three together (a host round trip between two kernels leaves the device idle for tens of us)
+    bool p1_pending = false;
+    bool p2_done = false;     // the caller ran P2 itself, piece by piece behind P1 (ms2 = its time)
+    double ms2 = 0;
+    bool may_rerun = false;   // the caller can run the batch again (RUN_BATCH_AGAIN)
+};
+
+// What a caller asks of pipe_prepare
+struct PipeRequest {
+    uint64_t n_records = 0;        // != 0: the key occurrences travel as (an estimated) n_records super-k-mer records
+    uint32_t nseg1 = PT_SEGMENTS;  // PipePlan::nseg1
+    uint32_t pieces = 1;           // PipePlan::pieces
+    // compact_tiles != 0: the caller's level-1 kernel is k_sk1w_extract over this many tiles in one piece and can write the compact
+    // form: taken up when the rest of the run allows it (a second level through the staged kernel, one region per leaf, segments
+    // short enough for 22-bit positions)
+    uint64_t compact_tiles = 0;
+    bool lng = false;              // PipePlan::lng
+    // listed: PipePlan::listed -- no first-level streams (the solid list alone may want pipe.a_recs), the caller has filled
+    // pipe.seg_counts1 (np1 x nseg1 fill levels) and pipe.skb_seg_start already
+    bool listed = false;
+    // level2_only: the level-1 scatter has run and the table has since been replaced by one of another size (pipe_resize_by_sample):
+    // the plan of the second level and of the merge is made again for it; level 1 (buckets, segments, their fill levels, the
+    // spill list) stays as it is -- the caller has checked that the new table splits into the same level-1 buckets
+    bool level2_only = false;
 };
 
 // first_read[t] for every tile (count_pipeline.h): by the reads where they are short, by a search per tile otherwise
@@ -1208,18 +1257,16 @@ static int pipe_reserve(mc_ctx *c, uint64_t wb, bool *hint_holds_out)
 }
 
 // Table capacity check, scratch buffers and cursors for one run of the partitioned pipeline over
-// `wb` key occurrences.  n_records != 0: they travel as (an estimated) n_records super-k-mer records.
-static int pipe_prepare(mc_ctx *c, uint64_t wb, PipePlan *pl, uint64_t n_records = 0, uint32_t nseg1 = PT_SEGMENTS, uint32_t pieces = 1,
-                        bool level2_only = false, uint64_t compact_tiles = 0, bool lng = false, bool listed = false)
-{   // listed: PipePlan::listed -- no first-level streams (the solid list alone may want pipe.a_recs), the caller has filled
-    // pipe.seg_counts1 (np1 x nseg1 fill levels) and pipe.skb_seg_start already
+// `wb` key occurrences, as `rq` asks.  Returns MC_OK or an error, no outcome.
+static int pipe_prepare(mc_ctx *c, uint64_t wb, PipePlan *pl, const PipeRequest &rq)
+{
+    const uint64_t n_records = rq.n_records, compact_tiles = rq.compact_tiles;
+    const uint32_t nseg1 = rq.nseg1;
+    uint32_t pieces = rq.pieces;
+    const bool lng = rq.lng, listed = rq.listed, level2_only = rq.level2_only;
     pl->lng = lng;
     pl->listed = listed;
-    const uint64_t rw = lng ? 2 : 1;  // 16-byte words a record   // compact_tiles != 0: the caller's level-1 kernel is k_sk1w_extract over this many tiles in one piece and can write the compact
-    // form: taken up when the rest of the run allows it (a second level through the staged kernel, one region per leaf, segments
-    // short enough for 22-bit positions)   // level2_only: the level-1 scatter has run and the table has since been replaced by one of another size (pipe_resize_by_sample):
-    // the plan of the second level and of the merge is made again for it; level 1 (buckets, segments, their fill levels, the
-    // spill list) stays as it is -- the caller has checked that the new table splits into the same level-1 buckets
+    const uint64_t rw = lng ? 2 : 1;  // 16-byte words a record
     pl->nseg1 = nseg1;
     pl->pieces = pieces;
     mc_ctx::Pipe &P = c->pipe;
@@ -1367,6 +1414,7 @@ static int pipe_drain_handed_on(mc_ctx *c, uint64_t n_listed, bool lng = false)
 // distinct k-mers are counted into a scratch set, the table is replaced by one of the size they call for, and the second
 // level and the merge are planned for that table: the batch is scattered once (before, the merge of 1024 leaves told the
 // size, and then everything ran again: 31 ms of counting on configs[1] against 19 with a hint).
+// Outcomes: RUN_BEYOND_LEAF_BITS (pl.vleaf only), RUN_NOT_LONG (pl.lng only).
 static int pipe_resize_by_sample(mc_ctx *c, PipePlan &pl, uint64_t n_records)
 {
     mc_ctx::Pipe &P = c->pipe;
@@ -1402,10 +1450,10 @@ static int pipe_resize_by_sample(mc_ctx *c, PipePlan &pl, uint64_t n_records)
         if (est > 0.45 * (double)(p2 << c->sb)) p2 *= 2;
         uint64_t reach = (uint64_t)PT_MAX_BUCKETS * 1024;
         reach = std::min<uint64_t>(reach, c->sw.sk_vleaf_max_regions);  // (tests: the way back at a small size)
-        if (p2 > reach) return 5;
+        if (p2 > reach) return RUN_BEYOND_LEAF_BITS;
         want = p2;
     }
-    if (pl.lng && est > 0.40 * (double)(want << c->sb)) return 4;  // (hash keys need their bins roomy, mc_create: the caller takes the per-window form)
+    if (pl.lng && est > 0.40 * (double)(want << c->sb)) return RUN_NOT_LONG;  // (hash keys need their bins roomy, mc_create: the caller takes the per-window form)
     if (pl.lng && want <= c->n_regions) { pl.guessed = false; return MC_OK; }  // (the table it was created with holds the batch)
     if (c->sw.ingest_debug) fprintf(stderr, "[count] first bucket: %llu distinct k-mers, %.0f M expected in all; table of %llu regions, %llu wanted\n",
                      (unsigned long long)c->h_scratch[24], est / 1e6, (unsigned long long)c->n_regions, (unsigned long long)want);
@@ -1419,7 +1467,12 @@ static int pipe_resize_by_sample(mc_ctx *c, PipePlan &pl, uint64_t n_records)
         c->st.grows++;
         HIPCHK(c, hipMemsetAsync(c->d_ctr + 6, 0, sizeof(unsigned long long), c->stream));  // keys at the coverage threshold: none yet
         PipePlan p2 = pl;
-        rc = pipe_prepare(c, pl.wb, &p2, n_records, pl.nseg1, 1, true, 0, pl.lng);
+        PipeRequest rq;
+        rq.n_records = n_records;
+        rq.nseg1 = pl.nseg1;
+        rq.lng = pl.lng;
+        rq.level2_only = true;
+        rc = pipe_prepare(c, pl.wb, &p2, rq);
         if (rc) return rc;
         if (p2.np1 != pl.np1 || p2.cap1 != pl.cap1 || p2.g != 0) return fail(c, MC_EINVAL, "internal: the resized table does not keep the level-1 buckets");
         pl = p2;
@@ -1430,282 +1483,315 @@ static int pipe_resize_by_sample(mc_ctx *c, PipePlan &pl, uint64_t n_records)
     return MC_OK;
 }
 
-// P2, P3 (with the retry after growing the table), spill drain and bookkeeping; ms1 = time of the
-// level-1 scatter that filled the a_* buckets.  Returns 1 (nothing merged yet) when the streams
-// overflowed even their spill list: the caller then counts the batch with the direct kernel.
-static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false, double ms2_exposed = 0, bool p1_pending = false,
-                       bool may_rerun = false)
-{   // p2_done: the caller ran P2 itself, piece by piece behind P1 (ms2_exposed = its time)
-    // p1_pending: the caller recorded ev_t[0], enqueued P1 and did not wait: P2 and P3 follow on the stream at once and
-    // the host hears of all three together (a host round trip between two kernels leaves the device idle for tens of us)
-    mc_ctx::Pipe &P = c->pipe;
-    const uint64_t np1 = pl.np1, n_leaves = pl.n_leaves;
-    const int k = c->cfg.k;
-    int rc;
-    double ms2 = ms2_exposed, ms3 = 0;
+constexpr uint32_t P3_MAX_GRID = 256 * 2 * 4 * (D2_THREADS < P3_THREADS ? P3_THREADS / D2_THREADS : 1);  // workgroups of a merge launch at most
+
+// One run of pipe_finish, as its stages (below, in the order they run) leave it to one another.  The plan goes with it: a stage that
+// times level 1 or runs level 2 says so there (p1_pending, p2_done, ms1, ms2).
+struct PipeRun {
+    PipePlan &pl;
     // P3 reads the leaves: P2's output (one segment each), or P1's buckets directly when there is no second level
-    const void *lk = pl.sk ? (pl.b2 > 1 ? (const void *)P.b_recs : (const void *)P.a_recs)
-                           : (pl.b2 > 1 ? (const void *)P.b_keys : (const void *)P.a_keys);
-    const uint32_t *lh = pl.compact ? nullptr : (pl.b2 > 1 ? P.b_hints : P.a_hints);  // (compact: the pointers sit in the records)
-    const uint32_t *lc = pl.b2 > 1 ? P.cursors2 : P.seg_counts1;
-    const uint64_t lcap = pl.b2 > 1 ? pl.cap2 : pl.cap1;
-    const uint32_t lseg = pl.b2 > 1 ? pl.pieces : pl.nseg1;
-    // The solid list (P3Emit): super-k-mer form with the leaves in b_recs, so that a_recs is free to take it, and a
-    // threshold to track.  Each P3 workgroup owns a segment.
-    const int p3_grid = (int)std::min<uint64_t>(n_leaves, 256 * 2 * 4 * (D2_THREADS < P3_THREADS ? P3_THREADS / D2_THREADS : 1));
-    P3Emit emit{nullptr, nullptr, 0, P.flags + 2};
-    if (pl.sk && pl.b2 > 1 && c->mm_k && c->solid_tracked && c->cov_hint > 0 && c->want_list) {
-        if (!P.emit_counts) HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&P.emit_counts), 256 * 2 * 4 * (D2_THREADS < P3_THREADS ? P3_THREADS / D2_THREADS : 1) * sizeof(uint32_t)));
-        HIPCHK(c, hipMemsetAsync(P.emit_counts, 0, 256 * 2 * 4 * (D2_THREADS < P3_THREADS ? P3_THREADS / D2_THREADS : 1) * sizeof(uint32_t), c->stream));
-        emit.recs = P.a_recs;
-        emit.counts = P.emit_counts;
-        emit.seg_cap = std::min<uint64_t>(P.a_recs_cap / (uint64_t)p3_grid, 0xFFFFFFF0ull);
-    }
+    const void *lk = nullptr;
+    const uint32_t *lh = nullptr, *lc = nullptr;  // (lh null: the compact form, the pointers sit in the records)
+    uint64_t lcap = 0;
+    uint32_t lseg = 0;
+    int p3_grid = 0;
+    P3Emit emit{};
+    bool virgin0 = false;           // the table held nothing before this run
+    uint32_t flags[3] = {0, 0, 0};  // read back: records were lost, a region overflowed, a segment of the solid list overflowed
+    unsigned long long n_spill = 0, n_handed_on = 0;
+    double ms3 = 0, ms4 = 0;  // the merge, the spill drain
+};
+
+// Which merge kernel takes the leaves and with which template arguments: the debug line and the launch both go by this.
+struct MergeChoice {
+    bool lng, dedup;            // k_p3_long<long_k>, k_p3_dedup<virgin, one_gpu, k31>, or neither: k_p3_merge
+    bool virgin, one_gpu, k31;
+    bool general_behind;        // k_p3_merge right behind k_p3_dedup
+    int long_k;
+};
+static MergeChoice merge_choice(const mc_ctx *c, const PipeRun &R, int virgin)
+{
+    const int k = c->cfg.k;
+    MergeChoice m{};
+    m.lng = R.pl.lng;
     // super-k-mer records, one region and one segment per leaf: the merge kernel that merges identical records first
     // (count_pipeline.h k_p3_dedup; MC_P3_DEDUP=0: the general kernel)
-    auto launch_p3_n = [&](uint32_t leaves, int grid, int virgin) {
-#define P3_ARGS lk, lh, lc, lcap, lseg, leaves, pl.g, c->view(), virgin, P.leaf_state, P.leaf_new, P.flags + 1, \
-                (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, emit, c->ptr_tries, P.flags
-#define P3D_ARGS static_cast<const uint4 *>(lk), lh, lc, lcap, leaves, c->view(), P.leaf_state, P.leaf_new, P.flags + 1, \
-                 (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, emit, c->ptr_tries, P.flags
-        if (c->sw.ingest_debug) {  // (every run of the merge stage: which kernel takes the leaves)
-            const bool dedup = !pl.lng && pl.sk && pl.g == 0 && lseg == 1 && c->sw.p3_dedup;
-            const bool one_gpu = c->ptr_tries == 1 && (emit.recs == nullptr || !(c->solid_tracked && c->cov_hint > 0));
-            char name[64];
-            if (pl.lng) snprintf(name, sizeof name, "k_p3_long");
-            else if (dedup) snprintf(name, sizeof name, "k_p3_dedup<%d, %d, %d>", virgin ? 1 : 0, one_gpu ? 1 : 0, virgin && one_gpu && k == 31 ? 1 : 0);
-            else snprintf(name, sizeof name, "k_p3_merge<%s>", pl.sk ? "true" : "false");
-            fprintf(stderr, "[count] merge: %s over %u leaves, lcap %llu, ptr_tries %u, general kernel behind it: %s\n", name, leaves,
-                    (unsigned long long)lcap, c->ptr_tries, dedup && lcap > DD_MAX_CAP ? "yes" : "no");
-        }
-        if (pl.lng) {
-#define P3L_ARGS static_cast<const uint4 *>(lk), lc, lcap, leaves, c->view(), virgin, P.leaf_state, P.leaf_new, P.flags + 1, \
-                 (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, emit, P.flags, c->dup_l1_view()
-            // (built for the k-mer lengths people run -- constant shifts, trip counts and powers of 5 --, and for any other from the argument)
-            if (k == 63) hipLaunchKernelGGL(k_p3_long<63>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
-            else if (k == 55) hipLaunchKernelGGL(k_p3_long<55>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
-            else if (k == 47) hipLaunchKernelGGL(k_p3_long<47>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
-            else if (k == 41) hipLaunchKernelGGL(k_p3_long<41>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
-            else hipLaunchKernelGGL(k_p3_long<0>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
-#undef P3L_ARGS
-        } else if (pl.sk && pl.g == 0 && lseg == 1 && c->sw.p3_dedup) {
-            const bool one_gpu = c->ptr_tries == 1 && (emit.recs == nullptr || !(c->solid_tracked && c->cov_hint > 0));
-            if (virgin && one_gpu && k == 31) hipLaunchKernelGGL((k_p3_dedup<true, true, true>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
-            else if (virgin && one_gpu) hipLaunchKernelGGL((k_p3_dedup<true, true>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
-            else if (virgin) hipLaunchKernelGGL((k_p3_dedup<true, false>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
-            else if (one_gpu) hipLaunchKernelGGL((k_p3_dedup<false, true>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
-            else hipLaunchKernelGGL((k_p3_dedup<false, false>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
-            // (it leaves the leaves of more than DD_MAX_CAP records alone: where the capacity allows such leaves, the general
-            // kernel follows at once and takes what is left -- it skips the merged ones, ~20 us when that is all of them)
-            if (lcap > DD_MAX_CAP) hipLaunchKernelGGL(k_p3_merge<true>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3_ARGS);
-        } else if (pl.sk) {
-            hipLaunchKernelGGL(k_p3_merge<true>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3_ARGS);
-        } else {
-            hipLaunchKernelGGL(k_p3_merge<false>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3_ARGS);
-        }
+    m.dedup = !m.lng && R.pl.sk && R.pl.g == 0 && R.lseg == 1 && c->sw.p3_dedup;
+    m.virgin = virgin;
+    m.one_gpu = c->ptr_tries == 1 && (R.emit.recs == nullptr || !(c->solid_tracked && c->cov_hint > 0));
+    m.k31 = m.virgin && m.one_gpu && k == 31;
+    // (k_p3_dedup leaves the leaves of more than DD_MAX_CAP records alone: where the capacity allows such leaves, the general
+    // kernel follows at once and takes what is left -- it skips the merged ones, ~20 us when that is all of them)
+    m.general_behind = m.dedup && R.lcap > DD_MAX_CAP;
+    // (built for the k-mer lengths people run -- constant shifts, trip counts and powers of 5 --, and for any other from the argument)
+    m.long_k = k == 63 || k == 55 || k == 47 || k == 41 ? k : 0;
+    return m;
+}
+
+// the merge kernel over the first `leaves` leaves
+static void launch_merge(mc_ctx *c, const PipeRun &R, uint32_t leaves, int grid, int virgin)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    const PipePlan &pl = R.pl;
+    const int k = c->cfg.k;
+    const MergeChoice m = merge_choice(c, R, virgin);
+#define P3_ARGS R.lk, R.lh, R.lc, R.lcap, R.lseg, leaves, pl.g, c->view(), virgin, P.leaf_state, P.leaf_new, P.flags + 1, \
+                (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, R.emit, c->ptr_tries, P.flags
+#define P3D_ARGS static_cast<const uint4 *>(R.lk), R.lh, R.lc, R.lcap, leaves, c->view(), P.leaf_state, P.leaf_new, P.flags + 1, \
+                 (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, R.emit, c->ptr_tries, P.flags
+#define P3L_ARGS static_cast<const uint4 *>(R.lk), R.lc, R.lcap, leaves, c->view(), virgin, P.leaf_state, P.leaf_new, P.flags + 1, \
+                 (uint32_t)(c->solid_tracked ? c->cov_hint : 0), c->d_ctr + 6, k, R.emit, P.flags, c->dup_l1_view()
+    if (c->sw.ingest_debug) {  // (every run of the merge stage: which kernel takes the leaves)
+        char name[64];
+        if (m.lng) snprintf(name, sizeof name, "k_p3_long");
+        else if (m.dedup) snprintf(name, sizeof name, "k_p3_dedup<%d, %d, %d>", m.virgin ? 1 : 0, m.one_gpu ? 1 : 0, m.k31 ? 1 : 0);
+        else snprintf(name, sizeof name, "k_p3_merge<%s>", pl.sk ? "true" : "false");
+        fprintf(stderr, "[count] merge: %s over %u leaves, lcap %llu, ptr_tries %u, general kernel behind it: %s\n", name, leaves,
+                (unsigned long long)R.lcap, c->ptr_tries, m.general_behind ? "yes" : "no");
+    }
+    if (m.lng) {
+        if (m.long_k == 63) hipLaunchKernelGGL(k_p3_long<63>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
+        else if (m.long_k == 55) hipLaunchKernelGGL(k_p3_long<55>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
+        else if (m.long_k == 47) hipLaunchKernelGGL(k_p3_long<47>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
+        else if (m.long_k == 41) hipLaunchKernelGGL(k_p3_long<41>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
+        else hipLaunchKernelGGL(k_p3_long<0>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3L_ARGS);
+    } else if (m.dedup) {
+        if (m.k31) hipLaunchKernelGGL((k_p3_dedup<true, true, true>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
+        else if (m.virgin && m.one_gpu) hipLaunchKernelGGL((k_p3_dedup<true, true>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
+        else if (m.virgin) hipLaunchKernelGGL((k_p3_dedup<true, false>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
+        else if (m.one_gpu) hipLaunchKernelGGL((k_p3_dedup<false, true>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
+        else hipLaunchKernelGGL((k_p3_dedup<false, false>), dim3(grid), dim3(D2_THREADS), 0, c->stream, P3D_ARGS);
+        if (m.general_behind) hipLaunchKernelGGL(k_p3_merge<true>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3_ARGS);
+    } else if (pl.sk) {
+        hipLaunchKernelGGL(k_p3_merge<true>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3_ARGS);
+    } else {
+        hipLaunchKernelGGL(k_p3_merge<false>, dim3(grid), dim3(P3_THREADS), 0, c->stream, P3_ARGS);
+    }
 #undef P3_ARGS
 #undef P3D_ARGS
-    };
-    auto launch_p3 = [&] { launch_p3_n((uint32_t)n_leaves, p3_grid, c->virgin ? 1 : 0); };
-    // hash keys in minimizer bins: the merge kernel also leaves every key it writes back in the key streams of dup_check.h, sized
-    // by what is known about the number of keys the table will hold
-    if (pl.lng && hash_bins(c) && pl.g == 0)
-        dup_arm(c, c->cfg.capacity_hint ? (double)c->cfg.capacity_hint : c->dup.expected_keys, (uint32_t)p3_grid);
+#undef P3L_ARGS
+}
+static void launch_merge_all(mc_ctx *c, const PipeRun &R) { launch_merge(c, R, (uint32_t)R.pl.n_leaves, R.p3_grid, c->virgin ? 1 : 0); }
+
+// the second scatter level: the level-1 buckets (or the caller's listed records) into their leaves
+static void launch_level2(mc_ctx *c, const PipePlan &pl)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    const uint64_t np1 = pl.np1;
+    static bool told = false;  // (once a process)
+    if (c->sw.ingest_debug && !told) {  // (where the streams lie: the second level's time differs between processes that differ in nothing else)
+        told = true;
+        fprintf(stderr, "[count] level-1 stream %p (%llu records a segment), level-2 stream %p (%llu a leaf), table %p\n", (void *)P.a_recs,
+                (unsigned long long)pl.cap1, (void *)P.b_recs, (unsigned long long)pl.cap2, (void *)c->slots);
+    }
+    if (pl.lng)
+        hipLaunchKernelGGL((k_sk2_scatter_compact<2, 2>), dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, pl.cap1,
+                           P.seg_counts1, (uint32_t)np1, pl.b2, P.cursors2, pl.cap2, P.b_recs, pl.sks, pl.nseg1, c->cur_ptr_base, pl.pos0,
+                           (uint64_t)pl.chunk_tiles * P1L_TILE);
+    else if (pl.sk && pl.compact && !pl.listed)
+        hipLaunchKernelGGL(k_sk2_scatter_compact<MC_SK2C_ITEMS>, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, pl.cap1,
+                           P.seg_counts1, (uint32_t)np1, pl.b2, P.cursors2, pl.cap2, P.b_recs, pl.sks, pl.nseg1, c->cur_ptr_base, pl.pos0,
+                           (uint64_t)pl.chunk_tiles * p1w_tile(false), pl.vleaf ? 10u - (uint32_t)__builtin_ctz(pl.b2) : 0u);
+    else if (pl.listed)
+        hipLaunchKernelGGL((k_sk2_scatter_staged<MC_SK2_ITEMS, true, false>), dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, pl.in_recs, pl.in_ptrs, (uint64_t)0,
+                           P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_recs, nullptr, pl.sks, pl.nseg1, P.skb_seg_start, nullptr);
+    else if (pl.sk)
+        hipLaunchKernelGGL(k_sk2_scatter_staged<MC_SK2_ITEMS>, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, P.a_hints, pl.cap1,
+                           P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_recs, P.b_hints, pl.sks, pl.nseg1);
     else
-        c->dup.l1_armed = false;
-    uint32_t flags[3] = {0, 0, 0};
-    unsigned long long n_spill = 0, n_handed_on = 0;
-    const bool virgin0 = c->virgin;
-    auto launch_p2 = [&] {
-        static bool told = false;  // (once a process)
-        if (c->sw.ingest_debug && !told) {  // (where the streams lie: the second level's time differs between processes that differ in nothing else)
-            told = true;
-            fprintf(stderr, "[count] level-1 stream %p (%llu records a segment), level-2 stream %p (%llu a leaf), table %p\n", (void *)P.a_recs,
-                    (unsigned long long)pl.cap1, (void *)P.b_recs, (unsigned long long)pl.cap2, (void *)c->slots);
-        }
-        if (pl.lng)
-            hipLaunchKernelGGL((k_sk2_scatter_compact<2, 2>), dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, pl.cap1,
-                               P.seg_counts1, (uint32_t)np1, pl.b2, P.cursors2, pl.cap2, P.b_recs, pl.sks, pl.nseg1, c->cur_ptr_base, pl.pos0,
-                               (uint64_t)pl.chunk_tiles * P1L_TILE);
-        else if (pl.sk && pl.compact && !pl.listed)
-            hipLaunchKernelGGL(k_sk2_scatter_compact<MC_SK2C_ITEMS>, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, pl.cap1,
-                               P.seg_counts1, (uint32_t)np1, pl.b2, P.cursors2, pl.cap2, P.b_recs, pl.sks, pl.nseg1, c->cur_ptr_base, pl.pos0,
-                               (uint64_t)pl.chunk_tiles * p1w_tile(false), pl.vleaf ? 10u - (uint32_t)__builtin_ctz(pl.b2) : 0u);
-        else if (pl.listed)
-            hipLaunchKernelGGL((k_sk2_scatter_staged<MC_SK2_ITEMS, true, false>), dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, pl.in_recs, pl.in_ptrs, (uint64_t)0,
-                               P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_recs, nullptr, pl.sks, pl.nseg1, P.skb_seg_start, nullptr);
-        else if (pl.sk)
-            hipLaunchKernelGGL(k_sk2_scatter_staged<MC_SK2_ITEMS>, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_recs, P.a_hints, pl.cap1,
-                               P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_recs, P.b_hints, pl.sks, pl.nseg1);
-        else
-            hipLaunchKernelGGL(k_p2_scatter, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_keys, P.a_hints, pl.cap1,
-                               P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_keys, P.b_hints, pl.sp, c->mm_k);
-    };
-    // how many distinct keys the batch holds, judged by the leaves merged so far (a table that held nothing before)
-    auto resize_for_batch = [&](uint64_t sample_leaves) -> int {
-        std::vector<uint32_t> st(sample_leaves), nw(sample_leaves);
-        HIPCHK(c, hipMemcpy(st.data(), P.leaf_state, sample_leaves * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(nw.data(), P.leaf_new, sample_leaves * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        uint64_t merged = 0, added = 0;
-        for (uint64_t i = 0; i < sample_leaves; i++)
-            if (st[i]) { merged++; added += nw[i]; }
-        {   // occurrences the merged leaves handed on to the next region (ovf_push) are keys too, nearly all of them new
-            unsigned long long ho = 0;
-            HIPCHK(c, hipMemcpy(&ho, c->d_ctr + 7, sizeof ho, hipMemcpyDeviceToHost));
-            added += std::min<uint64_t>(ho, mc_ctx::OVF_CAP);
-            if (ho > mc_ctx::OVF_CAP) added += (uint64_t)((double)(ho - mc_ctx::OVF_CAP));
-        }
-        // (the leaves that overflowed hold more than the average: at least a full leaf each)
-        const uint64_t per_full = (uint64_t)REGION_SLOTS << pl.g;
-        const double est = ((double)added + (double)(sample_leaves - merged) * (double)per_full * 1.5) * ((double)n_leaves / (double)sample_leaves) * 1.1 + 1024.0;
-        const double load = c->mm_k ? 0.36 : 0.6;
-        if (merged == sample_leaves && est <= (c->mm_k ? 0.5 : 0.7) * (double)c->n_slots()) return MC_OK;  // it fits: carry on
-        uint64_t want = regions_for(c, c->mm_k ? mm_slots_for(c, est, load) : (uint64_t)(est / load));
-        if (want <= c->n_regions) want = regions_for(c, c->n_slots() * 2);
-        if (c->sw.ingest_debug) fprintf(stderr, "[count] table too small: %llu of %llu sampled leaves merged, %llu keys in them: %.0f M keys expected; new table %.1f GB\n",
-                         (unsigned long long)merged, (unsigned long long)sample_leaves, (unsigned long long)added, est / 1e6, (double)(want << c->sb) * 16 / 1e9);
-        table_release(c, c->slots, c->slots_bytes);
-        c->slots = nullptr;
-        int r = table_alloc(c, want);  // (fresh device memory comes zeroed by the driver at ~30 GB/s: 0.7 s for 22 GB, once)
-        if (r) return r;
-        c->st.grows++;
-        HIPCHK(c, hipMemsetAsync(c->d_ctr + 6, 0, 2 * sizeof(unsigned long long), c->stream));  // keys at the coverage threshold: none yet; nothing handed on
-        return 3;
-    };
-    if (may_rerun && virgin0 && pl.guessed && n_leaves >= 8192 && pl.b2 > 1 && !p2_done) {
-        // Nothing vouches for the table's size (no capacity hint): merge 1024 leaves first -- the bin word is a mixed hash,
-        // any range of leaves is a fair sample -- and see what they hold.  Costs a host round trip; a whole merge into a
-        // table that turns out too small costs seven times the run.
-        const uint64_t K = 1024;
-        HIPCHK(c, hipEventRecord(c->ev_t[1], c->stream));
-        launch_p2();
+        hipLaunchKernelGGL(k_p2_scatter, dim3((unsigned)np1), dim3(PT_THREADS), 0, c->stream, P.a_keys, P.a_hints, pl.cap1,
+                           P.seg_counts1, (uint32_t)np1, pl.b1, pl.b2, P.cursors2, pl.cap2, P.b_keys, P.b_hints, pl.sp, c->mm_k);
+}
+
+// How many distinct keys the batch holds, judged by the first sample_leaves leaves as the merge kernel left them (a table that held
+// nothing before).  MC_OK: the table holds the batch.  Outcomes: RUN_BATCH_AGAIN, the table has been replaced by one that does.
+static int resize_for_batch(mc_ctx *c, const PipePlan &pl, uint64_t sample_leaves)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    std::vector<uint32_t> st(sample_leaves), nw(sample_leaves);
+    HIPCHK(c, hipMemcpy(st.data(), P.leaf_state, sample_leaves * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(nw.data(), P.leaf_new, sample_leaves * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint64_t merged = 0, added = 0;
+    for (uint64_t i = 0; i < sample_leaves; i++)
+        if (st[i]) { merged++; added += nw[i]; }
+    {   // occurrences the merged leaves handed on to the next region (ovf_push) are keys too, nearly all of them new
+        unsigned long long ho = 0;
+        HIPCHK(c, hipMemcpy(&ho, c->d_ctr + 7, sizeof ho, hipMemcpyDeviceToHost));
+        added += std::min<uint64_t>(ho, mc_ctx::OVF_CAP);
+        if (ho > mc_ctx::OVF_CAP) added += (uint64_t)((double)(ho - mc_ctx::OVF_CAP));
+    }
+    // (the leaves that overflowed hold more than the average: at least a full leaf each)
+    const uint64_t per_full = (uint64_t)REGION_SLOTS << pl.g;
+    const double est = ((double)added + (double)(sample_leaves - merged) * (double)per_full * 1.5) * ((double)pl.n_leaves / (double)sample_leaves) * 1.1 + 1024.0;
+    const double load = c->mm_k ? 0.36 : 0.6;
+    if (merged == sample_leaves && est <= (c->mm_k ? 0.5 : 0.7) * (double)c->n_slots()) return MC_OK;  // it fits: carry on
+    uint64_t want = regions_for(c, c->mm_k ? mm_slots_for(c, est, load) : (uint64_t)(est / load));
+    if (want <= c->n_regions) want = regions_for(c, c->n_slots() * 2);
+    if (c->sw.ingest_debug) fprintf(stderr, "[count] table too small: %llu of %llu sampled leaves merged, %llu keys in them: %.0f M keys expected; new table %.1f GB\n",
+                     (unsigned long long)merged, (unsigned long long)sample_leaves, (unsigned long long)added, est / 1e6, (double)(want << c->sb) * 16 / 1e9);
+    table_release(c, c->slots, c->slots_bytes);
+    c->slots = nullptr;
+    int r = table_alloc(c, want);  // (fresh device memory comes zeroed by the driver at ~30 GB/s: 0.7 s for 22 GB, once)
+    if (r) return r;
+    c->st.grows++;
+    HIPCHK(c, hipMemsetAsync(c->d_ctr + 6, 0, 2 * sizeof(unsigned long long), c->stream));  // keys at the coverage threshold: none yet; nothing handed on
+    return RUN_BATCH_AGAIN;
+}
+
+// What the run has timed goes into the statistics; finished: it counted the batch (else it ends early, and the caller goes on with it)
+static void book_run(mc_ctx *c, const PipeRun &R, bool finished)
+{
+    c->st.p1_ms += R.pl.ms1;
+    c->st.p2_ms += R.pl.ms2;
+    c->st.p3_ms += R.ms3;
+    c->st.count_ms += R.pl.ms1 + R.pl.ms2 + R.ms3 + R.ms4;
+    c->st.count_total_ms += R.pl.ms1 + R.pl.ms2 + R.ms3 + R.ms4;
+    if (!finished) return;
+    c->st.spill_keys += R.n_spill;
+    c->st.count_launches++;
+    c->st.windows += R.pl.wb;
+}
+
+// Nothing vouches for the table's size (no capacity hint): the second level, then the merge of 1024 leaves first -- the bin word is
+// a mixed hash, any range of leaves is a fair sample -- to see what they hold.  Costs a host round trip; a whole merge into a
+// table that turns out too small costs seven times the run.  Outcomes: RUN_LOST_RECORDS, RUN_BATCH_AGAIN (times booked).
+static int merge_sample(mc_ctx *c, PipeRun &R)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    const uint64_t K = 1024;
+    HIPCHK(c, hipEventRecord(c->ev_t[1], c->stream));
+    launch_level2(c, R.pl);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_t[2], c->stream));
+    launch_merge(c, R, (uint32_t)K, (int)K, 1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(R.flags, P.flags, sizeof R.flags, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float f = 0;
+    if (R.pl.p1_pending) { HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[0], c->ev_t[1])); R.pl.ms1 = f; R.pl.p1_pending = false; }
+    HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[1], c->ev_t[2]));
+    R.pl.ms2 += f;
+    R.pl.p2_done = true;
+    if (R.flags[0]) return RUN_LOST_RECORDS;  // (nothing was merged)
+    const int rc = resize_for_batch(c, R.pl, K);
+    if (rc == RUN_BATCH_AGAIN) book_run(c, R, false);  // (level 1 and level 2: the sample's merge is not timed)
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(P.flags + 1, 0, sizeof(uint32_t), c->stream));
+    return MC_OK;
+}
+
+// P2 (where the run has one and it has not run yet) and the first P3 back to back.  The capacities of the streams are estimates
+// (and a few heavy keys can fill a bucket's spill list alone): P3 looks at the "records lost" flag itself and merges nothing when
+// it is set, so that the caller can still count the batch another way.  Outcomes: RUN_LOST_RECORDS.
+static int scatter_and_merge(mc_ctx *c, PipeRun &R)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    const bool level2 = R.pl.b2 > 1 && !R.pl.p2_done;
+    HIPCHK(c, hipEventRecord(c->ev_t[1], c->stream));
+    if (level2) {
+        launch_level2(c, R.pl);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_t[2], c->stream));
-        launch_p3_n((uint32_t)K, (int)K, 1);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(flags, P.flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        float f = 0;
-        if (p1_pending) { HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[0], c->ev_t[1])); ms1 = f; p1_pending = false; }
-        HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[1], c->ev_t[2]));
-        ms2 += f;
-        p2_done = true;
-        if (flags[0]) return 1;  // (records lost: nothing was merged)
-        rc = resize_for_batch(K);
-        if (rc == 3) {
-            c->st.p1_ms += ms1;
-            c->st.p2_ms += ms2;
-            c->st.count_ms += ms1 + ms2;
-            c->st.count_total_ms += ms1 + ms2;
-        }
+    }
+    HIPCHK(c, hipEventRecord(c->ev_t[2], c->stream));
+    launch_merge_all(c, R);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_t[3], c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_scratch + 16, P.flags, 4 * sizeof(uint32_t) + sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_scratch + 19, c->d_ctr + 7, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(R.flags, c->h_scratch + 16, sizeof R.flags);
+    R.n_spill = c->h_scratch[18];
+    R.n_handed_on = c->h_scratch[19];
+    float f = 0;
+    if (R.pl.p1_pending) { HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[0], c->ev_t[1])); R.pl.ms1 = f; }
+    if (level2) { HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[1], c->ev_t[2])); R.pl.ms2 += f; }
+    if (R.flags[0]) return RUN_LOST_RECORDS;  // (nothing was merged)
+    HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[2], c->ev_t[3]));
+    R.ms3 += f;
+    c->virgin = false;
+    return MC_OK;
+}
+// Minimizer bins that no number of regions can hold: regions by the key's hash from here on, and the leaves that were not merged
+// go through the direct kernel, as many at a time as the table has room for.
+static int add_unmerged_leaves(mc_ctx *c, const PipeRun &R)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    const PipePlan &pl = R.pl;
+    const uint64_t n_leaves = pl.n_leaves;
+    const uint32_t lseg = R.lseg;
+    const int k = c->cfg.k;
+    int rc = to_hash_regions(c, 4);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(P.leaf_new, 0, n_leaves * sizeof(uint32_t), c->stream));  // (n_used was recounted)
+    std::vector<uint32_t> st(n_leaves), cnt(n_leaves * (uint64_t)lseg);
+    HIPCHK(c, hipMemcpy(st.data(), P.leaf_state, n_leaves * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(cnt.data(), R.lc, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint32_t lo_leaf = 0;
+    while (lo_leaf < n_leaves) {
+        uint64_t allowed, need = 0;
+        uint32_t hi_leaf = lo_leaf;
+        rc = table_reserve(c, 1ull << 26, &allowed);
         if (rc) return rc;
-        HIPCHK(c, hipMemsetAsync(P.flags + 1, 0, sizeof(uint32_t), c->stream));
-    }
-    {   // P2 and the first P3 back to back.  The capacities of the streams are estimates (and a few heavy keys can fill
-        // a bucket's spill list alone): P3 looks at the "records lost" flag itself and merges nothing when it is set, so
-        // that the caller can still count the batch another way.
-        HIPCHK(c, hipEventRecord(c->ev_t[1], c->stream));
-        if (pl.b2 > 1 && !p2_done) {
-            launch_p2();
-            HIPCHK(c, hipGetLastError());
+        while (hi_leaf < n_leaves) {
+            uint64_t w = 0;
+            if (!st[hi_leaf])
+                for (uint32_t sg = 0; sg < lseg; sg++) w += std::min<uint64_t>(cnt[(uint64_t)hi_leaf * lseg + sg], R.lcap) * (pl.lng ? SKL_MAX_WINDOWS : SK_MAX_WINDOWS);
+            if (hi_leaf > lo_leaf && need + w > allowed) break;
+            need += w;
+            hi_leaf++;
         }
-        HIPCHK(c, hipEventRecord(c->ev_t[2], c->stream));
-        launch_p3();
+        if (need > allowed) {  // a single leaf above what one launch may add: make room for it
+            rc = table_reserve(c, need, &allowed);
+            if (rc) return rc;
+            if (need > allowed) return fail(c, MC_EOVERFLOW, "internal: a leaf of %llu k-mer occurrences does not fit one launch", (unsigned long long)need);
+        }
+        if (need && pl.lng)
+            hipLaunchKernelGGL(k_skl_add_unmerged, dim3(std::min<uint32_t>(hi_leaf - lo_leaf, 4096u)), dim3(256), 0, c->stream,
+                               static_cast<const uint4 *>(R.lk), R.lc, R.lcap, lo_leaf, hi_leaf, P.leaf_state, k, c->view());
+        else if (need)
+            hipLaunchKernelGGL(k_sk_add_unmerged, dim3(std::min<uint32_t>(hi_leaf - lo_leaf, 4096u)), dim3(256), 0, c->stream,
+                               static_cast<const uint4 *>(R.lk), R.lh, R.lc, R.lcap, lseg, lo_leaf, hi_leaf, P.leaf_state, k, c->view());
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_t[3], c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_scratch + 16, P.flags, 4 * sizeof(uint32_t) + sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_scratch + 19, c->d_ctr + 7, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        memcpy(flags, c->h_scratch + 16, sizeof flags);
-        n_spill = c->h_scratch[18];
-        n_handed_on = c->h_scratch[19];
-        float f = 0;
-        if (p1_pending) { HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[0], c->ev_t[1])); ms1 = f; }
-        if (pl.b2 > 1 && !p2_done) { HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[1], c->ev_t[2])); ms2 += f; }
-        if (flags[0]) return 1;  // (nothing was merged)
-        HIPCHK(c, hipEventElapsedTime(&f, c->ev_t[2], c->ev_t[3]));
-        ms3 += f;
-        c->virgin = false;
+        lo_leaf = hi_leaf;
     }
-    if (flags[1] && virgin0 && !flags[0] && may_rerun) {  // (may_rerun: the caller can run the batch again -- returns 3)
-        // The table held nothing before this run and is too small for it (no capacity hint, or a poor one).  Rebuilding it
-        // by rehashing and merging the leaves that are left in two sweeps each costs 40 times the run (785 against 19 ms
-        // on configs[1]); what the merged leaves added says how many distinct keys the batch holds, so: a fresh table of
-        // the right size, and the caller runs the batch again.
-        rc = resize_for_batch(n_leaves);
-        if (rc != 3) return rc ? rc : fail(c, MC_EOVERFLOW, "internal: a leaf overflowed in a table that should hold the batch");
-        c->st.p1_ms += ms1;
-        c->st.p2_ms += ms2;
-        c->st.p3_ms += ms3;
-        c->st.count_ms += ms1 + ms2 + ms3;
-        c->st.count_total_ms += ms1 + ms2 + ms3;
-        return 3;
-    }
-    // P3 again, with a larger table, while a region overflows
+    return MC_OK;
+}
+
+// What the merge kernels handed on goes in, and while a region overflowed: a table of twice the regions and P3 again.
+static int merge_until_no_overflow(mc_ctx *c, PipeRun &R)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    PipePlan &pl = R.pl;
+    const uint64_t n_leaves = pl.n_leaves;
+    int rc;
     for (int attempt = 0;; attempt++) {
         if (attempt > 0) {
-            rc = timed(c, &ms3, [&] { launch_p3(); });
+            rc = timed(c, &R.ms3, [&] { launch_merge_all(c, R); });
             if (rc) return rc;
             c->virgin = false;
-            HIPCHK(c, hipMemcpy(flags, P.flags, sizeof flags, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(&n_handed_on, c->d_ctr + 7, sizeof n_handed_on, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(R.flags, P.flags, sizeof R.flags, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(&R.n_handed_on, c->d_ctr + 7, sizeof R.n_handed_on, hipMemcpyDeviceToHost));
         }
-        if (flags[0]) return fail(c, MC_EOVERFLOW, "internal: spill list of the partitioned counting pipeline overflowed");
+        if (R.flags[0]) return fail(c, MC_EOVERFLOW, "internal: spill list of the partitioned counting pipeline overflowed");
         // (every leaf has been merged or, where the hand-on list ran full, left as a valid region: the list can go in)
         const bool bins_before = hash_bins(c);
-        rc = pipe_drain_handed_on(c, n_handed_on, pl.lng);
+        rc = pipe_drain_handed_on(c, R.n_handed_on, pl.lng);
         if (rc) return rc;
-        n_handed_on = 0;
+        R.n_handed_on = 0;
         if (pl.lng && bins_before && !hash_bins(c))  // (the drain moved the table to hash-prefix regions: n_used was recounted, the merged leaves' keys included)
             HIPCHK(c, hipMemsetAsync(P.leaf_new, 0, n_leaves * sizeof(uint32_t), c->stream));
         if (!pl.lng && (n_leaves << pl.g) < c->n_regions) {  // (the drain doubled the table: a leaf covers more regions now; n_used was recounted)
             while ((n_leaves << pl.g) < c->n_regions) pl.g++;
             HIPCHK(c, hipMemsetAsync(P.leaf_new, 0, n_leaves * sizeof(uint32_t), c->stream));
         }
-        if (flags[2]) emit.recs = nullptr;  // a segment of the solid list overflowed: the BFS set-up sweeps the table instead
-        if (!flags[1]) break;
+        if (R.flags[2]) R.emit.recs = nullptr;  // a segment of the solid list overflowed: the BFS set-up sweeps the table instead
+        if (!R.flags[1]) return MC_OK;
         if (pl.lng || attempt >= 6 || pl.g >= 5) {
             // (long records: a table of hash keys in minimizer bins cannot be rebuilt with more bins -- it gives them up at the first leaf that fails)
             if (!(pl.sk && (c->mm_k || pl.lng)))
                 return fail(c, MC_EOVERFLOW, "k-mer table regions keep overflowing; pass a capacity_hint (distinct k-mers)");
-            // minimizer bins that no number of regions can hold: regions by the key's hash from here on, and the leaves
-            // that were not merged go through the direct kernel, as many at a time as the table has room for
-            rc = to_hash_regions(c, 4);
-            if (rc) return rc;
-            HIPCHK(c, hipMemsetAsync(P.leaf_new, 0, n_leaves * sizeof(uint32_t), c->stream));  // (n_used was recounted)
-            std::vector<uint32_t> st(n_leaves), cnt(n_leaves * (uint64_t)lseg);
-            HIPCHK(c, hipMemcpy(st.data(), P.leaf_state, n_leaves * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(cnt.data(), lc, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            uint32_t lo_leaf = 0;
-            while (lo_leaf < n_leaves) {
-                uint64_t allowed, need = 0;
-                uint32_t hi_leaf = lo_leaf;
-                rc = table_reserve(c, 1ull << 26, &allowed);
-                if (rc) return rc;
-                while (hi_leaf < n_leaves) {
-                    uint64_t w = 0;
-                    if (!st[hi_leaf])
-                        for (uint32_t sg = 0; sg < lseg; sg++) w += std::min<uint64_t>(cnt[(uint64_t)hi_leaf * lseg + sg], lcap) * (pl.lng ? SKL_MAX_WINDOWS : SK_MAX_WINDOWS);
-                    if (hi_leaf > lo_leaf && need + w > allowed) break;
-                    need += w;
-                    hi_leaf++;
-                }
-                if (need > allowed) {  // a single leaf above what one launch may add: make room for it
-                    rc = table_reserve(c, need, &allowed);
-                    if (rc) return rc;
-                    if (need > allowed) return fail(c, MC_EOVERFLOW, "internal: a leaf of %llu k-mer occurrences does not fit one launch", (unsigned long long)need);
-                }
-                if (need && pl.lng)
-                    hipLaunchKernelGGL(k_skl_add_unmerged, dim3(std::min<uint32_t>(hi_leaf - lo_leaf, 4096u)), dim3(256), 0, c->stream,
-                                       static_cast<const uint4 *>(lk), lc, lcap, lo_leaf, hi_leaf, P.leaf_state, k, c->view());
-                else if (need)
-                    hipLaunchKernelGGL(k_sk_add_unmerged, dim3(std::min<uint32_t>(hi_leaf - lo_leaf, 4096u)), dim3(256), 0, c->stream,
-                                       static_cast<const uint4 *>(lk), lh, lc, lcap, lseg, lo_leaf, hi_leaf, P.leaf_state, k, c->view());
-                HIPCHK(c, hipGetLastError());
-                lo_leaf = hi_leaf;
-            }
-            emit.recs = nullptr;
-            break;
+            R.emit.recs = nullptr;
+            return add_unmerged_leaves(c, R);
         }
         rc = table_grow(c, c->n_regions * 2);
         if (rc) return rc;
@@ -1714,59 +1800,110 @@ static int pipe_finish(mc_ctx *c, PipePlan &pl, double ms1, bool p2_done = false
         // the rebuild recounted n_used, keys of the leaves merged so far included
         HIPCHK(c, hipMemsetAsync(P.leaf_new, 0, n_leaves * sizeof(uint32_t), c->stream));
     }
-    hipLaunchKernelGGL(k_sum_leaf_new, dim3(64), dim3(256), 0, c->stream, P.leaf_new, (uint32_t)n_leaves, c->d_ctr);
+}
+
+// what did not fit its bucket goes through the direct kernel (n_spill: read with the flags, scatter_and_merge)
+static int drain_spill(mc_ctx *c, PipeRun &R)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    const PipePlan &pl = R.pl;
+    const unsigned long long n_spill = R.n_spill;
+    const int k = c->cfg.k;
+    const uint32_t thr = (uint32_t)(c->solid_tracked ? c->cov_hint : 0);
+    int rc;
+    uint64_t i = 0;
+    if (n_spill && pl.lng && hash_bins(c)) {
+        // (the table was sized by the hint that let this run take long records, and the direct path's usual preparations would
+        // move it out of its minimizer bins: the few records that found no room in the streams go in as they are, each to its bin)
+        rc = timed(c, &R.ms4, [&] {
+            hipLaunchKernelGGL(k_skl_add_records, dim3(grid_for(n_spill, 256)), dim3(256), 0, c->stream, P.spill_recs, (uint64_t)n_spill, k, c->view(), thr, c->d_ctr + 6,
+                               c->dup_l1_view());
+        });
+        if (rc) return rc;
+        i = n_spill;
+        unsigned long long parked = 0;  // what found no room in its bin's chain is a key without a leaf: only a by-key table takes it
+        HIPCHK(c, hipMemcpy(&parked, c->d_ctr + 7, sizeof parked, hipMemcpyDeviceToHost));
+        if (parked) { rc = drain_parked(c); if (rc) return rc; }
+    }
+    while (i < n_spill) {
+        uint64_t allowed;
+        rc = table_reserve(c, (n_spill - i) * (pl.lng ? SKL_MAX_WINDOWS : pl.sk ? SK_MAX_WINDOWS : 1), &allowed);
+        if (rc) return rc;
+        const uint64_t m = std::min<uint64_t>(pl.lng ? std::max<uint64_t>(allowed / SKL_MAX_WINDOWS, 1) : pl.sk ? std::max<uint64_t>(allowed / SK_MAX_WINDOWS, 1) : allowed, n_spill - i);
+        rc = timed(c, &R.ms4, [&] {
+            if (pl.lng)
+                hipLaunchKernelGGL(k_skl_add_records, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, P.spill_recs + 2 * i, m, k, c->view(), thr, c->d_ctr + 6,
+                                   DupL1{nullptr, nullptr, 0, 0, nullptr});  // (by key: the table is in hash-prefix regions by now)
+            else if (pl.sk)
+                hipLaunchKernelGGL(k_sk_add_records, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, P.spill_recs + i, (const uint32_t *)nullptr, m, k,
+                                   c->view(), thr, c->d_ctr + 6);
+            else
+                hipLaunchKernelGGL(k_add_keys_hint, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, P.spill_keys + i,
+                                   P.spill_hints + i, m, c->view(), thr, c->d_ctr + 6);
+        });
+        if (rc) return rc;
+        i += m;
+    }
+    return MC_OK;
+}
+
+// P2, P3 (with the retry after growing the table), spill drain and bookkeeping of a run that pipe_prepare planned and whose level 1
+// the caller has run or enqueued (PipePlan: ms1, p1_pending, p2_done, ms2, may_rerun).
+// Outcomes: RUN_LOST_RECORDS (the streams overflowed even their spill list); RUN_BATCH_AGAIN (pl.may_rerun only).
+static int pipe_finish(mc_ctx *c, PipePlan &pl)
+{
+    mc_ctx::Pipe &P = c->pipe;
+    const bool level2 = pl.b2 > 1;
+    PipeRun R{pl};
+    R.virgin0 = c->virgin;
+    R.emit = P3Emit{nullptr, nullptr, 0, P.flags + 2};
+    R.lk = pl.sk ? (level2 ? (const void *)P.b_recs : (const void *)P.a_recs) : (level2 ? (const void *)P.b_keys : (const void *)P.a_keys);
+    R.lh = pl.compact ? nullptr : (level2 ? P.b_hints : P.a_hints);
+    R.lc = level2 ? P.cursors2 : P.seg_counts1;
+    R.lcap = level2 ? pl.cap2 : pl.cap1;
+    R.lseg = level2 ? pl.pieces : pl.nseg1;
+    // The solid list (P3Emit): super-k-mer form with the leaves in b_recs, so that a_recs is free to take it, and a
+    // threshold to track.  Each P3 workgroup owns a segment.
+    R.p3_grid = (int)std::min<uint64_t>(pl.n_leaves, P3_MAX_GRID);
+    if (pl.sk && level2 && c->mm_k && c->solid_tracked && c->cov_hint > 0 && c->want_list) {
+        if (!P.emit_counts) HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&P.emit_counts), P3_MAX_GRID * sizeof(uint32_t)));
+        HIPCHK(c, hipMemsetAsync(P.emit_counts, 0, P3_MAX_GRID * sizeof(uint32_t), c->stream));
+        R.emit.recs = P.a_recs;
+        R.emit.counts = P.emit_counts;
+        R.emit.seg_cap = std::min<uint64_t>(P.a_recs_cap / (uint64_t)R.p3_grid, 0xFFFFFFF0ull);
+    }
+    // hash keys in minimizer bins: the merge kernel also leaves every key it writes back in the key streams of dup_check.h, sized
+    // by what is known about the number of keys the table will hold
+    if (pl.lng && hash_bins(c) && pl.g == 0)
+        dup_arm(c, c->cfg.capacity_hint ? (double)c->cfg.capacity_hint : c->dup.expected_keys, (uint32_t)R.p3_grid);
+    else
+        c->dup.l1_armed = false;
+    int rc = MC_OK;
+    if (pl.may_rerun && R.virgin0 && pl.guessed && pl.n_leaves >= 8192 && level2 && !R.pl.p2_done) rc = merge_sample(c, R);
+    if (!rc) rc = scatter_and_merge(c, R);
+    if (rc) return rc;
+    if (R.flags[1] && R.virgin0 && pl.may_rerun) {
+        // The table held nothing before this run and is too small for it (no capacity hint, or a poor one).  Rebuilding it
+        // by rehashing and merging the leaves that are left in two sweeps each costs 40 times the run (785 against 19 ms
+        // on configs[1]); what the merged leaves added says how many distinct keys the batch holds, so: a fresh table of
+        // the right size, and the caller runs the batch again.
+        rc = resize_for_batch(c, pl, pl.n_leaves);
+        if (rc != RUN_BATCH_AGAIN) return rc ? rc : fail(c, MC_EOVERFLOW, "internal: a leaf overflowed in a table that should hold the batch");
+        book_run(c, R, false);
+        return RUN_BATCH_AGAIN;
+    }
+    rc = merge_until_no_overflow(c, R);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sum_leaf_new, dim3(64), dim3(256), 0, c->stream, P.leaf_new, (uint32_t)pl.n_leaves, c->d_ctr);
     HIPCHK(c, hipGetLastError());
-    // what did not fit its bucket goes through the direct kernel (n_spill: read with the flags above)
-    double ms4 = 0;
-    if (n_spill) {
-        const uint32_t thr = (uint32_t)(c->solid_tracked ? c->cov_hint : 0);
-        uint64_t i = 0;
-        if (pl.lng && hash_bins(c)) {
-            // (the table was sized by the hint that let this run take long records, and the direct path's usual preparations would
-            // move it out of its minimizer bins: the few records that found no room in the streams go in as they are, each to its bin)
-            rc = timed(c, &ms4, [&] {
-                hipLaunchKernelGGL(k_skl_add_records, dim3(grid_for(n_spill, 256)), dim3(256), 0, c->stream, P.spill_recs, (uint64_t)n_spill, k, c->view(), thr, c->d_ctr + 6,
-                                   c->dup_l1_view());
-            });
-            if (rc) return rc;
-            i = n_spill;
-            unsigned long long parked = 0;  // what found no room in its bin's chain is a key without a leaf: only a by-key table takes it
-            HIPCHK(c, hipMemcpy(&parked, c->d_ctr + 7, sizeof parked, hipMemcpyDeviceToHost));
-            if (parked) { rc = drain_parked(c); if (rc) return rc; }
-        }
-        while (i < n_spill) {
-            uint64_t allowed;
-            rc = table_reserve(c, (n_spill - i) * (pl.lng ? SKL_MAX_WINDOWS : pl.sk ? SK_MAX_WINDOWS : 1), &allowed);
-            if (rc) return rc;
-            const uint64_t m = std::min<uint64_t>(pl.lng ? std::max<uint64_t>(allowed / SKL_MAX_WINDOWS, 1) : pl.sk ? std::max<uint64_t>(allowed / SK_MAX_WINDOWS, 1) : allowed, n_spill - i);
-            rc = timed(c, &ms4, [&] {
-                if (pl.lng)
-                    hipLaunchKernelGGL(k_skl_add_records, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, P.spill_recs + 2 * i, m, k, c->view(), thr, c->d_ctr + 6,
-                                       DupL1{nullptr, nullptr, 0, 0, nullptr});  // (by key: the table is in hash-prefix regions by now)
-                else if (pl.sk)
-                    hipLaunchKernelGGL(k_sk_add_records, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, P.spill_recs + i, (const uint32_t *)nullptr, m, k,
-                                       c->view(), thr, c->d_ctr + 6);
-                else
-                    hipLaunchKernelGGL(k_add_keys_hint, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, P.spill_keys + i,
-                                       P.spill_hints + i, m, c->view(), thr, c->d_ctr + 6);
-            });
-            if (rc) return rc;
-            i += m;
-        }
-    }
-    if (emit.recs && !n_spill) {  // (spilled records went into the table behind P3's back)
+    rc = drain_spill(c, R);
+    if (rc) return rc;
+    if (R.emit.recs && !R.n_spill) {  // (spilled records went into the table behind P3's back)
         c->solid_list_fresh = true;
-        c->solid_list_segs = (uint32_t)p3_grid;
-        c->solid_list_segcap = emit.seg_cap;
+        c->solid_list_segs = (uint32_t)R.p3_grid;
+        c->solid_list_segcap = R.emit.seg_cap;
     }
-    c->st.p1_ms += ms1;
-    c->st.p2_ms += ms2;
-    c->st.p3_ms += ms3;
-    c->st.spill_keys += n_spill;
-    c->st.count_ms += ms1 + ms2 + ms3 + ms4;
-    c->st.count_total_ms += ms1 + ms2 + ms3 + ms4;
-    c->st.count_launches++;
-    c->st.windows += pl.wb;
+    book_run(c, R, true);
     return MC_OK;
 }
 
@@ -1809,15 +1946,15 @@ static uint64_t sk_records_bound(const mc_ctx *c, uint64_t wb, uint64_t nr)
 }
 
 // One batch of reads [r0, r1) through the partitioned pipeline (count_pipeline.h).  wb = its windows,
-// base0 / end_abs = read_offsets[r0] / read_offsets[r1].
+// base0 / end_abs = read_offsets[r0] / read_offsets[r1].  Outcomes: RUN_BATCH_AGAIN, which add_reads_partitioned handles, and
+// RUN_RESPLIT (nothing of the batch was counted), which it passes on to the loops that cut the runs.
 static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t r0, uint64_t r1,
                                       uint64_t base0, uint64_t end_abs, uint64_t wb);
 static uint64_t max_run_bases(const mc_ctx *c, double windows_per_base);
-constexpr int RC_RESPLIT = 5;  // (internal) the run must be cut again: the table has left its minimizer bins under it and takes one record a window now
 static int add_reads_partitioned(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t r0, uint64_t r1,
                                  uint64_t base0, uint64_t end_abs, uint64_t wb)
 {
-    // 3 from the pipeline: the (empty) table was too small and has been replaced by one of the right size -- once more
+    // RUN_BATCH_AGAIN from the pipeline is handled here: once more, into the table that replaced the empty one
     unsigned long long empty0 = 0;  // occurrences of the key that looks like a free slot (hash keys only): counted apart, by P1
     const bool hashed = c->cfg.key_mode != MC_KEY_PACKED;
     if (hashed) {
@@ -1826,7 +1963,7 @@ static int add_reads_partitioned(mc_ctx *c, const uint64_t *d_words, const uint6
     }
     for (int run = 0;; run++) {
         const int rc = add_reads_partitioned_once(c, d_words, d_off, r0, r1, base0, end_abs, wb);
-        if (rc != 3) return rc;
+        if (rc != RUN_BATCH_AGAIN) return rc;  // (MC_OK, an error or RUN_RESPLIT)
         if (run >= 8) return fail(c, MC_EOVERFLOW, "k-mer table regions keep overflowing; pass a capacity_hint (distinct k-mers)");  // (a rerun multiplies the table by 4.5 at least)
         if (hashed) {
             HIPCHK(c, hipMemcpyAsync(c->d_ctr + 1, &empty0, sizeof empty0, hipMemcpyHostToDevice, c->stream));
@@ -1857,28 +1994,33 @@ static int count_batch_direct(mc_ctx *c, const uint64_t *d_words, const uint64_t
     return MC_OK;
 }
 
-// One run as long records (count_long.h).  4: the run does not qualify -- the caller moves the table to hash-prefix regions and
-// takes the per-window form; otherwise what pipe_finish returns.
+// One run as long records (count_long.h).  Outcomes: RUN_NOT_LONG (the run does not qualify: the caller moves the table to
+// hash-prefix regions and takes the per-window form), RUN_LOST_RECORDS (from pipe_finish, which may not ask for the batch again here).
 static int add_reads_long(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t r0, uint64_t r1, uint64_t base0, uint64_t end_abs,
                           uint64_t wb)
 {
     mc_ctx::Pipe &P = c->pipe;
     const uint64_t nr = r1 - r0;
-    if (c->cfg.key_mode != MC_KEY_POLY || c->cfg.k < SKL_MIN_K || c->cfg.k > SKL_MAX_K) return 4;
+    if (c->cfg.key_mode != MC_KEY_POLY || c->cfg.k < SKL_MIN_K || c->cfg.k > SKL_MAX_K) return RUN_NOT_LONG;
     unsigned long long used;
     uint32_t fatal;
     int rc = dup_unmerge(c);  // (slots that hold their keys' sums get their own counts back: the merge kernel adds to whichever slot a bin holds)
     if (!rc) rc = read_counters(c, &used, &fatal);
     if (rc) return rc;
     // (only a table sized for what it will hold -- by a hint that still holds, or, holding nothing yet, by a sample of this batch: it cannot grow)
-    if (fatal || !((c->cfg.capacity_hint && used < c->cfg.capacity_hint) || c->virgin)) return 4;
+    if (fatal || !((c->cfg.capacity_hint && used < c->cfg.capacity_hint) || c->virgin)) return RUN_NOT_LONG;
     PipePlan pl;
     // (bin words of the two smallest hashes: runs two thirds as long -- 10.6 windows a record for 15.9 on configs[2]'s reads)
     const uint64_t n_records = c->mm_k < 0 ? sk_records_bound(c, wb, nr) * 8 / 5 : sk_records_bound(c, wb, nr);
     const uint64_t n_tiles_abs = (end_abs + P1L_TILE - 1) / P1L_TILE;
-    rc = pipe_prepare(c, wb, &pl, n_records, (uint32_t)P1W_SEGMENTS, 1, false, n_tiles_abs - base0 / P1L_TILE, true);
+    PipeRequest rq;
+    rq.n_records = n_records;
+    rq.nseg1 = (uint32_t)P1W_SEGMENTS;
+    rq.compact_tiles = n_tiles_abs - base0 / P1L_TILE;
+    rq.lng = true;
+    rc = pipe_prepare(c, wb, &pl, rq);
     if (rc) return rc;
-    if (!pl.compact || !hash_bins(c)) return 4;
+    if (!pl.compact || !hash_bins(c)) return RUN_NOT_LONG;
     const uint64_t *offs = d_off + r0;
     rc = ensure_buf(c, &P.tile_first, &P.tiles1_cap, n_tiles_abs);
     if (rc) return rc;
@@ -1892,11 +2034,13 @@ static int add_reads_long(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_
     hipLaunchKernelGGL(k_skl_extract, dim3(P1W_SEGMENTS), dim3(P1W_THREADS), 0, c->stream, d_words, offs, nr, base0, end_abs, n_tiles_abs, P.tile_first,
                        c->cfg.k, pl.b1, P.seg_counts1, pl.cap1, P.a_recs, sp, pl.chunk_tiles, c->mm_k < 0 ? 1u : 0u);
     HIPCHK(c, hipGetLastError());
-    rc = pipe_resize_by_sample(c, pl, n_records);  // (no hint: the table is sized by what the first bucket holds; 4: its bins would be too full)
-    if (rc) return rc;
-    if (pl.guessed) return 4;  // (no sample could be taken: nothing vouches for the table)
+    rc = pipe_resize_by_sample(c, pl, n_records);  // (no hint: the table is sized by what the first bucket holds; RUN_NOT_LONG: its bins would be too full)
+    if (rc == RUN_BEYOND_LEAF_BITS) return fail(c, MC_EINVAL, "internal: long records have no leaf bits for a table to be beyond (PipePlan::vleaf)");
+    if (rc) return rc;  // (an error or RUN_NOT_LONG)
+    if (pl.guessed) return RUN_NOT_LONG;  // (no sample could be taken: nothing vouches for the table)
     c->st.long_runs++;
-    return pipe_finish(c, pl, 0, false, 0, true, false);
+    pl.p1_pending = true;
+    return pipe_finish(c, pl);  // (pl.may_rerun is not set: no RUN_BATCH_AGAIN)
 }
 
 static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t r0, uint64_t r1,
@@ -1907,13 +2051,13 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
     const uint64_t nr = r1 - r0;
     if (hash_bins(c)) {
         int lrc = add_reads_long(c, d_words, d_off, r0, r1, base0, end_abs, wb);
-        if (lrc == 1) return count_batch_direct(c, d_words, d_off, r0, r1, base0, end_abs, wb);  // (the streams lost records: nothing was merged)
-        if (lrc != 4) return lrc;
+        if (lrc == RUN_LOST_RECORDS) return count_batch_direct(c, d_words, d_off, r0, r1, base0, end_abs, wb);  // (nothing was merged)
+        if (lrc != RUN_NOT_LONG) return lrc;  // (MC_OK or an error)
         lrc = to_hash_regions(c, 3);
         if (lrc) return lrc;
         // The run was cut for long records (2^34 bases); one record a window takes far less (39 M reads of 150 bases
         // at k = 63 pass the 32-bit bucket indices).  The caller cuts what is left again, for the table as it is now.
-        if (end_abs - base0 > max_run_bases(c, (double)wb / (double)std::max<uint64_t>(end_abs - base0, 1))) return RC_RESPLIT;
+        if (end_abs - base0 > max_run_bases(c, (double)wb / (double)std::max<uint64_t>(end_abs - base0, 1))) return RUN_RESPLIT;
     }
     const uint64_t n_records = c->mm_k ? sk_records_bound(c, wb, nr) : 0;
     // One key per window (hash keys, short k): a large batch goes through the two scatter levels in pieces of ~2^30 windows
@@ -1922,10 +2066,14 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
     // (only where the memory is needed: at 0.9 G windows two pieces cost 55 ms against 35 ms in one)
     // (super-k-mer records go in one piece)
     constexpr uint32_t sk_tile = p1w_tile(false);  // k_sk1w_extract<false, ..>, both forms
-    int rc = pipe_prepare(c, wb, &pl, n_records, n_records ? (uint32_t)P1W_SEGMENTS : (uint32_t)PT_SEGMENTS,
-                          n_records || wb < (3ull << 29) ? 1u : (uint32_t)std::min<uint64_t>(8, (wb + (1ull << 30) - 1) >> 30), false,
-                          n_records ? (end_abs + sk_tile - 1) / sk_tile - base0 / sk_tile : 0);
+    PipeRequest rq;
+    rq.n_records = n_records;
+    rq.nseg1 = n_records ? (uint32_t)P1W_SEGMENTS : (uint32_t)PT_SEGMENTS;
+    rq.pieces = n_records || wb < (3ull << 29) ? 1u : (uint32_t)std::min<uint64_t>(8, (wb + (1ull << 30) - 1) >> 30);
+    rq.compact_tiles = n_records ? (end_abs + sk_tile - 1) / sk_tile - base0 / sk_tile : 0;
+    int rc = pipe_prepare(c, wb, &pl, rq);
     if (rc) return rc;
+    pl.may_rerun = true;
     const uint32_t pieces = pl.pieces;
     const uint64_t *offs = d_off + r0;
     // tiles are cut over the absolute base positions [0, end_abs); the ones before base0 hold no read of ours
@@ -1933,7 +2081,6 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
     const uint64_t n_tiles_abs = (end_abs + tile_size - 1) / tile_size;
     rc = ensure_buf(c, &P.tile_first, &P.tiles1_cap, n_tiles_abs);
     if (rc) return rc;
-    double ms1 = 0;
     if (pieces > 1) {
         const uint64_t t_first = base0 / tile_size, per = (n_tiles_abs - t_first + pieces - 1) / pieces;
         // (the two levels alternate on one stream; an event behind every kernel books each level's time where it belongs --
@@ -1955,15 +2102,14 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventSynchronize(c->ev_seq[2 * pieces - 1]));
-        double ms2 = 0;
         for (uint32_t pc = 0; pc < pieces; pc++) {
             float f1 = 0, f2 = 0;
             HIPCHK(c, hipEventElapsedTime(&f1, pc ? c->ev_seq[2 * pc - 1] : c->ev0, c->ev_seq[2 * pc]));
             HIPCHK(c, hipEventElapsedTime(&f2, c->ev_seq[2 * pc], c->ev_seq[2 * pc + 1]));
-            ms1 += f1;
-            ms2 += f2;
+            pl.ms1 += f1;
+            pl.ms2 += f2;
         }
-        rc = pipe_finish(c, pl, ms1, true, ms2, false, true);
+        pl.p2_done = true;
     } else {
         HIPCHK(c, hipEventRecord(c->ev_t[0], c->stream));  // (no wait here: pipe_finish enqueues P2 and P3 right behind)
         launch_tile_first(c, offs, nr, n_tiles_abs, P.tile_first, tile_size);
@@ -1983,8 +2129,8 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
             launch_p1_reads(c, d_words, offs, nr, base0, end_abs, n_tiles_abs, P.tile_first, pl.b1, P.seg_counts1, pl.cap1, P.a_keys,
                             P.a_hints, pl.sp, 0, nullptr);
         HIPCHK(c, hipGetLastError());
-        rc = pipe_resize_by_sample(c, pl, n_records);
-        if (rc == 5 && !c->no_vleaf) {  // (the batch wants a table beyond the reach of the records' leaf bits: once more, the two-array way)
+        rc = pipe_resize_by_sample(c, pl, n_records);  // (no long records here: no RUN_NOT_LONG)
+        if (rc == RUN_BEYOND_LEAF_BITS && !c->no_vleaf) {  // (the batch wants a table beyond the reach of the records' leaf bits: once more, the two-array way)
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (c->sw.ingest_debug) fprintf(stderr, "[count] the batch wants a table beyond the reach of its records' ten leaf bits: the first level again, two arrays\n");
             c->no_vleaf = true;
@@ -1992,19 +2138,14 @@ static int add_reads_partitioned_once(mc_ctx *c, const uint64_t *d_words, const 
             c->no_vleaf = false;
             return rc;
         }
+        if (rc > 0) return fail(c, MC_EINVAL, "internal: the sample of the first bucket ended in '%s' where nothing asked for it", RUN_OUTCOME_NAMES[rc]);
         if (rc) return rc;
-        rc = pipe_finish(c, pl, ms1, false, 0, true, true);
+        pl.p1_pending = true;
     }
-    if (rc != 1) return rc;
+    rc = pipe_finish(c, pl);
+    if (rc != RUN_LOST_RECORDS) return rc;  // (MC_OK, an error or RUN_BATCH_AGAIN)
     // (super-k-mer streams overflowed: unusually short runs) count this batch with the direct kernel instead
     return count_batch_direct(c, d_words, d_off, r0, r1, base0, end_abs, wb);
-}
-
-
-static int add_reads_partitioned_any(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t r0, uint64_t r1, uint64_t base0,
-                                     uint64_t end_abs, uint64_t wb)
-{
-    return add_reads_partitioned(c, d_words, d_off, r0, r1, base0, end_abs, wb);
 }
 
 // A flat stream of keys (+ optional hints) through the partitioned pipeline: the keys a rank owns
@@ -2014,18 +2155,15 @@ static int add_keys_partitioned(mc_ctx *c, const uint64_t *d_keys, const uint32_
     mc_ctx::Pipe &P = c->pipe;
     PipePlan pl;
     int rc = by_key_ready(c);
-    if (!rc) rc = pipe_prepare(c, n, &pl);
+    if (!rc) rc = pipe_prepare(c, n, &pl, PipeRequest());
     if (rc) return rc;
-    double ms1 = 0;
-    rc = timed(c, &ms1, [&] {
-        const uint64_t n_tiles = (n + PT_TILE - 1) / PT_TILE;
-        (void)n_tiles;
+    rc = timed(c, &pl.ms1, [&] {
         hipLaunchKernelGGL(k_p1_keys_scatter, dim3(PT_SEGMENTS), dim3(PT_THREADS), 0, c->stream,
                            d_keys, d_hints, n, pl.b1, P.seg_counts1, pl.cap1, P.a_keys, P.a_hints, c->d_ctr + 1, pl.sp, c->mm_k);
     });
     if (rc) return rc;
-    rc = pipe_finish(c, pl, ms1);
-    if (rc != 1) return rc;
+    rc = pipe_finish(c, pl);
+    if (rc != RUN_LOST_RECORDS) return rc;  // (MC_OK or an error: pl.may_rerun is not set)
     // (the streams overflowed: a few keys make up most of the batch) the direct kernel instead
     c->solid_tracked = false;
     c->solid_list_fresh = false;
@@ -2072,24 +2210,25 @@ static int add_records_partitioned(mc_ctx *c, const uint4 *d_recs, const uint32_
     unsigned long long wb = 0;
     HIPCHK(c, hipMemcpy(&wb, sum, sizeof wb, hipMemcpyDeviceToHost));
     PipePlan pl;
-    int rc = pipe_prepare(c, wb, &pl, n);
+    PipeRequest rq;
+    rq.n_records = n;
+    int rc = pipe_prepare(c, wb, &pl, rq);
     if (rc) return rc;
-    double ms1 = 0;
-    rc = timed(c, &ms1, [&] {
+    rc = timed(c, &pl.ms1, [&] {
         hipLaunchKernelGGL(k_sk1_records, dim3(PT_SEGMENTS), dim3(PT_THREADS), 0, c->stream, d_recs, d_bins, n, pl.b1, P.seg_counts1,
                            pl.cap1, P.a_recs, P.a_hints, pl.sks);
     });
     if (rc) return rc;
-    rc = pipe_finish(c, pl, ms1);
-    if (rc != 1) return rc;
+    rc = pipe_finish(c, pl);
+    if (rc != RUN_LOST_RECORDS) return rc;  // (MC_OK or an error: pl.may_rerun is not set)
     return add_records_direct(c, d_recs, d_bins, n);  // (the buckets overflowed)
 }
 
 // Records that arrive in level-1 bucket order already (the binned exchange, include/mcgpu.h mc_add_superkmers_binned_dev): part p of
 // the buffer -- records part_off[p] .. part_off[p + 1] -- holds part_counts[p * fine + f] records of fine bucket f = mulhi32(bin word,
 // fine), f ascending.  Where this table's level-1 buckets are unions of fine buckets the run starts at the second level, every part
-// r = fine / np1 segments of every bucket; returns 2 where they are not (or the table has no second level, or the parts are too
-// many): the caller counts the records as a flat stream.
+// r = fine / np1 segments of every bucket.  Outcomes: RUN_NOT_BINNED where they are not (or the table has no second level, or the
+// parts are too many): the caller counts the records as a flat stream.
 static int add_records_binned(mc_ctx *c, const uint4 *d_recs, const uint32_t *d_ptrs, uint64_t n, uint64_t n_windows, uint32_t fine, uint32_t n_parts,
                               const uint64_t *part_off, const uint32_t *d_part_counts)
 {
@@ -2101,10 +2240,10 @@ static int add_records_binned(mc_ctx *c, const uint4 *d_recs, const uint32_t *d_
     }
     uint64_t n_leaves, np1;
     uint32_t g;
-    if (plan_levels(c, true, &n_leaves, &g, &np1)) return 2;
-    if (n_leaves / np1 <= 1 || fine % np1 || n >= (1ull << 31)) return 2;
+    if (plan_levels(c, true, &n_leaves, &g, &np1)) return RUN_NOT_BINNED;
+    if (n_leaves / np1 <= 1 || fine % np1 || n >= (1ull << 31)) return RUN_NOT_BINNED;
     const uint64_t r = fine / np1, nseg = (uint64_t)n_parts * r;
-    if (nseg > (uint64_t)P1W_SEGMENTS || nseg == 0) return 2;
+    if (nseg > (uint64_t)P1W_SEGMENTS || nseg == 0) return RUN_NOT_BINNED;
     int rc = ensure_buf(c, &P.seg_counts1, &P.segs1_cap, np1 * nseg);
     if (!rc) rc = ensure_buf(c, &P.skb_seg_start, &P.skb_seg_start_cap, np1 * nseg);
     if (!rc) rc = ensure_buf(c, &P.skb_small, &P.skb_small_cap, (uint64_t)P1W_SEGMENTS + 2 * PT_MAX_BUCKETS + 8);
@@ -2130,13 +2269,17 @@ static int add_records_binned(mc_ctx *c, const uint4 *d_recs, const uint32_t *d_
         c->solid_list_fresh = false;
     }
     PipePlan pl;
-    rc = pipe_prepare(c, n_windows, &pl, n, (uint32_t)nseg, 1, false, 0, false, true);
+    PipeRequest rq;
+    rq.n_records = n;
+    rq.nseg1 = (uint32_t)nseg;
+    rq.listed = true;
+    rc = pipe_prepare(c, n_windows, &pl, rq);
     if (rc) return rc;
     if (pl.np1 != np1 || pl.b2 <= 1) return fail(c, MC_EINVAL, "internal: the plan of a binned run changed under it");
     pl.in_recs = d_recs;
     pl.in_ptrs = d_ptrs;
-    rc = pipe_finish(c, pl, 0.0);
-    if (rc != 1) return rc;
+    rc = pipe_finish(c, pl);
+    if (rc != RUN_LOST_RECORDS) return rc;  // (MC_OK or an error: pl.may_rerun is not set)
     return add_records_direct(c, d_recs, d_ptrs, n);  // (the leaves' streams overflowed)
 }
 
@@ -2242,14 +2385,13 @@ static int add_reads_impl(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_
             if (r1 > n_reads) r1 = n_reads;
             const uint64_t wb = windows_of(r, r1);
             if (wb) {
-                int rc = add_reads_partitioned_any(c, d_words, d_off, r, r1, h_off[r], h_off[r1], wb);
-                if (rc == RC_RESPLIT) { max_bases = max_run_bases(c, 1.0); continue; }  // (nothing of [r, r1) was counted)
+                int rc = add_reads_partitioned(c, d_words, d_off, r, r1, h_off[r], h_off[r1], wb);
+                if (rc == RUN_RESPLIT) { max_bases = max_run_bases(c, 1.0); continue; }  // (nothing of [r, r1) was counted)
                 if (rc) return rc;
             }
             r = r1;
         }
         counts_changed(c);
-        c->solid_cov = -1; c->solid_external = false;
         return MC_OK;
     }
     uint64_t r = 0;
@@ -2275,7 +2417,6 @@ static int add_reads_impl(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_
         r = r1;
     }
     counts_changed(c);
-    c->solid_cov = -1; c->solid_external = false;
     return MC_OK;
 }
 
@@ -2669,7 +2810,7 @@ int mc_add_reads_packed(mc_ctx *c, const uint64_t *words, const uint64_t *off, u
 static int add_reads_dev_counted(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t n_reads, uint64_t n_bases, int64_t in_store);
 int add_reads_dev_locked(mc_ctx *c, const uint64_t *d_words, const uint64_t *d_off, uint64_t n_reads, uint64_t n_bases, int64_t in_store)
 {
-    const int rc = add_reads_dev_counted(c, d_words, d_off, n_reads, n_bases, in_store);
+    const int rc = abi_result(c, add_reads_dev_counted(c, d_words, d_off, n_reads, n_bases, in_store));  // (every caller is an entry point of the C ABI)
     if (c->rs_copy_pending) {  // the caller's buffer is his again when this returns, and later work on the stream may read the store
         c->rs_copy_pending = false;
         HIPCHK(c, hipStreamSynchronize(c->pipe_stream));
@@ -2702,11 +2843,10 @@ static int add_reads_dev_counted(mc_ctx *c, const uint64_t *d_words, const uint6
     const bool partition = c->sw.count_path == 2 || (c->sw.count_path == 0 && total >= (1ull << 22));
     const double wpb = last_off > first_off ? (double)total / (double)(last_off - first_off) : 1.0;  // windows per base
     if (partition && last_off - first_off < max_run_bases(c, wpb)) {  // one batch: no need for the offsets on the host
-        int rc = total ? add_reads_partitioned_any(c, d_words, d_off, 0, n_reads, first_off, last_off, total) : MC_OK;
-        if (rc != RC_RESPLIT) {  // (RC_RESPLIT: the long form declined and the batch is too large for one record a window: in runs, below)
+        int rc = total ? add_reads_partitioned(c, d_words, d_off, 0, n_reads, first_off, last_off, total) : MC_OK;
+        if (rc != RUN_RESPLIT) {  // (RUN_RESPLIT: the long form declined and the batch is too large for one record a window: in runs, below)
             if (rc) return rc;
             counts_changed(c);
-            c->solid_cov = -1; c->solid_external = false;
             return MC_OK;
         }
     }
@@ -2743,15 +2883,14 @@ static int add_reads_dev_counted(mc_ctx *c, const uint64_t *d_words, const uint6
             HIPCHK(c, hipMemcpyAsync(&wb, sum, sizeof wb, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (wb) {
-                int rc = add_reads_partitioned_any(c, d_words, d_off, r, r1, off_r, off_r1, wb);
-                if (rc == RC_RESPLIT) continue;  // (nothing of [r, r1) was counted; the next cut is made for the table as it is now)
+                int rc = add_reads_partitioned(c, d_words, d_off, r, r1, off_r, off_r1, wb);
+                if (rc == RUN_RESPLIT) continue;  // (nothing of [r, r1) was counted; the next cut is made for the table as it is now)
                 if (rc) return rc;
             }
             r = r1;
             off_r = off_r1;
         }
         counts_changed(c);
-        c->solid_cov = -1; c->solid_external = false;
         return MC_OK;
     }
     // the launch planner of the direct kernel needs the offsets on the host (8 bytes per read, once per call)
@@ -2786,7 +2925,7 @@ int mc_add_keys_dev(mc_ctx *c, const int64_t *d_keys, const uint32_t *d_hints, u
         for (uint64_t i = 0; i < n; i += max_batch) {
             const uint64_t m = std::min<uint64_t>(max_batch, n - i);
             int rc = add_keys_partitioned(c, reinterpret_cast<const uint64_t *>(d_keys) + i, d_hints ? d_hints + i : nullptr, m);
-            if (rc) return rc;
+            if (rc) return abi_result(c, rc);
         }
     } else {
         c->solid_tracked = false;
@@ -2814,7 +2953,6 @@ int mc_add_keys_dev(mc_ctx *c, const int64_t *d_keys, const uint32_t *d_hints, u
         }
     }
     counts_changed(c);
-    c->solid_cov = -1; c->solid_external = false;
     return MC_OK;
 }
 
@@ -2838,7 +2976,6 @@ int mc_add_pairs_dev(mc_ctx *c, const int64_t *d_keys, const int16_t *d_counts, 
         i += m;
     }
     counts_changed(c);
-    c->solid_cov = -1; c->solid_external = false;
     return MC_OK;
 }
 
@@ -3220,15 +3357,14 @@ int mc_add_superkmers_binned_dev(mc_ctx *c, const uint64_t *d_recs, const uint32
     if (n && c->mm_k) {
         c->ptr_tries = c->all_ptrs ? 1 : 16;  // (records of ranks that keep no read store carry no pointer)
         int rc = add_records_binned(c, reinterpret_cast<const uint4 *>(d_recs), d_ptrs, n, n_windows, n_fine, n_parts, part_offsets, d_part_counts);
-        if (rc != 2) {
-            if (rc) return rc;
+        if (rc != RUN_NOT_BINNED) {
+            if (rc) return abi_result(c, rc);
             c->st.binned_runs++;
             counts_changed(c);
-            c->solid_cov = -1; c->solid_external = false;
             return MC_OK;
         }
     }
-    return add_superkmers_locked(c, d_recs, d_ptrs, n);  // (this table's buckets are not unions of the fine ones: records are records in any order)
+    return abi_result(c, add_superkmers_locked(c, d_recs, d_ptrs, n));  // (this table's buckets are not unions of the fine ones: records are records in any order)
 }
 
 int mc_add_superkmers_dev(mc_ctx *c, const uint64_t *d_recs, const uint32_t *d_bins, uint64_t n)
@@ -3238,28 +3374,16 @@ int mc_add_superkmers_dev(mc_ctx *c, const uint64_t *d_recs, const uint32_t *d_b
     if (!c->sk_form) return fail(c, MC_ESTATE, "mc_add_superkmers_dev: this context does not count through super-k-mers");
     if ((!d_recs || !d_bins) && n) return fail(c, MC_EINVAL, "mc_add_superkmers_dev: null pointer");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    return add_superkmers_locked(c, d_recs, d_bins, n);
+    return abi_result(c, add_superkmers_locked(c, d_recs, d_bins, n));
 }
 
 static int add_superkmers_locked(mc_ctx *c, const uint64_t *d_recs, const uint32_t *d_bins, uint64_t n)
 {
     c->ptr_tries = c->all_ptrs ? 1 : 16;  // (records of ranks that keep no read store carry no pointer)
     if (!c->mm_k) {  // the context gave up minimizer bins (to_hash_regions): the records are expanded by the direct kernel
-        c->solid_tracked = false;
-        c->solid_list_fresh = false;
-        uint64_t i = 0;
-        while (i < n) {
-            uint64_t allowed;
-            int rc = table_reserve(c, (n - i) * SK_MAX_WINDOWS, &allowed);
-            if (rc) return rc;
-            const uint64_t m = std::min<uint64_t>(std::max<uint64_t>(allowed / SK_MAX_WINDOWS, 1), n - i);
-            hipLaunchKernelGGL(k_sk_add_records, dim3(grid_for(m, 256)), dim3(256), 0, c->stream, reinterpret_cast<const uint4 *>(d_recs) + i, d_bins + i, m,
-                               c->cfg.k, c->view(), 0u, c->d_ctr + 6);
-            HIPCHK(c, hipGetLastError());
-            i += m;
-        }
+        int rc = add_records_direct(c, reinterpret_cast<const uint4 *>(d_recs), d_bins, n);
+        if (rc) return rc;
         counts_changed(c);
-        c->solid_cov = -1; c->solid_external = false;
         return MC_OK;
     }
     const uint64_t max_batch = 1ull << 28;  // records per pipeline run (32-bit bucket indices)
@@ -3269,7 +3393,6 @@ static int add_superkmers_locked(mc_ctx *c, const uint64_t *d_recs, const uint32
         if (rc) return rc;
     }
     counts_changed(c);
-    c->solid_cov = -1; c->solid_external = false;
     return MC_OK;
 }
 
