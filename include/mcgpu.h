@@ -351,6 +351,30 @@ int mc_save_kmers(mc_ctx *ctx, const char *bin_path, const char *stat_path, int 
                   uint64_t *n_written);
 int mc_load_kmers(mc_ctx *ctx, const char *path, int freq_threshold, uint64_t *n_records, uint64_t *n_added);
 
+/* ... and the same on the device (csrc/kmers_bin.hip; src/io/IOUtils.java:39-65,94-126, src/io/KmersLoadWorker.java:9-23).
+ * mc_kmers_encode_dev: the records of printKmers in device memory.  Call after mc_finalize_counts (else MC_ESTATE).  A key of the table
+ * is what mc_export lists at min_cov 0; its value is its count saturated at 32767; d_hist (32768 bins, zeroed by the call; may be
+ * NULL) takes the histogram of ALL keys; a key with value > threshold becomes a record.  Records come in ascending order of their
+ * table slots, the key equal to the free-slot mark (hash modes; counted out of band) last: the bytes are a function of the table, two
+ * calls give the same ones.  *n_total = keys, *n_written = records.  d_bytes == NULL only counts (and fills d_hist).  d_bytes must be
+ * 16-byte aligned and hold 10 * n_written bytes: a smaller cap_bytes is MC_EINVAL (the message names both numbers, the counts are
+ * still returned) and nothing is stored.
+ * mc_kmers_decode_dev: KmersLoadWorker's filter on the device: of the n_records records at d_bytes (16-byte aligned) those with
+ * count > freq_threshold (a signed compare: count bytes 80 00 are -32768) go to d_keys (8-byte aligned) / d_counts (4-byte aligned),
+ * n_records entries each, in any order; *n_kept = how many.  The table is not touched: mc_add_pairs_dev takes the result.
+ * mc_save_kmers_gpu / mc_load_kmers_gpu: mc_save_kmers / mc_load_kmers with these kernels, their contract, files and messages.  The
+ * save sweeps the table once for the counts, then encodes chunks of whole table tiles -- at most MC_KMERS_CHUNK_RECORDS records, 2048 at
+ * least -- into two staging buffers in turn; each is copied into pinned memory and written by a writer thread while the next one is
+ * encoded, so the extra memory is two chunks on either side, whatever the table's size.  The file has the records in slot order.  The
+ * load checks the file's length first (nothing is added from a file that is no whole number of records), then a reader thread
+ * brings chunk i + 1 to the device while chunk i is decoded and added.  (environment: MC_KMERS_CHUNK_RECORDS, default 8 Mi, 64 at least.) */
+int mc_kmers_encode_dev(mc_ctx *ctx, int threshold, uint8_t *d_bytes, uint64_t cap_bytes, uint64_t *d_hist, uint64_t *n_total,
+                        uint64_t *n_written);
+int mc_kmers_decode_dev(mc_ctx *ctx, const uint8_t *d_bytes, uint64_t n_records, int freq_threshold, int64_t *d_keys, int16_t *d_counts,
+                        uint64_t *n_kept);
+int mc_save_kmers_gpu(mc_ctx *ctx, const char *bin_path, const char *stat_path, int threshold, uint64_t *n_total, uint64_t *n_written);
+int mc_load_kmers_gpu(mc_ctx *ctx, const char *path, int freq_threshold, uint64_t *n_records, uint64_t *n_added);
+
 /* ---- reads-classifier: per-read k-mer coverage of a second read set in this table (src/tools/ReadsClassifier.java:154-200,
  * src/algo/PairFinder.java:32-57, src/algo/ReadsFinderInGraph.java:37-161).
  * Reads come in the packed layout above, but whole: the caller turns N / n / . into base code 0 (A) -- what

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libmcgpu.so")
 CLI = os.path.join(LIBDIR, "metacherchant")
 
 # the library's units (csrc/context.h says what each holds), and the host reader the read-file entry point uses
-HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip", "trim_paths.hip",
+HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip", "trim_paths.hip", "kmers_bin.hip",
                os.path.join("host", "envfinder.cpp")]
 # every header under csrc/ makes every object stale (a stale library would travel to the GPU box unnoticed)
 HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "envfinder.h"), os.path.join("test", "bfs_old_race.h"),

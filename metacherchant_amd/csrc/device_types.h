@@ -43,6 +43,23 @@ struct DupSet {
     unsigned long long *n_keys;  // distinct keys in the set
 };
 
+// (device code of the units that sweep the table: mcgpu.hip through dup_check.h, kmers_bin.hip)
+__device__ __forceinline__ bool dup_set_find(const DupSet &q, uint64_t key, uint64_t *at)
+{
+    for (uint64_t s = fmix64(key) & q.mask;; s = (s + 1) & q.mask) {
+        const unsigned long long v = q.qk[s];
+        if (v == key) { *at = s; return true; }
+        if (v == ~0ull) return false;
+    }
+}
+// what a sweep that counts or lists KEYS (exports, "Hashtable size") asks about a slot: is it a listed key's second (third, ...) slot?
+__device__ __forceinline__ bool dup_is_shadow(const DupSet &q, uint64_t key, uint64_t slot)
+{
+    if (!q.qk) return false;
+    uint64_t s;
+    return dup_set_find(q, key, &s) && q.prim[s] != slot;
+}
+
 // every slot of a listed key: (slot index, its own count, the set entry) noted, count added to the entry's sum
 struct DupTwin { unsigned long long slot; uint32_t own, entry; };
 

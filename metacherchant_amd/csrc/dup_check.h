@@ -283,14 +283,7 @@ __global__ void __launch_bounds__(DUP_FIND_THREADS) k_dup_find(DupL2 in, DupOut 
     }
 }
 
-__device__ __forceinline__ bool dup_set_find(const DupSet &q, uint64_t key, uint64_t *at)
-{
-    for (uint64_t s = fmix64(key) & q.mask;; s = (s + 1) & q.mask) {
-        const unsigned long long v = q.qk[s];
-        if (v == key) { *at = s; return true; }
-        if (v == ~0ull) return false;
-    }
-}
+// (dup_set_find, the set's look-up, and dup_is_shadow, what an export asks about a slot, are in device_types.h: kmers_bin.hip sweeps the table too)
 __global__ void k_dupq_build(const unsigned long long *__restrict__ keys, uint64_t n, DupSet q)
 {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -326,14 +319,6 @@ __global__ void k_dup_apply(Slot *slots, const DupTwin *__restrict__ tw, uint64_
     const DupTwin t = tw[i];
     const unsigned long long sum = q.tot[t.entry];
     slots[t.slot].count = merged ? (uint32_t)(sum > (1ull << 30) ? (1ull << 30) : sum) : t.own;
-}
-
-// what a sweep that counts or lists KEYS (exports, "Hashtable size") asks about a slot: is it a listed key's second (third, ...) slot?
-__device__ __forceinline__ bool dup_is_shadow(const DupSet &q, uint64_t key, uint64_t slot)
-{
-    if (!q.qk) return false;
-    uint64_t s;
-    return dup_set_find(q, key, &s) && q.prim[s] != slot;
 }
 
 

@@ -111,6 +111,9 @@ struct Options {
     // --trim-on: who works out which k-mers --trim keeps (no counterpart in the reference; the files are the same)
     std::string trim_on = "auto";
     bool trim_on_given = false;
+    // --kmers-io: who encodes / decodes the records of a <name>.kmers.bin (no counterpart in the reference; the files are the same)
+    std::string kmers_io = "auto";
+    bool kmers_io_given = false;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -123,7 +126,7 @@ const OptSpec SPECS[] = {
     {"merge", nullptr, 1}, {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0},
     {"continue", "c", 1}, {"force", nullptr, 1}, {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0},
     {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"output-dir", nullptr, 0}, {"env", "e", 2}, {"geneid", "g", 0},
-    {"compact", nullptr, 0}, {"join", nullptr, 0}, {"parse", nullptr, 0}, {"trim-on", nullptr, 0},
+    {"compact", nullptr, 0}, {"join", nullptr, 0}, {"parse", nullptr, 0}, {"trim-on", nullptr, 0}, {"kmers-io", nullptr, 0},
 };
 
 // --tool reads-classifier: its parameters (ReadsClassifier.java:42-95) and the launch options
@@ -132,6 +135,7 @@ const OptSpec CLASSIFIER_SPECS[] = {
     {"hash", nullptr, 0}, {"interval95", nullptr, 1}, {"found-threshold", "found", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"parse", nullptr, 0},
+    {"kmers-io", nullptr, 0},
 };
 
 // --tool triple-reads-classifier: its parameters (TripleReadsClassifier.java:40-105) and the launch options
@@ -141,6 +145,7 @@ const OptSpec TRIPLE_SPECS[] = {
     {"half-threshold", "half", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"parse", nullptr, 0},
+    {"kmers-io", nullptr, 0},
 };
 
 // --tool seq-cov: its parameters (SequenceCoverage.java:30-72) and the launch options
@@ -311,6 +316,11 @@ Options parse_args(int argc, char **argv)
         o.trim_on = *v;
         o.trim_on_given = true;
     }
+    if (auto v = val("kmers-io")) {
+        if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--kmers-io takes host, gpu or auto, not '" + *v + "'");
+        o.kmers_io = *v;
+        o.kmers_io_given = true;
+    }
     if (auto v = val("seq")) o.seq = *v;
     if (auto v = val("hicseq")) o.hicseq = *v;
     if (auto v = val("output")) o.output = *v;
@@ -458,6 +468,10 @@ void usage()
     puts("                -r / --read-file / the read filter.  host: one thread reads the records and the tool packs them; gpu: the text of an");
     puts("                uncompressed FASTA / FASTQ file is tokenised on the device and stays there for the kernels; the files are the same;");
     puts("                default auto: gpu for an uncompressed file of 31.6 MB or more, the smallest size measured, where it already wins)");
+    puts("                --kmers-io host|gpu|auto (kmer-counter, reads-classifier, triple-reads-classifier: who turns the table into the records");
+    puts("                of <name>.kmers.bin and such a file's records into (key, count) pairs.  host: one thread, byte by byte; gpu: kernels on");
+    puts("                --device, the file streamed in chunks beside them (the records then come in the order of the table's slots); the files");
+    puts("                hold the same records; default auto: the GPU for a save of 10^7 keys or more and a load of 10^4 records or more, from where it was measured to win)");
 }
 
 #define MC_CHECK(ctx, call)                                                       \
@@ -584,6 +598,34 @@ struct Trimmer {
     }
 };
 
+// --kmers-io: the records of a <name>.kmers.bin by the host's loops (mc_save_kmers, mc_load_kmers) or by the kernels of csrc/kmers_bin.hip
+// with the file streamed in chunks beside them (mc_save_kmers_gpu, mc_load_kmers_gpu); `auto`, the default, takes the GPU from
+// KMERS_SAVE_AUTO_MIN keys in the table for a save, from KMERS_LOAD_AUTO_MIN records in the file for a load.
+// Each is the smallest size at which scripts/kmers_bin_bench.py (tables of 10^4 to 10^8 random keys, k = 31 and 63, medians of 5 runs, the
+// two ways in turn; profiles/kmers_bin_bench.txt) found the GPU way's median below the host way's FASTEST run, there and at
+// every larger size.  The save: the host's loop is the faster one up to 10^6 keys (0.32 ms against 1.22 ms at 10^4, 5.9 against 6.4 ms at
+// 10^6 of k = 31; at k = 63 the medians cross, 9.8 against 9.0 ms, but the host's fastest run, 6.2 ms, is below: no win) -- the GPU way
+// sets up two pinned and two device staging buffers, a stream and a thread a call -- and the slower one from 10^7 on: 76.3 ms (74.3 at
+// best) against 45.3 ms, and 833 (795) against 259 ms at 10^8, 798 (757) against 261 ms at k = 63.
+// The load: the GPU way wins at every measured size, 8.3 ms against 38.0 (36.7 at best) at 10^4 records, 19.5 against 63.6 (60.1) at
+// 10^7, 45 against 236 (222) at 10^8: the host loop sizes and zeroes its 80 MB and 64 + 16 MB vectors whatever the file's length.
+// Below the smallest measured size (10^4) nothing is measured and `auto` is the host.  File time is the storage's and common to both ways.
+constexpr uint64_t KMERS_SAVE_AUTO_MIN = 10000000, KMERS_LOAD_AUTO_MIN = 10000;
+bool kmers_on_gpu(const Options &o, uint64_t records, uint64_t auto_min)
+{
+    return o.kmers_io == "gpu" || (o.kmers_io == "auto" && records >= auto_min);
+}
+
+// IOUtils.loadKmers of one file (threshold 0) into the table
+void load_kmers_file(const Options &o, mc_ctx *ctx, const std::string &path)
+{
+    struct stat st;
+    const uint64_t records = stat(path.c_str(), &st) == 0 ? (uint64_t)st.st_size / 10 : 0;
+    const bool on_gpu = kmers_on_gpu(o, records, KMERS_LOAD_AUTO_MIN);
+    info("Loading " + std::to_string(records) + " k-mer records on the " + (on_gpu ? "GPU (mc_load_kmers_gpu)" : "host (mc_load_kmers)"));
+    MC_CHECK(ctx, on_gpu ? mc_load_kmers_gpu(ctx, path.c_str(), 0, nullptr, nullptr) : mc_load_kmers(ctx, path.c_str(), 0, nullptr, nullptr));
+}
+
 // the reads of all --reads files into the table; returns hm.size()
 uint64_t load_reads(const std::vector<std::string> &files, Engine &e)
 {
@@ -643,7 +685,9 @@ int run_kmer_counter(const Options &o)
     remove((out_dir + "/.keep").c_str());
     logline("DEBUG", "Starting to print k-mers to " + bin);
     uint64_t total = 0, good = 0;
-    MC_CHECK(ctx, mc_save_kmers(ctx, bin.c_str(), st.c_str(), 0, &total, &good));
+    const bool on_gpu = kmers_on_gpu(o, size, KMERS_SAVE_AUTO_MIN);
+    info("Writing " + std::to_string(size) + " k-mer records on the " + (on_gpu ? "GPU (mc_save_kmers_gpu)" : "host (mc_save_kmers)"));
+    MC_CHECK(ctx, on_gpu ? mc_save_kmers_gpu(ctx, bin.c_str(), st.c_str(), 0, &total, &good) : mc_save_kmers(ctx, bin.c_str(), st.c_str(), 0, &total, &good));
     char pct[32];
     if (size) snprintf(pct, sizeof pct, "%.1f", good * 100.0 / (double)size);
     else snprintf(pct, sizeof pct, "NaN");  // (Java's String.format of 0.0 / 0)
@@ -899,7 +943,7 @@ void load_graph(const Options &o, int k, const std::vector<std::string> &kmer_fi
     mc_ctx *ctx = E.c;
     uint64_t n_distinct = 0;
     if (kmers_bin) {  // IOUtils.loadKmers(files, 0, ...)
-        for (const std::string &path : kmer_files) MC_CHECK(ctx, mc_load_kmers(ctx, path.c_str(), 0, nullptr, nullptr));
+        for (const std::string &path : kmer_files) load_kmers_file(o, ctx, path);
         E.finalize(&n_distinct);
         info("Hashtable size: " + std::to_string(n_distinct) + " kmers");
     } else {
@@ -1986,6 +2030,8 @@ int run(const Options &o)
     if (o.trim && o.trim_on == "gpu" && !o.devices.empty())  // (a group has no single context to run mc_trim_paths on)
         throw Error("--trim-on gpu does not go with --devices: the trim of a group's walk runs on the host (--trim-on host or auto)");
     if (o.join_given && o.tool != "environment-finder-multi") throw Error("--join does not apply to --tool " + o.tool);
+    if (o.kmers_io_given && o.tool != "kmer-counter" && o.tool != "reads-classifier" && o.tool != "triple-reads-classifier")
+        throw Error("--kmers-io does not apply to --tool " + o.tool);
     if (o.parse_given && o.tool != "reads-classifier" && o.tool != "triple-reads-classifier" && o.tool != "seq-cov" && o.tool != "fmt-visualizer" &&
         o.tool != "environment-assembler-finder")
         throw Error("--parse does not apply to --tool " + o.tool);

@@ -37,6 +37,9 @@ struct mc_switches {
     // diagnostics
     bool ingest_debug = false;                // MC_INGEST_DEBUG=1: what the counting and reading paths decided, on stderr
     bool unitigs_stats = false;               // MC_UNITIGS_STATS=1: device time of every pass of mc_unitigs on stderr, a line a call
+    bool kmers_stats = false;                 // MC_KMERS_STATS=1: the stages of mc_save_kmers_gpu / mc_load_kmers_gpu on stderr, a line a call
+    // the table as a file
+    uint64_t kmers_chunk_records = 8ull << 20;  // MC_KMERS_CHUNK_RECORDS: records per staging chunk of mc_save_kmers_gpu / mc_load_kmers_gpu (64 at least)
     // mc_group
     bool group_gather_reads = true;           // MC_EXCHANGE_GATHER_READS=0: the other devices' records carry no pointers
     int group_transport = 0;                  // MC_GROUP_TRANSPORT=rccl|peer: 1 | 2; 0: as the config's flags say
@@ -70,6 +73,8 @@ inline mc_switches read_switches()
     s.bfs_stats = getenv("MC_BFS_STATS") != nullptr;
     s.ingest_debug = getenv("MC_INGEST_DEBUG") != nullptr;
     s.unitigs_stats = getenv("MC_UNITIGS_STATS") != nullptr;
+    s.kmers_stats = getenv("MC_KMERS_STATS") != nullptr;
+    s.kmers_chunk_records = std::max<uint64_t>(num("MC_KMERS_CHUNK_RECORDS", 8ull << 20), 64);
     s.group_gather_reads = !off("MC_EXCHANGE_GATHER_READS");
     if (const char *e = getenv("MC_GROUP_TRANSPORT")) s.group_transport = !strcmp(e, "rccl") ? 1 : !strcmp(e, "peer") ? 2 : 0;
     if (const char *e = getenv("MC_GROUP_BATCH_READS")) if (*e) s.group_batch_reads = std::max<uint64_t>(strtoull(e, nullptr, 10), 1024);

@@ -117,6 +117,7 @@ EXPORTS = [
     "mc_kmer_presence", "mc_kmer_presence_dev", "mc_reads_in_set", "mc_reads_in_set_dev",
     "mc_components", "mc_components_dev", "mc_components_free", "mc_unitigs", "mc_unitigs_dev", "mc_unitigs_free",
     "mc_env_join", "mc_env_join_dev", "mc_env_join_free", "mc_trim_paths", "mc_trim_paths_dev",
+    "mc_kmers_encode_dev", "mc_kmers_decode_dev", "mc_save_kmers_gpu", "mc_load_kmers_gpu",
     "mc_tokenize_whole", "mc_tokenize_whole_dev", "mc_whole_text_bytes", "mc_whole_reads_to_host", "mc_whole_reads_free", "mc_reads_append_dev",
 ]
 
@@ -163,6 +164,11 @@ def load():
     L.mc_finalize_counts.argtypes = [vp, u64p]
     L.mc_save_kmers.argtypes = [vp, C.c_char_p, C.c_char_p, i32, u64p, u64p]
     L.mc_load_kmers.argtypes = [vp, C.c_char_p, i32, u64p, u64p]
+    if hasattr(L, "mc_kmers_encode_dev"):  # (MC_LIB may name a library built before the .kmers.bin unit)
+        L.mc_kmers_encode_dev.argtypes = [vp, i32, vp, u64, vp, u64p, u64p]
+        L.mc_kmers_decode_dev.argtypes = [vp, vp, u64, i32, vp, vp, u64p]
+        L.mc_save_kmers_gpu.argtypes = [vp, C.c_char_p, C.c_char_p, i32, u64p, u64p]
+        L.mc_load_kmers_gpu.argtypes = [vp, C.c_char_p, i32, u64p, u64p]
     L.mc_get.argtypes = [vp, i64p, u64, i16p]
     L.mc_get_dev.argtypes = [vp, vp, u64, vp]
     L.mc_kmer_keys.argtypes = [vp, u64p, u64p, u64, i64p]
@@ -563,6 +569,35 @@ class Context:
         a, b = C.c_uint64(0), C.c_uint64(0)
         self._chk(self._L.mc_load_kmers(self._h, os.fsencode(path), freq_threshold, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def save_kmers_gpu(self, bin_path, stat_path=None, threshold=0):
+        """save_kmers with the records encoded on the device and streamed to the file in chunks; the same files but for the
+        records' order (ascending table slots), the same return value."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.mc_save_kmers_gpu(self._h, os.fsencode(bin_path), os.fsencode(stat_path) if stat_path else None,
+                                            threshold, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def load_kmers_gpu(self, path, freq_threshold=0):
+        """load_kmers with the records decoded on the device, chunk i + 1 read while chunk i is added; the same return value."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.mc_load_kmers_gpu(self._h, os.fsencode(path), freq_threshold, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def kmers_encode_dev(self, threshold, d_bytes, cap_bytes, d_hist=None):
+        """mc_kmers_encode_dev: the .kmers.bin records of the table (10 bytes each, ascending table slots) into d_bytes (uint8, 16-byte
+        aligned, cap_bytes long; None: count only), the frequency histogram of all keys into d_hist (32768 x int64; may be None).
+        Returns (keys in the table, records written) as save_kmers does; McError when 10 * records > cap_bytes."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.mc_kmers_encode_dev(self._h, int(threshold), _dptr(d_bytes), int(cap_bytes), _dptr(d_hist), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def kmers_decode_dev(self, d_bytes, n_records, freq_threshold, d_keys, d_counts):
+        """mc_kmers_decode_dev: of the n_records records at d_bytes (16-byte aligned) those with count > freq_threshold into d_keys
+        (int64) / d_counts (int16), n_records entries each, in any order; returns how many.  The table is not touched."""
+        n = C.c_uint64(0)
+        self._chk(self._L.mc_kmers_decode_dev(self._h, _dptr(d_bytes), int(n_records), int(freq_threshold), _dptr(d_keys), _dptr(d_counts), C.byref(n)))
+        return int(n.value)
 
     def superkmer_capacity(self, n_windows, n_reads):
         """Records to make room for when a batch of reads is split with extract_superkmers_dev; 0 when this
