@@ -707,6 +707,57 @@ void mc_whole_reads_free(mc_ctx *ctx, mc_whole_reads *r);
 int mc_reads_append_dev(mc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_offsets, uint64_t n_reads, uint64_t *d_dst_words,
                         uint64_t dst_bases, uint64_t *d_dst_offsets);
 
+/* ---- the classifiers' FASTQ records as text, rendered on the device (csrc/render_fastq.hip): the body of
+ * WritersUtils.writeDnaQsToFastqFile (itmo!/io/writers/FastqDedicatedWriter.java:39-60 with Illumina.getPhredChar), which
+ * ReadsClassifier.java:186-199 and TripleReadsClassifier.java:243-262 call once per output file.
+ * A record is "@<n>\n<bases>\n+\n<quals>\n": <n> in decimal, counting from 1 per file; a base is "AGCT"[code] (an N is base 0 and
+ * prints as A); a quality is phred + 64.  It has 2 len + digits(n) + 6 bytes.
+ * Input: n_sides (1 or 2) sides of n_reads reads each (mate 1, mate 2).  A side's words are packed as mc_classify_reads_dev takes them,
+ * phred holds a byte a base at the same base positions, offsets n_reads + 1 base positions (the first need not be 0: a slice of a
+ * mc_whole_reads result will do), stream a byte a read: the output stream of the read (below n_streams <= MC_RENDER_MAX_STREAMS), or
+ * MC_RENDER_SKIP for none.  Inside a stream the records come in item order, item = n_sides * read + side: read 0 side 0, read 0 side 1,
+ * read 1 side 0, ... -- so one stream may take records of both sides.  first_number (host memory, n_streams entries): the first record
+ * of stream t in this call is @first_number[t], the next one more, so a file continues over calls; MC_RENDER_UNNUMBERED makes the
+ * stream's records start at the '\n' behind the number (2 len + 5 bytes), for lists whose numbers the caller knows later.
+ * Output: d_text (16-byte aligned, `capacity` bytes) holds the streams one after another: stream t is out->bytes[t] bytes from
+ * out->start[t] on, a multiple of 16, and out->records[t] records.  Bytes between the streams and behind the last are not written.
+ * mc_render_fastq_bound(n_bases, n_items) is a capacity that always suffices (2 n_bases + 26 n_items + 256, rounded up to 16; host
+ * only); a smaller capacity than the call needs is MC_EOVERFLOW, decided before anything is written to d_text.  No byte at or behind
+ * `capacity` is written, whatever the inputs hold.  Two calls on the same input give the same bytes.
+ * Data errors are the reference's: the call returns MC_OK with out->error set, the text is then unspecified.  MC_RENDER_EMPTY: a
+ * selected read of length 0 ("Empty DnaQ!"); MC_RENDER_QUALITY: a phred above 62 (getPhredChar's "Invalid quality code byte"),
+ * out->error_value the byte.  error_side / error_read name the offending item with the lowest item index (and its first such base).
+ * Errors: MC_EINVAL for null pointers, n_sides not 1 or 2, n_streams 0 or above MC_RENDER_MAX_STREAMS, n_sides * n_reads >= 2^40,
+ * d_text not 16-byte aligned, and a stream byte that is neither below n_streams nor MC_RENDER_SKIP (found on the device: out->error is
+ * MC_RENDER_STREAM, error_side / error_read / error_value say where and what).  n_reads == 0 is MC_OK with no bytes.
+ * mc_render_fastq takes host pointers and gives the text in host memory, mc_render_fastq_dev device ones (first_number and out are
+ * host memory in both).  Any context will do: its table plays no part. */
+#define MC_RENDER_MAX_STREAMS 16
+#define MC_RENDER_SKIP 0xFF
+#define MC_RENDER_UNNUMBERED (~0ull)
+#define MC_RENDER_EMPTY 1
+#define MC_RENDER_QUALITY 2
+#define MC_RENDER_STREAM 3
+typedef struct {
+    const uint64_t *words;
+    const uint8_t *phred;
+    const uint64_t *offsets;
+    const uint8_t *stream;
+} mc_render_side;
+typedef struct {
+    uint64_t start[MC_RENDER_MAX_STREAMS], bytes[MC_RENDER_MAX_STREAMS], records[MC_RENDER_MAX_STREAMS];
+    int32_t error;        /* 0, or MC_RENDER_EMPTY / MC_RENDER_QUALITY / MC_RENDER_STREAM */
+    uint32_t error_side;
+    uint64_t error_read;
+    uint32_t error_value;
+    double device_ms;     /* from the first pass to the last on the context's stream (HIP events; the scans' totals are waited for in between) */
+} mc_render_result;
+int mc_render_fastq_dev(mc_ctx *ctx, const mc_render_side *sides, uint32_t n_sides, uint64_t n_reads, uint32_t n_streams,
+                        const uint64_t *first_number, uint8_t *d_text, uint64_t capacity, mc_render_result *out);
+int mc_render_fastq(mc_ctx *ctx, const mc_render_side *sides, uint32_t n_sides, uint64_t n_reads, uint32_t n_streams,
+                    const uint64_t *first_number, uint8_t *text, uint64_t capacity, mc_render_result *out);
+uint64_t mc_render_fastq_bound(uint64_t n_bases, uint64_t n_items);
+
 /* ---- measurement */
 typedef struct {
     uint64_t windows;       /* k-mer occurrences counted so far */

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libmcgpu.so")
 CLI = os.path.join(LIBDIR, "metacherchant")
 
 # the library's units (csrc/context.h says what each holds), and the host reader the read-file entry point uses
-HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip", "trim_paths.hip", "kmers_bin.hip",
+HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip", "trim_paths.hip", "kmers_bin.hip", "render_fastq.hip",
                os.path.join("host", "envfinder.cpp")]
 # every header under csrc/ makes every object stale (a stale library would travel to the GPU box unnoticed)
 HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "envfinder.h"), os.path.join("test", "bfs_old_race.h"),
@@ -101,7 +101,7 @@ def build_host(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     common = [os.path.join(hdir, "envfinder.cpp")]
     hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "gpu_compactor.h"), os.path.join(hdir, "gpu_joiner.h"), os.path.join(hdir, "whole_reads_source.h"),
-            os.path.join(ROOT, "include", "mcgpu.h")]
+            os.path.join(hdir, "fastq_out.h"), os.path.join(ROOT, "include", "mcgpu.h")]
     flags = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")]
     if force or _stale(HOSTTEST, common + hdrs + [os.path.join(hdir, "hosttest.cpp"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h")]):
         cmd = ["g++"] + flags + ["-o", HOSTTEST, os.path.join(hdir, "hosttest.cpp")] + common + ["-lz", "-ldl"]
@@ -188,7 +188,8 @@ def build_host_sanitized(kind, force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     out = os.path.join(LIBDIR, "mc_hosttest_" + kind)
     srcs = [os.path.join(hdir, "hosttest.cpp"), os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h"), os.path.join(ROOT, "include", "mcgpu.h")]
+    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "fastq_out.h"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h"),
+            os.path.join(ROOT, "include", "mcgpu.h")]
     san = {"asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "tsan": ["-fsanitize=thread"]}[kind]
     if force or _stale(out, srcs + hdrs):
         cmd = ["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")] + san + [

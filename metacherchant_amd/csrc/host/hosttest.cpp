@@ -22,6 +22,11 @@
 // read: "R <length>\t<bases, N as A>\t<phreds as chars from '!'>".  `mc_hosttest dnaq-range <file> <chunk>`: the same lines from the file
 // cut at record starts every <chunk> bytes, each piece read by DnaQReader over a range of memory.  An error ends both with status 1 after
 // the reads before it.
+// `mc_hosttest render-host <out_dir>`: what --render adds to the host's writers (csrc/host/fastq_out.h), on designed reads (read i has
+// i % 7 + 1 bases, base j the code (i + j) % 4 and the phred (3 i + 5 j) % 63).  <out_dir>/a.fastq: reads 0 .. 4 through FastqOut::put, 5 .. 9
+// as one block through put_rendered, 10 .. 11 through put again.  <out_dir>/b.fastq: reads 8 and 9 through put, then a SideList that took
+// read 0 as a read, 1 .. 4 as a block of bodies, 5 as a read, 6 .. 7 as bodies.  Prints "a <records> b <records>", then render_ranges of
+// two designed covers, a line "R a b seg0 seg1" a range, and "E <message>" for a cover that ends before the batch does.
 // `mc_hosttest placement <k>`: where the table puts a key (csrc/kmer_hash.h, the functions the kernels compile).  Reads hexadecimal
 // 64-bit words from stdin, one a line, and prints for each "fmix64 sk_order sk_bin sk_hmin_of_kmer": the hash of the word as a key, the
 // order and the bin of its low 32 bits, and the smallest order among the SK_M-mers of the word as a packed k-mer of k bases.
@@ -48,6 +53,7 @@
 #include "../kmer_hash.h"
 #include "../read_ptr.h"
 #include "envfinder.h"
+#include "fastq_out.h"
 
 using namespace mch;
 
@@ -228,6 +234,72 @@ int main(int argc, char **argv)
             }
             return 0;
         }
+        if (argc == 3 && std::string(argv[1]) == "render-host") {
+            auto read = [](size_t i, std::vector<uint8_t> &c, std::vector<uint8_t> &q) {
+                c.resize(i % 7 + 1);
+                q.resize(c.size());
+                for (size_t j = 0; j < c.size(); j++) { c[j] = (uint8_t)((i + j) % 4); q[j] = (uint8_t)((3 * i + 5 * j) % 63); }
+            };
+            // reads [a, b) as text: numbered from `first` on, or (first == 0) as unnumbered bodies with their lengths
+            auto text = [&](size_t a, size_t b, unsigned long long first, std::vector<uint64_t> *lens) {
+                std::string t;
+                std::vector<uint8_t> c, q;
+                for (size_t i = a; i < b; i++) {
+                    read(i, c, q);
+                    if (first) t += "@" + std::to_string(first + (i - a));
+                    t += '\n';
+                    for (uint8_t x : c) t += "AGCT"[x];
+                    t += "\n+\n";
+                    for (uint8_t x : q) t += (char)(x + 64);
+                    t += '\n';
+                    if (lens) lens->push_back(c.size());
+                }
+                return t;
+            };
+            const std::string dir = argv[2];
+            std::vector<uint8_t> c, q;
+            FastqOut a(dir + "/a.fastq"), b(dir + "/b.fastq");
+            for (size_t i = 0; i < 5; i++) { read(i, c, q); a.put(c.data(), q.data(), c.size()); }
+            const std::string block = text(5, 10, a.n + 1, nullptr);
+            a.put_rendered(reinterpret_cast<const uint8_t *>(block.data()), block.size(), 5);
+            a.put_rendered(nullptr, 0, 0);
+            for (size_t i = 10; i < 12; i++) { read(i, c, q); a.put(c.data(), q.data(), c.size()); }
+            SideList list;
+            auto bodies = [&](size_t from, size_t to) {
+                std::vector<uint64_t> lens;
+                const std::string t = text(from, to, 0, &lens);
+                list.put_bodies(reinterpret_cast<const uint8_t *>(t.data()), t.size(), lens.data(), lens.size());
+            };
+            read(0, c, q);
+            list.put(c.data(), q.data(), c.size());
+            bodies(1, 5);
+            read(5, c, q);
+            list.put(c.data(), q.data(), c.size());
+            bodies(6, 8);
+            bodies(8, 8);
+            for (size_t i = 8; i < 10; i++) { read(i, c, q); b.put(c.data(), q.data(), c.size()); }
+            list.append_to(b);
+            a.close();
+            b.close();
+            printf("a %llu b %llu\n", a.n, b.n);
+            typedef std::vector<std::pair<uint64_t, uint64_t>> Cover;
+            const Cover two[2] = {{{0, 5}, {5, 0}, {5, 7}, {12, 30}}, {{0, 3}, {3, 3}, {6, 20}, {26, 10}}}, one[1] = {{{0, 4}, {4, 4}, {8, 1}}};
+            for (const RenderRange &r : render_ranges(two, 2, 30)) printf("R %llu %llu %zu %zu\n", (unsigned long long)r.a, (unsigned long long)r.b, r.seg[0], r.seg[1]);
+            for (const RenderRange &r : render_ranges(one, 1, 9)) printf("R %llu %llu %zu 0\n", (unsigned long long)r.a, (unsigned long long)r.b, r.seg[0]);
+            printf("R none %zu\n", render_ranges(one, 1, 0).size());
+            try {
+                (void)render_ranges(one, 1, 10);
+            } catch (const Error &e) {
+                printf("E %s\n", e.what());
+            }
+            try {
+                std::vector<uint64_t> lens(1, 3);
+                list.put_bodies(reinterpret_cast<const uint8_t *>("x"), 1, lens.data(), 1);
+            } catch (const Error &e) {
+                printf("E %s\n", e.what());
+            }
+            return 0;
+        }
         if (argc == 3 && std::string(argv[1]) == "placement") {
             const int k = atoi(argv[2]);
             if (k < mc::SK_M || k > 32) throw Error("placement: k from 15 to 32");
@@ -324,7 +396,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> [poly] | pointers <pos>... | dedup-tags <records> | long-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> [poly] | pointers <pos>... | dedup-tags <records> | long-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | render-host <out_dir> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

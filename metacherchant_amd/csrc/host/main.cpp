@@ -27,6 +27,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "envfinder.h"
+#include "fastq_out.h"
 #include "gpu_compactor.h"
 #include "gpu_joiner.h"
 #include "mcgpu.h"
@@ -114,6 +115,9 @@ struct Options {
     // --kmers-io: who encodes / decodes the records of a <name>.kmers.bin (no counterpart in the reference; the files are the same)
     std::string kmers_io = "auto";
     bool kmers_io_given = false;
+    // --render: who turns the classifiers' reads into the text of their FASTQ files (no counterpart in the reference; the files are the same)
+    std::string render = "auto";
+    bool render_given = false;
 };
 
 struct OptSpec { const char *name; const char *shortopt; int kind; };  // kind: 0 value, 1 bool (optional arg), 2 multi
@@ -127,6 +131,7 @@ const OptSpec SPECS[] = {
     {"continue", "c", 1}, {"force", nullptr, 1}, {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0},
     {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"output-dir", nullptr, 0}, {"env", "e", 2}, {"geneid", "g", 0},
     {"compact", nullptr, 0}, {"join", nullptr, 0}, {"parse", nullptr, 0}, {"trim-on", nullptr, 0}, {"kmers-io", nullptr, 0},
+    {"render", nullptr, 0},
 };
 
 // --tool reads-classifier: its parameters (ReadsClassifier.java:42-95) and the launch options
@@ -135,7 +140,7 @@ const OptSpec CLASSIFIER_SPECS[] = {
     {"hash", nullptr, 0}, {"interval95", nullptr, 1}, {"found-threshold", "found", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"parse", nullptr, 0},
-    {"kmers-io", nullptr, 0},
+    {"kmers-io", nullptr, 0}, {"render", nullptr, 0},
 };
 
 // --tool triple-reads-classifier: its parameters (TripleReadsClassifier.java:40-105) and the launch options
@@ -145,7 +150,7 @@ const OptSpec TRIPLE_SPECS[] = {
     {"half-threshold", "half", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"parse", nullptr, 0},
-    {"kmers-io", nullptr, 0},
+    {"kmers-io", nullptr, 0}, {"render", nullptr, 0},
 };
 
 // --tool seq-cov: its parameters (SequenceCoverage.java:30-72) and the launch options
@@ -321,6 +326,11 @@ Options parse_args(int argc, char **argv)
         o.kmers_io = *v;
         o.kmers_io_given = true;
     }
+    if (auto v = val("render")) {
+        if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--render takes host, gpu or auto, not '" + *v + "'");
+        o.render = *v;
+        o.render_given = true;
+    }
     if (auto v = val("seq")) o.seq = *v;
     if (auto v = val("hicseq")) o.hicseq = *v;
     if (auto v = val("output")) o.output = *v;
@@ -468,6 +478,11 @@ void usage()
     puts("                -r / --read-file / the read filter.  host: one thread reads the records and the tool packs them; gpu: the text of an");
     puts("                uncompressed FASTA / FASTQ file is tokenised on the device and stays there for the kernels; the files are the same;");
     puts("                default auto: gpu for an uncompressed file of 31.6 MB or more, the smallest size measured, where it already wins)");
+    puts("                --render host|gpu|auto (reads-classifier, triple-reads-classifier: who turns the reads of the output files into FASTQ text.");
+    puts("                host: a record and a base at a time; gpu: mc_render_fastq renders every file's records of a batch in one call and each");
+    puts("                file takes them with one write; the files are the same; default auto: the GPU only for reads --parse gpu has already");
+    puts("                taken to the device, from the measured size on at which the whole tool wins: a first -r file of 31.6 MB for the triple");
+    puts("                classifier, of 3.16 GB for reads-classifier; the host otherwise)");
     puts("                --kmers-io host|gpu|auto (kmer-counter, reads-classifier, triple-reads-classifier: who turns the table into the records");
     puts("                of <name>.kmers.bin and such a file's records into (key, count) pairs.  host: one thread, byte by byte; gpu: kernels on");
     puts("                --device, the file streamed in chunks beside them (the records then come in the order of the table's slots); the files");
@@ -785,69 +800,45 @@ int run_multi(const Options &o)
 
 // WritersUtils.writeDnaQsToFastqFile (itmo!/io/writers/FastqDedicatedWriter.java:39-60): "@<n>" counting from 1 (DataCounter), the
 // bases with N printed as A (the DnaQ holds base 0 there), "+", the qualities as Illumina (phred + 64, Illumina.getPhredChar)
-// MC_INGEST_DEBUG=1: the time spent in FastqOut::put (rendering a record and its fwrite), summed over the writers, for the log line
-// "[ingest] FastqOut: ..." at the end of reads-classifier -- the share of the run that DESIGN.md 3.14 reports
-const bool g_time_writers = getenv("MC_INGEST_DEBUG") != nullptr;
-double g_fastq_out_s = 0;
-unsigned long long g_fastq_out_n = 0;
+// (FastqOut and SideList: fastq_out.h)
 
-struct FastqOut {
-    FILE *f = nullptr;
-    unsigned long long n = 0;
-    std::string path, rec;
-    explicit FastqOut(const std::string &p) : path(p)
-    {
-        f = fopen(p.c_str(), "wb");
-        if (!f) throw Error("Failed to write to file " + p);
-        setvbuf(f, nullptr, _IOFBF, 1 << 20);
-    }
-    ~FastqOut() { if (f) fclose(f); }
-    void close()
-    {
-        if (f && (fclose(f) != 0)) { f = nullptr; throw Error("Failed to write to file " + path); }
-        f = nullptr;
-    }
-    void put(const uint8_t *codes, const uint8_t *phred, size_t len)
-    {
-        if (len == 0) throw Error("Empty DnaQ!");
-        const auto t0 = g_time_writers ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-        rec = "@" + std::to_string(++n) + "\n";
-        const size_t at = rec.size();
-        rec.resize(at + 2 * len + 4);
-        char *b = &rec[at], *q = b + len + 3;
-        for (size_t i = 0; i < len; i++) {
-            b[i] = "AGCT"[codes[i] & 3];
-            if (phred[i] > 62) throw Error("Invalid quality code byte: " + std::to_string(phred[i]));
-            q[i] = (char)(phred[i] + 64);
-        }
-        b[len] = '\n'; b[len + 1] = '+'; b[len + 2] = '\n'; q[len] = '\n';
-        if (fwrite(rec.data(), 1, rec.size(), f) != rec.size()) throw Error("Failed to write to file " + path);
-        if (g_time_writers) { g_fastq_out_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); g_fastq_out_n++; }
-    }
-};
+void hip_check(hipError_t e, const char *what)
+{
+    if (e != hipSuccess) throw Error(std::string(what) + ": " + hipGetErrorString(e));
+}
 
-// records kept aside (bases and phreds, length first) and appended to a FastqOut later: the "second only" halves of the _s files
-struct SideList {
-    FILE *f = tmpfile();
-    SideList() { if (!f) throw Error("Failed to create a temporary file"); }
-    ~SideList() { if (f) fclose(f); }
-    void put(const uint8_t *codes, const uint8_t *phred, size_t len)
+// device memory of the tool's own, grown by doubling
+struct DevArray {
+    char *p = nullptr;
+    size_t cap = 0, size = 0;
+    DevArray() = default;
+    DevArray(const DevArray &) = delete;
+    DevArray &operator=(const DevArray &) = delete;
+    ~DevArray() { if (p) (void)hipFree(p); }
+    void reserve(size_t bytes)
     {
-        const uint64_t n = len;
-        if (fwrite(&n, 8, 1, f) != 1 || fwrite(codes, 1, len, f) != len || fwrite(phred, 1, len, f) != len) throw Error("Failed to write a temporary file");
+        if (bytes <= cap) return;
+        const size_t nc = std::max(bytes, 2 * cap);
+        char *q = nullptr;
+        hip_check(hipMalloc(reinterpret_cast<void **>(&q), nc), "hipMalloc");
+        if (size) hip_check(hipMemcpy(q, p, size, hipMemcpyDeviceToDevice), "hipMemcpy");
+        if (p) (void)hipFree(p);
+        p = q;
+        cap = nc;
     }
-    void append_to(FastqOut &out)
+    void put(size_t at, const void *h, size_t bytes)  // host bytes to [at, at + bytes)
     {
-        rewind(f);
-        std::vector<uint8_t> c, q;
-        uint64_t n = 0;
-        while (fread(&n, 8, 1, f) == 1) {
-            c.resize(n);
-            q.resize(n);
-            if (fread(c.data(), 1, n, f) != n || fread(q.data(), 1, n, f) != n) throw Error("Failed to read a temporary file");
-            out.put(c.data(), q.data(), n);
-        }
+        reserve(at + bytes);
+        if (bytes) hip_check(hipMemcpy(p + at, h, bytes, hipMemcpyHostToDevice), "hipMemcpy");
+        size = std::max(size, at + bytes);
     }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = size = 0;
+    }
+    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
 // --parse: who reads the whole reads of a -r file.  host: DnaQReader on one thread, then the tool packs the bases and looks for the
@@ -883,6 +874,153 @@ struct ReadsIn {
         else host.reset(new DnaQReader(path));
     }
     size_t read(DnaQBatch &b, size_t max_reads, uint64_t max_bases = ~0ull) { return gpu ? gpu->read(b, max_reads, max_bases) : host->read(b, max_reads); }
+};
+
+// --render: who turns the reads that go to the classifiers' FASTQ files into text.  host: FastqOut::put, a record and a base at a
+// time; gpu: mc_render_fastq* renders every output stream of a batch in one call, the text comes down into one staging buffer and
+// each file takes its stream with one fwrite; auto: gpu only for reads that are on the device already (--parse gpu took every -r file
+// there) and a first -r file of at least the size from which the whole tool was measured to be faster that way
+// (scripts/render_bench.py): the triple classifier at 10^5 records of 150 bases, the smallest size measured;
+// reads-classifier at 10^7 -- at 10^5 and 10^6 its two ways lie within each other's spread, and auto stays host.
+constexpr uint64_t RENDER_AUTO_MIN = 3160000000, RENDER_AUTO_MIN_TRIPLE = 31600000;
+
+bool render_on_gpu(const Options &o, bool reads_on_device, uint64_t auto_min)
+{
+    if (o.render == "gpu") return true;
+    if (o.render == "host" || !reads_on_device) return false;
+    struct stat st;
+    return stat(o.read_files[0].c_str(), &st) == 0 && (uint64_t)st.st_size >= auto_min;
+}
+
+// page-locked host memory that grows: where the rendered text comes down
+struct PinnedStage {
+    uint8_t *p = nullptr;
+    size_t cap = 0;
+    PinnedStage() = default;
+    PinnedStage(const PinnedStage &) = delete;
+    PinnedStage &operator=(const PinnedStage &) = delete;
+    ~PinnedStage() { if (p) (void)hipHostFree(p); }
+    void reserve(size_t bytes)
+    {
+        if (bytes <= cap) return;
+        const size_t nc = std::max(bytes, 2 * cap);
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        hip_check(hipHostMalloc(reinterpret_cast<void **>(&p), nc), "hipHostMalloc");
+        cap = nc;
+    }
+};
+
+// The output streams of a tool under --render gpu: stream t is a file (out[t]: its records are numbered from the file's count on) or
+// a list kept aside (tail[t]: unnumbered bodies, numbered when the list is appended).  A batch is rendered from its device view
+// (render_segments) or, for reads the host parsed, from the batch itself (render_batch); st[s][i] is the stream of read i of side s.
+struct Renderer {
+    mc_ctx *ctx = nullptr;
+    uint32_t n_streams = 0;
+    FastqOut *out[MC_RENDER_MAX_STREAMS] = {};
+    SideList *tail[MC_RENDER_MAX_STREAMS] = {};
+    std::vector<uint8_t> st[2];
+    DevArray text, d_stream[2];
+    PinnedStage stage;
+    std::vector<uint8_t> host_text;
+    unsigned long long records = 0, tail_records = 0, calls = 0;
+    double call_s = 0, copy_s = 0, device_ms = 0;  // MC_INGEST_DEBUG: in mc_render_fastq*, in the copies down, on the device
+
+    static double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+    void first_numbers(uint64_t *first) const
+    {
+        for (uint32_t t = 0; t < n_streams; t++) first[t] = out[t] ? out[t]->n + 1 : MC_RENDER_UNNUMBERED;
+    }
+    static void data_error(const mc_render_result &r)  // FastqOut::put's messages
+    {
+        if (r.error == MC_RENDER_EMPTY) throw Error("Empty DnaQ!");
+        if (r.error == MC_RENDER_QUALITY) throw Error("Invalid quality code byte: " + std::to_string(r.error_value));
+    }
+    // the streams of reads [a, b) of the batch, rendered into `bytes`, go to their files and lists
+    void deliver(const uint8_t *bytes, const mc_render_result &r, int n_sides, const DnaQBatch *const *b, uint64_t a, uint64_t e)
+    {
+        std::vector<uint64_t> lens;
+        for (uint32_t t = 0; t < n_streams; t++) {
+            records += r.records[t];
+            if (out[t]) {
+                out[t]->put_rendered(bytes + r.start[t], r.bytes[t], r.records[t]);
+            } else if (r.records[t]) {
+                lens.clear();
+                for (uint64_t i = a; i < e; i++)
+                    for (int s = 0; s < n_sides; s++)
+                        if (st[s][i] == t) lens.push_back(b[s]->offsets[i + 1] - b[s]->offsets[i]);
+                tail[t]->put_bodies(bytes + r.start[t], r.bytes[t], lens.data(), lens.size());
+                tail_records += r.records[t];
+            }
+        }
+        calls++;
+    }
+    // the first n reads of a batch from its device view: a call per sub-range of reads that lie in one segment on every side
+    void render_segments(int n_sides, const std::vector<WholeSegment> *const *segs, const DnaQBatch *const *b, uint64_t n)
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> cover[2];
+        for (int s = 0; s < n_sides; s++) {
+            for (const WholeSegment &g : *segs[s]) cover[s].emplace_back(g.first, g.n_reads);
+            d_stream[s].put(0, st[s].data(), n);
+        }
+        for (const RenderRange &r : render_ranges(cover, n_sides, n)) {
+            mc_render_side sides[2] = {};
+            uint64_t bases = 0;
+            for (int s = 0; s < n_sides; s++) {
+                const WholeSegment &g = (*segs[s])[r.seg[s]];
+                // (a view without bases may come without phreds: no base, no phred is read)
+                sides[s] = mc_render_side{g.d_words, g.d_phred ? g.d_phred : reinterpret_cast<const uint8_t *>(g.d_words), g.d_offsets + (r.a - g.first),
+                                          d_stream[s].as<uint8_t>() + r.a};
+                bases += b[s]->offsets[r.b] - b[s]->offsets[r.a];
+            }
+            text.reserve(mc_render_fastq_bound(bases, (uint64_t)n_sides * (r.b - r.a)));
+            uint64_t first[MC_RENDER_MAX_STREAMS];
+            first_numbers(first);
+            mc_render_result res;
+            auto t0 = std::chrono::steady_clock::now();
+            MC_CHECK(ctx, mc_render_fastq_dev(ctx, sides, (uint32_t)n_sides, r.b - r.a, n_streams, first, text.as<uint8_t>(), text.cap, &res));
+            call_s += since(t0);
+            device_ms += res.device_ms;
+            data_error(res);
+            const uint64_t end = res.start[n_streams - 1] + res.bytes[n_streams - 1];
+            stage.reserve(end);
+            t0 = std::chrono::steady_clock::now();
+            if (end) hip_check(hipMemcpy(stage.p, text.p, end, hipMemcpyDeviceToHost), "hipMemcpy");
+            copy_s += since(t0);
+            deliver(stage.p, res, n_sides, b, r.a, r.b);
+        }
+    }
+    // ... and of reads the host parsed: packed as classify_batch packs them, one call
+    void render_batch(int n_sides, const DnaQBatch *const *b, uint64_t n)
+    {
+        static const uint8_t none = 0;
+        std::vector<uint64_t> words[2];
+        mc_render_side sides[2] = {};
+        uint64_t bases = 0;
+        for (int s = 0; s < n_sides; s++) {
+            pack_whole_reads(*b[s], 0, n, words[s], nullptr);
+            sides[s] = mc_render_side{words[s].data(), b[s]->phred.empty() ? &none : b[s]->phred.data(), b[s]->offsets.data(), st[s].empty() ? &none : st[s].data()};
+            bases += b[s]->offsets[n];
+        }
+        host_text.resize(mc_render_fastq_bound(bases, (uint64_t)n_sides * n));
+        uint64_t first[MC_RENDER_MAX_STREAMS];
+        first_numbers(first);
+        mc_render_result res;
+        const auto t0 = std::chrono::steady_clock::now();
+        MC_CHECK(ctx, mc_render_fastq(ctx, sides, (uint32_t)n_sides, n, n_streams, first, host_text.data(), host_text.size(), &res));
+        call_s += since(t0);
+        device_ms += res.device_ms;
+        data_error(res);
+        deliver(host_text.data(), res, n_sides, b, 0, n);
+    }
+    // the debug line's numbers: `written` the records of all files when they are complete
+    void report(unsigned long long written) const
+    {
+        fprintf(stderr, "[ingest] render: %llu records in %llu call(s) on the device, %llu through the host\n", records, calls,
+                written - (records - tail_records));
+        if (calls) fprintf(stderr, "[ingest] render stage: %.3f s in the calls (%.3f ms on the device), %.3f s in the copies down\n", call_s, device_ms, copy_s);
+    }
 };
 
 // findReadWithCorrection's one low-quality position of each of the first n reads: -1 for none, -2 for several (mc_classify_reads)
@@ -978,6 +1116,19 @@ int run_reads_classifier(const Options &o)
     FastqOut found1(out_dir + "/found_1.fastq"), found2(out_dir + "/found_2.fastq"), nf1(out_dir + "/not_found_1.fastq"),
         nf2(out_dir + "/not_found_2.fastq"), found_s(out_dir + "/found_s.fastq"), nf_s(out_dir + "/not_found_s.fastq");
     SideList found_s_tail, nf_s_tail;
+    // (the reads are on the device when --parse gpu took every file there)
+    const bool on_device = r1.gpu && (!paired || r2->gpu);
+    std::unique_ptr<Renderer> R;
+    if (render_on_gpu(o, on_device, RENDER_AUTO_MIN)) {
+        R.reset(new Renderer);
+        R->ctx = ctx;
+        R->n_streams = 8;
+        FastqOut *files[6] = {&found1, &found2, &nf1, &nf2, &found_s, &nf_s};
+        for (int t = 0; t < 6; t++) R->out[t] = files[t];
+        R->tail[6] = &found_s_tail;
+        R->tail[7] = &nf_s_tail;
+        hip_check(hipSetDevice(o.device), "hipSetDevice");
+    }
     long long both = 0, first_only = 0, second_only = 0, neither = 0;
     constexpr size_t BATCH = 1u << 20;
     DnaQBatch b1, b2;
@@ -989,6 +1140,29 @@ int run_reads_classifier(const Options &o)
         if (n == 0) break;
         const std::vector<mc_read_cov> c1 = classify_side(ctx, r1, b1, n, o);
         const std::vector<mc_read_cov> c2 = paired ? classify_side(ctx, *r2, b2, n, o) : std::vector<mc_read_cov>(n);
+        if (R) {  // --render gpu: the host still decides every read's stream (and counts); the records are rendered on the device
+            enum { FOUND_1, FOUND_2, NF_1, NF_2, FOUND_S, NF_S, FOUND_S_TAIL, NF_S_TAIL };
+            R->st[0].assign(n, MC_RENDER_SKIP);
+            if (paired) R->st[1].assign(n, MC_RENDER_SKIP);
+            for (size_t i = 0; i < n; i++) {
+                const size_t l1 = b1.offsets[i + 1] - b1.offsets[i], l2 = paired ? b2.offsets[i + 1] - b2.offsets[i] : 0;
+                const bool f1 = c1[i].found != 0;
+                const bool f2 = l2 == 0 ? !f1 : c2[i].found != 0;  // (a single-end read is paired with an empty one)
+                uint8_t t1 = MC_RENDER_SKIP, t2 = MC_RENDER_SKIP;
+                if (f1 && f2) { both++; t1 = FOUND_1; t2 = FOUND_2; }
+                else if (f1) { first_only++; if (l1) t1 = FOUND_S; if (l2) t2 = NF_S; }
+                else if (f2) { second_only++; if (l2) t2 = FOUND_S_TAIL; if (l1) t1 = NF_S_TAIL; }
+                else { neither++; t1 = NF_1; t2 = NF_2; }
+                R->st[0][i] = t1;
+                if (paired) R->st[1][i] = t2;
+            }
+            const DnaQBatch *bs[2] = {&b1, &b2};
+            const std::vector<WholeSegment> *segs[2] = {r1.gpu ? &r1.gpu->segments() : nullptr, paired && r2->gpu ? &r2->gpu->segments() : nullptr};
+            if (on_device) R->render_segments(paired ? 2 : 1, segs, bs, n);
+            else R->render_batch(paired ? 2 : 1, bs, n);
+            if (paired && n < BATCH) break;  // (one of the files is done)
+            continue;
+        }
         for (size_t i = 0; i < n; i++) {
             const uint8_t *s1 = b1.codes.data() + b1.offsets[i], *q1 = b1.phred.data() + b1.offsets[i];
             const size_t l1 = b1.offsets[i + 1] - b1.offsets[i];
@@ -1034,7 +1208,11 @@ int run_reads_classifier(const Options &o)
     nf_s_tail.append_to(nf_s);
     for (FastqOut *f : {&found1, &found2, &nf1, &nf2, &found_s, &nf_s}) f->close();
     info("Reads have been written. Finishing...");
-    if (g_time_writers) fprintf(stderr, "[ingest] FastqOut: %.3f s in put() for %llu records\n", g_fastq_out_s, g_fastq_out_n);
+    if (g_time_writers) {
+        fprintf(stderr, "[ingest] FastqOut: %.3f s in put() for %llu records\n", g_fastq_out_s, g_fastq_out_n);
+        const Renderer none;
+        (R ? R.get() : &none)->report(found1.n + found2.n + nf1.n + nf2.n + found_s.n + nf_s.n);
+    }
     write_file(o.work_dir + "/SUCCESS", "");
     return 0;
 }
@@ -1044,45 +1222,6 @@ int run_reads_classifier(const Options &o)
 // Both sides' reads stay on the device for both passes.  A read's pass-1 class is that of the last read of its side with the same bases
 // (the reference's maps keyed by bases: mc_reads_last_copy).  The reference runs pairs on a thread pool, so its lists' order and its
 // maps' last writer are only defined at -p 1; here they are that: input order in every file, "last" = the greatest input index.
-
-void hip_check(hipError_t e, const char *what)
-{
-    if (e != hipSuccess) throw Error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// device memory of the tool's own, grown by doubling
-struct DevArray {
-    char *p = nullptr;
-    size_t cap = 0, size = 0;
-    DevArray() = default;
-    DevArray(const DevArray &) = delete;
-    DevArray &operator=(const DevArray &) = delete;
-    ~DevArray() { if (p) (void)hipFree(p); }
-    void reserve(size_t bytes)
-    {
-        if (bytes <= cap) return;
-        const size_t nc = std::max(bytes, 2 * cap);
-        char *q = nullptr;
-        hip_check(hipMalloc(reinterpret_cast<void **>(&q), nc), "hipMalloc");
-        if (size) hip_check(hipMemcpy(q, p, size, hipMemcpyDeviceToDevice), "hipMemcpy");
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = nc;
-    }
-    void put(size_t at, const void *h, size_t bytes)  // host bytes to [at, at + bytes)
-    {
-        reserve(at + bytes);
-        if (bytes) hip_check(hipMemcpy(p + at, h, bytes, hipMemcpyHostToDevice), "hipMemcpy");
-        size = std::max(size, at + bytes);
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = size = 0;
-    }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
 
 std::vector<mc_read_cov> classify_segments(mc_ctx *ctx, const std::vector<WholeSegment> &segs, size_t n, const Options &o)
 {
@@ -1162,10 +1301,10 @@ struct SideStore {
 
 // the pairs of two DnaQ readers, batch by batch: PairSource (itmo!/io/sources/PairSource.java:35-45) ends them with the shorter file
 template <typename F>
-void for_each_pair_batch(const Options &o, F &&f)
+void for_each_pair_batch(const Options &o, F &&f, bool need_ctx = false)
 {
-    Engine T;  // (--parse gpu: any context tokenises; the graphs are not loaded yet)
-    if (parse_on_gpu(o, o.read_files[0]) || parse_on_gpu(o, o.read_files[1])) {
+    Engine T;  // (--parse gpu: any context tokenises, and --render gpu: any context renders; the graphs are not loaded yet)
+    if (need_ctx || parse_on_gpu(o, o.read_files[0]) || parse_on_gpu(o, o.read_files[1])) {
         mc_config cfg{};
         cfg.k = o.k;
         cfg.device = o.device;
@@ -1291,10 +1430,38 @@ int run_triple_reads_classifier(const Options &o)
         found_s(out_dir + "/found_s.fastq"), half_s(out_dir + "/half_found_s.fastq"), nf_s(out_dir + "/not_found_s.fastq");
     FastqOut *pair_out[3][2] = {{&nf1, &nf2}, {&half1, &half2}, {&found1, &found2}}, *single_out[3] = {&nf_s, &half_s, &found_s};
     uint64_t at = 0;
-    for_each_pair_batch(o, [&](const DnaQBatch &b1, const DnaQBatch &b2, size_t m, const ReadsIn &, const ReadsIn &) {
+    // (the reads are on the device when --parse gpu takes both files there)
+    const bool render_gpu = render_on_gpu(o, parse_on_gpu(o, o.read_files[0]) && parse_on_gpu(o, o.read_files[1]), RENDER_AUTO_MIN_TRIPLE);
+    Renderer R;
+    R.n_streams = 9;  // stream 2 * class + side: the pair files; 6 + class: the _s files, which take both sides in item order
+    for (int c = 0; c < 3; c++) {
+        R.out[2 * c] = pair_out[c][0];
+        R.out[2 * c + 1] = pair_out[c][1];
+        R.out[6 + c] = single_out[c];
+    }
+    for_each_pair_batch(o, [&](const DnaQBatch &b1, const DnaQBatch &b2, size_t m, const ReadsIn &r1, const ReadsIn &r2) {
         if (at + m > n) throw Error("The read files changed while they were being classified");
+        const DnaQBatch *b[2] = {&b1, &b2};
+        if (render_gpu) {
+            R.ctx = r1.ctx;
+            for (int s = 0; s < 2; s++) R.st[s].assign(m, MC_RENDER_SKIP);
+            for (size_t i = 0; i < m; i++, at++) {
+                const uint8_t cls[2] = {c1[at], c2[at]};
+                for (int s = 0; s < 2; s++) {
+                    const uint64_t len = b[s]->offsets[i + 1] - b[s]->offsets[i];
+                    if (cls[0] == cls[1]) {
+                        if (len || cls[0] == MC_CLASS_FOUND) R.st[s][i] = (uint8_t)(2 * cls[0] + s);
+                    } else if (len) {
+                        R.st[s][i] = (uint8_t)(6 + cls[s]);
+                    }
+                }
+            }
+            const std::vector<WholeSegment> *segs[2] = {r1.gpu ? &r1.gpu->segments() : nullptr, r2.gpu ? &r2.gpu->segments() : nullptr};
+            if (r1.gpu && r2.gpu) R.render_segments(2, segs, b, m);
+            else R.render_batch(2, b, m);
+            return;
+        }
         for (size_t i = 0; i < m; i++, at++) {
-            const DnaQBatch *b[2] = {&b1, &b2};
             const uint8_t cls[2] = {c1[at], c2[at]};
             for (int s = 0; s < 2; s++) {
                 const uint64_t o0 = b[s]->offsets[i], len = b[s]->offsets[i + 1] - o0;
@@ -1306,8 +1473,12 @@ int run_triple_reads_classifier(const Options &o)
                 }
             }
         }
-    });
+    }, render_gpu);
     for (FastqOut *f : {&found1, &found2, &half1, &half2, &nf1, &nf2, &found_s, &half_s, &nf_s}) f->close();
+    if (g_time_writers) {
+        fprintf(stderr, "[ingest] FastqOut: %.3f s in put() for %llu records\n", g_fastq_out_s, g_fastq_out_n);
+        R.report(found1.n + found2.n + half1.n + half2.n + nf1.n + nf2.n + found_s.n + half_s.n + nf_s.n);
+    }
     info("Reads have been written. Finishing...");
     write_file(o.work_dir + "/SUCCESS", "");
     return 0;
@@ -2035,6 +2206,7 @@ int run(const Options &o)
     if (o.parse_given && o.tool != "reads-classifier" && o.tool != "triple-reads-classifier" && o.tool != "seq-cov" && o.tool != "fmt-visualizer" &&
         o.tool != "environment-assembler-finder")
         throw Error("--parse does not apply to --tool " + o.tool);
+    if (o.render_given && o.tool != "reads-classifier" && o.tool != "triple-reads-classifier") throw Error("--render does not apply to --tool " + o.tool);
     if (o.tool == "kmer-counter") return run_kmer_counter(o);
     if (o.tool == "environment-finder-multi") return run_multi(o);
     if (o.tool == "reads-classifier") return run_reads_classifier(o);

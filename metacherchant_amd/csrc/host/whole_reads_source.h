@@ -30,6 +30,7 @@ struct WholeSegment {
     const uint64_t *d_words, *d_offsets;  // n_reads + 1 offsets: base positions in d_words (the first need not be 0)
     const int32_t *d_bad_pos;             // mc_classify_reads' bad_pos of the n_reads reads
     uint64_t first, n_reads;              // reads first .. first + n_reads - 1 of the batch just delivered
+    const uint8_t *d_phred = nullptr;     // a phred a base at the base positions of d_offsets (NULL: the source was not asked for bytes)
 };
 
 class WholeReadsSource {
@@ -212,7 +213,7 @@ private:
                 check(hipMemcpy(b.codes.data() + at, c.res.d_codes + o0, o1 - o0, hipMemcpyDeviceToHost), "hipMemcpy");
                 check(hipMemcpy(b.phred.data() + at, c.res.d_phred + o0, o1 - o0, hipMemcpyDeviceToHost), "hipMemcpy");
             }
-            segs_.push_back(WholeSegment{c.res.d_words, c.res.d_offsets + c.pos, c.res.d_bad_pos + c.pos, first, take});
+            segs_.push_back(WholeSegment{c.res.d_words, c.res.d_offsets + c.pos, c.res.d_bad_pos + c.pos, first, take, c.res.d_phred});
         } else {
             const DnaQBatch &h = c.host;
             const uint64_t o0 = h.offsets[c.pos], o1 = h.offsets[c.pos + take];
@@ -227,13 +228,15 @@ private:
             const std::vector<int32_t> bad = low_quality_positions(h, c.pos, take);
             check(hipSetDevice(device_), "hipSetDevice");
             char *d = nullptr;
-            const size_t wb = words.size() * 8, ob = off.size() * 8, bb = std::max<size_t>(bad.size() * 4, 4);
-            check(hipMalloc(reinterpret_cast<void **>(&d), wb + ob + bb), "hipMalloc");
+            const size_t wb = words.size() * 8, ob = off.size() * 8, bb = std::max<size_t>(bad.size() * 4, 4), qb = want_bytes_ ? (size_t)(o1 - o0) : 0;
+            check(hipMalloc(reinterpret_cast<void **>(&d), wb + ob + bb + std::max<size_t>(qb, 1)), "hipMalloc");
             owned_.push_back(d);
             check(hipMemcpy(d, words.data(), wb, hipMemcpyHostToDevice), "hipMemcpy");
             check(hipMemcpy(d + wb, off.data(), ob, hipMemcpyHostToDevice), "hipMemcpy");
             if (take) check(hipMemcpy(d + wb + ob, bad.data(), bad.size() * 4, hipMemcpyHostToDevice), "hipMemcpy");
-            segs_.push_back(WholeSegment{reinterpret_cast<uint64_t *>(d), reinterpret_cast<uint64_t *>(d + wb), reinterpret_cast<int32_t *>(d + wb + ob), first, take});
+            if (qb) check(hipMemcpy(d + wb + ob + bb, h.phred.data() + o0, qb, hipMemcpyHostToDevice), "hipMemcpy");  // (off starts at 0)
+            segs_.push_back(WholeSegment{reinterpret_cast<uint64_t *>(d), reinterpret_cast<uint64_t *>(d + wb), reinterpret_cast<int32_t *>(d + wb + ob), first, take,
+                                         want_bytes_ ? reinterpret_cast<uint8_t *>(d + wb + ob + bb) : nullptr});
         }
         c.pos += take;
     }

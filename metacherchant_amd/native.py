@@ -92,6 +92,17 @@ class _WholeReads(C.Structure):
                 ("d_bad_pos", C.c_void_p), ("d_codes", C.c_void_p), ("d_phred", C.c_void_p), ("device_ms", C.c_double)]
 
 
+class _RenderSide(C.Structure):
+    """mc_render_side"""
+    _fields_ = [("words", C.c_void_p), ("phred", C.c_void_p), ("offsets", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class _RenderResult(C.Structure):
+    """mc_render_result"""
+    _fields_ = [("start", C.c_uint64 * 16), ("bytes", C.c_uint64 * 16), ("records", C.c_uint64 * 16), ("error", C.c_int32),
+                ("error_side", C.c_uint32), ("error_read", C.c_uint64), ("error_value", C.c_uint32), ("device_ms", C.c_double)]
+
+
 WHOLE_FASTA, WHOLE_FASTQ = 0, 1  # mc_tokenize_whole format
 WHOLE_CODES, WHOLE_PHRED = 1, 2  # mc_tokenize_whole flags
 READ_COV_DTYPE = np.dtype([("sum", np.int32), ("covered", np.int32), ("last", np.int16), ("found", np.uint8), ("pad", np.uint8)])
@@ -100,6 +111,8 @@ LAST_COPY_WEAK_FP = 1  # mc_reads_last_copy flags (tests only): a 4-bit first fi
 CLASS_NOT_FOUND, CLASS_HALF_FOUND, CLASS_FOUND = 0, 1, 2  # mc_triple_classes
 SEQ_COV_MAX_TABLES = 4  # mc_seq_coverage
 PRESENCE_MAX_TABLES = 4  # mc_kmer_presence
+RENDER_MAX_STREAMS, RENDER_SKIP, RENDER_UNNUMBERED = 16, 0xFF, 2**64 - 1  # mc_render_fastq
+RENDER_EMPTY, RENDER_QUALITY, RENDER_STREAM = 1, 2, 3  # mc_render_result.error
 READS_IN_SET_WEAK_FILTER = 1  # mc_reads_in_set flags (tests only): no bit filter, every window is looked up in the set's table
 
 
@@ -119,6 +132,7 @@ EXPORTS = [
     "mc_env_join", "mc_env_join_dev", "mc_env_join_free", "mc_trim_paths", "mc_trim_paths_dev",
     "mc_kmers_encode_dev", "mc_kmers_decode_dev", "mc_save_kmers_gpu", "mc_load_kmers_gpu",
     "mc_tokenize_whole", "mc_tokenize_whole_dev", "mc_whole_text_bytes", "mc_whole_reads_to_host", "mc_whole_reads_free", "mc_reads_append_dev",
+    "mc_render_fastq", "mc_render_fastq_dev", "mc_render_fastq_bound",
 ]
 
 _LIB = None
@@ -248,6 +262,12 @@ def load():
         L.mc_whole_reads_free.argtypes = [vp, wr]
         L.mc_whole_reads_free.restype = None
         L.mc_reads_append_dev.argtypes = [vp, vp, vp, u64, vp, u64, vp]
+    if hasattr(L, "mc_render_fastq"):
+        rs, rr = C.POINTER(_RenderSide), C.POINTER(_RenderResult)
+        L.mc_render_fastq_dev.argtypes = [vp, rs, C.c_uint32, u64, C.c_uint32, u64p, vp, u64, rr]
+        L.mc_render_fastq.argtypes = [vp, rs, C.c_uint32, u64, C.c_uint32, u64p, vp, u64, rr]
+        L.mc_render_fastq_bound.argtypes = [u64, u64]
+        L.mc_render_fastq_bound.restype = u64
     if hasattr(L, "mc_shard_export"):  # (a tuning build of an older revision, MC_LIB: scripts/gpu_variants.sh)
         L.mc_shard_export.argtypes = [vp, C.c_char_p]
         L.mc_shard_attach.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, i32]
@@ -995,6 +1015,61 @@ def tokenize_whole(context, text, fastq, phred_offset=33, codes=True, phred=True
         out = d.to_host()
         out.update(n_reads=d.n_reads, n_bases=d.n_bases, device_ms=d.device_ms)
         return out
+
+
+def render_fastq_bound(n_bases, n_items):
+    """mc_render_fastq_bound: a capacity that always suffices for n_items records of n_bases bases in all"""
+    return int(load().mc_render_fastq_bound(int(n_bases), int(n_items)))
+
+
+def _render_result(r, n_streams):
+    return {"start": [int(r.start[t]) for t in range(n_streams)], "bytes": [int(r.bytes[t]) for t in range(n_streams)],
+            "records": [int(r.records[t]) for t in range(n_streams)], "error": int(r.error), "error_side": int(r.error_side),
+            "error_read": int(r.error_read), "error_value": int(r.error_value), "device_ms": float(r.device_ms)}
+
+
+def render_fastq_dev(context, sides, n_reads, n_streams, first_number, d_text, capacity):
+    """mc_render_fastq_dev: the FASTQ records of n_reads reads a side as text in d_text (uint8, 16-byte aligned, `capacity` bytes).  sides:
+    one or two tuples (d_words, d_phred, d_offsets, d_stream) of device tensors or pointers -- packed bases, a phred a base, n_reads + 1
+    base positions, a stream byte a read (RENDER_SKIP for none); first_number: per stream the number of its first record, or
+    RENDER_UNNUMBERED.  Returns a dict: start, bytes, records per stream, error (0, RENDER_EMPTY, RENDER_QUALITY), error_side,
+    error_read, error_value, device_ms.  McError when `capacity` is too small (-5) or an argument is bad; then .result holds that dict."""
+    arr = (_RenderSide * max(len(sides), 2))()
+    for i, s in enumerate(sides):
+        arr[i] = _RenderSide(*[_dptr(x) for x in s])
+    first = np.ascontiguousarray(first_number, dtype=np.uint64)
+    r = _RenderResult()
+    rc = load().mc_render_fastq_dev(context._h, arr, len(sides), int(n_reads), int(n_streams), _p(first, C.c_uint64), _dptr(d_text),
+                                    int(capacity), C.byref(r))
+    return _render_checked(context, rc, r, n_streams)
+
+
+def _render_checked(context, rc, r, n_streams):
+    res = _render_result(r, min(max(int(n_streams), 0), RENDER_MAX_STREAMS))
+    try:
+        context._chk(rc)
+    except McError as e:
+        e.result = res
+        raise
+    return res
+
+
+def render_fastq(context, sides, n_reads, n_streams, first_number, capacity=None, fill=0):
+    """mc_render_fastq: render_fastq_dev on numpy arrays (words uint64, phred uint8, offsets uint64, stream uint8 per side).  Returns
+    (text, result): text a uint8 array of `capacity` bytes (default: render_fastq_bound of the input), filled with `fill` where the call
+    writes nothing, stream t at result["start"][t] : + result["bytes"][t]."""
+    keep = [[np.ascontiguousarray(a, dtype=t) for a, t in zip(s, (np.uint64, np.uint8, np.uint64, np.uint8))] for s in sides]
+    arr = (_RenderSide * max(len(keep), 2))()
+    for i, s in enumerate(keep):
+        arr[i] = _RenderSide(*[a.ctypes.data_as(C.c_void_p) for a in s])
+    if capacity is None:
+        capacity = render_fastq_bound(sum(int(s[2][n_reads]) - int(s[2][0]) for s in keep), n_reads * len(keep))
+    text = np.full(max(int(capacity), 1), fill, dtype=np.uint8)
+    first = np.ascontiguousarray(first_number, dtype=np.uint64)
+    r = _RenderResult()
+    rc = load().mc_render_fastq(context._h, arr, len(keep), int(n_reads), int(n_streams), _p(first, C.c_uint64), text.ctypes.data_as(C.c_void_p),
+                                int(capacity), C.byref(r))
+    return text[:int(capacity)], _render_checked(context, rc, r, n_streams)
 
 
 def key_owner(key, n_owners):
