@@ -93,91 +93,72 @@ def code_objects(lib, outdir):
 
 
 HOSTTEST = os.path.join(LIBDIR, "mc_hosttest")
+HOSTDIR = os.path.join(CSRC, "host")
+HOST_FLAGS = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")]
+
+
+def _host_sources(suffix):
+    return sorted(os.path.join(HOSTDIR, f) for f in os.listdir(HOSTDIR) if f.endswith(suffix))
+
+
+def _link_host(out, units, force, verbose):
+    """A host program of csrc/host/<units>.cpp + envfinder.cpp against libmcgpu.so and HIP's host API (no device code).  Any host
+    header, any of its units or the library newer than the program rebuilds it; several units compile side by side into lib/obj_<name>."""
+    srcs = [os.path.join(HOSTDIR, u + ".cpp") for u in units + ["envfinder"]]
+    if not force and not _stale(out, srcs + _host_sources(".h") + [os.path.join(ROOT, "include", "mcgpu.h"), LIB]):
+        return out
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
+    flags = HOST_FLAGS + ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include")]
+    if len(units) > 1:
+        objdir = os.path.join(LIBDIR, "obj_" + os.path.basename(out))
+        os.makedirs(objdir, exist_ok=True)
+        objs = [os.path.join(objdir, os.path.splitext(os.path.basename(s))[0] + ".o") for s in srcs]
+        with ThreadPoolExecutor(min(len(srcs), MAX_JOBS)) as ex:
+            list(ex.map(lambda so: _run(["g++", "-c"] + flags + ["-o", so[1], so[0]], verbose), zip(srcs, objs)))
+        srcs = objs
+    _run(["g++"] + flags + ["-o", out] + srcs + ["-L", LIBDIR, "-lmcgpu", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN",
+                                                 "-Wl,-rpath," + os.path.join(rocm, "lib"), "-lpthread", "-lz", "-ldl"], verbose)
+    return out
+
+
+# the CLI's units (csrc/host/main.cpp says what each holds)
+CLI_UNITS = ["main", "options", "cli", "tool_kmer_counter", "tool_multi", "tool_classifiers", "tool_seq_cov", "tool_visualisers",
+             "tool_assembler_finder", "tool_environment_finder"]
 
 
 def build_host(force=False, verbose=False):
     """C++ host side: the `metacherchant` CLI (links libmcgpu.so) and the CPU-only `mc_hosttest`."""
-    hdir = os.path.join(CSRC, "host")
     os.makedirs(LIBDIR, exist_ok=True)
-    common = [os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "gpu_compactor.h"), os.path.join(hdir, "gpu_joiner.h"), os.path.join(hdir, "whole_reads_source.h"),
-            os.path.join(hdir, "fastq_out.h"), os.path.join(ROOT, "include", "mcgpu.h")]
-    flags = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")]
-    if force or _stale(HOSTTEST, common + hdrs + [os.path.join(hdir, "hosttest.cpp"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h")]):
-        cmd = ["g++"] + flags + ["-o", HOSTTEST, os.path.join(hdir, "hosttest.cpp")] + common + ["-lz", "-ldl"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    if os.path.exists(LIB) and (force or _stale(CLI, common + hdrs + [os.path.join(hdir, "main.cpp"), LIB])):
+    srcs = [os.path.join(HOSTDIR, "hosttest.cpp"), os.path.join(HOSTDIR, "envfinder.cpp")]
+    if force or _stale(HOSTTEST, srcs + _host_sources(".h") + [os.path.join(ROOT, "include", "mcgpu.h"), os.path.join(CSRC, "kmer_hash.h"),
+                                                               os.path.join(CSRC, "read_ptr.h")]):
+        _run(["g++"] + HOST_FLAGS + ["-o", HOSTTEST] + srcs + ["-lz", "-ldl"], verbose)
+    if os.path.exists(LIB):
         # (the CLI keeps the triple-reads-classifier's reads on the device itself: HIP's host API, no device code)
-        rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
-        cmd = ["g++"] + flags + ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"), "-o", CLI, os.path.join(hdir, "main.cpp")] + common + [
-            "-L", LIBDIR, "-lmcgpu", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib"),
-            "-lpthread", "-lz", "-ldl"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
+        _link_host(CLI, CLI_UNITS, force, verbose)
     return CLI
 
 
 UNITIGS_BENCH = os.path.join(LIBDIR, "mc_unitigs_bench")
+TRIM_PATHS_BENCH = os.path.join(LIBDIR, "mc_trim_paths_bench")
+WHOLE_READS_BENCH = os.path.join(LIBDIR, "mc_whole_reads_bench")
 
 
 def build_unitigs_bench(force=False, verbose=False):
     """mc_unitigs_bench (csrc/host/unitigs_bench.cpp): make_picture with and without mc_unitigs, timed; scripts/unitigs_bench.py runs it"""
-    hdir = os.path.join(CSRC, "host")
-    srcs = [os.path.join(hdir, "unitigs_bench.cpp"), os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "gpu_compactor.h"), os.path.join(ROOT, "include", "mcgpu.h")]
-    if force or _stale(UNITIGS_BENCH, srcs + hdrs + [LIB]):
-        rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-o", UNITIGS_BENCH] + srcs + [
-            "-L", LIBDIR, "-lmcgpu", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib"),
-            "-lpthread", "-lz", "-ldl"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    return UNITIGS_BENCH
-
-
-TRIM_PATHS_BENCH = os.path.join(LIBDIR, "mc_trim_paths_bench")
+    return _link_host(UNITIGS_BENCH, ["unitigs_bench"], force, verbose)
 
 
 def build_trim_paths_bench(force=False, verbose=False):
     """mc_trim_paths_bench (csrc/host/trim_paths_bench.cpp): the trim of one pass, the host's walk against mc_trim_paths, timed;
     scripts/trim_paths_bench.py runs it"""
-    hdir = os.path.join(CSRC, "host")
-    srcs = [os.path.join(hdir, "trim_paths_bench.cpp"), os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(ROOT, "include", "mcgpu.h")]
-    if force or _stale(TRIM_PATHS_BENCH, srcs + hdrs + [LIB]):
-        rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-o", TRIM_PATHS_BENCH] + srcs + [
-            "-L", LIBDIR, "-lmcgpu", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib"),
-            "-lpthread", "-lz", "-ldl"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    return TRIM_PATHS_BENCH
-
-
-WHOLE_READS_BENCH = os.path.join(LIBDIR, "mc_whole_reads_bench")
+    return _link_host(TRIM_PATHS_BENCH, ["trim_paths_bench"], force, verbose)
 
 
 def build_whole_reads_bench(force=False, verbose=False):
     """mc_whole_reads_bench (csrc/host/whole_reads_bench.cpp): the reader stage of the classifying tools, host against device, timed;
     scripts/whole_reads_bench.py runs it"""
-    hdir = os.path.join(CSRC, "host")
-    srcs = [os.path.join(hdir, "whole_reads_bench.cpp"), os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "whole_reads_source.h"), os.path.join(ROOT, "include", "mcgpu.h")]
-    if force or _stale(WHOLE_READS_BENCH, srcs + hdrs + [LIB]):
-        rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"), "-I",
-               os.path.join(ROOT, "include"), "-o", WHOLE_READS_BENCH] + srcs + [
-            "-L", LIBDIR, "-lmcgpu", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib"),
-            "-lpthread", "-lz", "-ldl"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    return WHOLE_READS_BENCH
+    return _link_host(WHOLE_READS_BENCH, ["whole_reads_bench"], force, verbose)
 
 
 def build_host_sanitized(kind, force=False, verbose=False):
@@ -188,7 +169,7 @@ def build_host_sanitized(kind, force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     out = os.path.join(LIBDIR, "mc_hosttest_" + kind)
     srcs = [os.path.join(hdir, "hosttest.cpp"), os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "fastq_out.h"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h"),
+    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "fastq_out.h"), os.path.join(hdir, "classifier_streams.h"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h"),
             os.path.join(ROOT, "include", "mcgpu.h")]
     san = {"asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "tsan": ["-fsanitize=thread"]}[kind]
     if force or _stale(out, srcs + hdrs):

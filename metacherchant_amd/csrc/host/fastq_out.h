@@ -1,4 +1,4 @@
-// The classifiers' FASTQ writers (main.cpp) and what --render adds to them, free of HIP so that mc_hosttest runs them under the
+// The classifiers' FASTQ writers (tool_classifiers.cpp) and what --render adds to them, free of HIP so that mc_hosttest runs them under the
 // sanitizers: FastqOut (WritersUtils.writeDnaQsToFastqFile, itmo!/io/writers/FastqDedicatedWriter.java:39-60) with put_rendered for
 // records that come as text, SideList with the body form for records whose numbers are not known yet, and render_ranges, which cuts
 // a batch at the segments of its device view.

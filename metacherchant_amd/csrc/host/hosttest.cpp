@@ -27,6 +27,10 @@
 // as one block through put_rendered, 10 .. 11 through put again.  <out_dir>/b.fastq: reads 8 and 9 through put, then a SideList that took
 // read 0 as a read, 1 .. 4 as a block of bodies, 5 as a read, 6 .. 7 as bodies.  Prints "a <records> b <records>", then render_ranges of
 // two designed covers, a line "R a b seg0 seg1" a range, and "E <message>" for a cover that ends before the batch does.
+// `mc_hosttest streams`: which output stream the classifiers give each read of a pair (csrc/host/classifier_streams.h), for every input.
+// "P found1 found2 len1 len2 st1 st2 counter" for reads-classifier's paired rule (lengths 0 and 3), "S found1 len1 st1 st2 counter"
+// for its single-end rule (called with a found flag and a length for the second side that it must ignore), "T class1 class2 len1 len2
+// st1 st2" for the triple rule; a stream prints as its number, MC_RENDER_SKIP as 255, a counter as its PAIR_* number.
 // `mc_hosttest placement <k>`: where the table puts a key (csrc/kmer_hash.h, the functions the kernels compile).  Reads hexadecimal
 // 64-bit words from stdin, one a line, and prints for each "fmix64 sk_order sk_bin sk_hmin_of_kmer": the hash of the word as a key, the
 // order and the bin of its low 32 bits, and the smallest order among the SK_M-mers of the word as a packed k-mer of k bases.
@@ -52,6 +56,7 @@
 
 #include "../kmer_hash.h"
 #include "../read_ptr.h"
+#include "classifier_streams.h"
 #include "envfinder.h"
 #include "fastq_out.h"
 
@@ -300,6 +305,29 @@ int main(int argc, char **argv)
             }
             return 0;
         }
+        if (argc == 2 && std::string(argv[1]) == "streams") {
+            const size_t lens[2] = {0, 3};
+            for (int f1 = 0; f1 < 2; f1++)
+                for (int f2 = 0; f2 < 2; f2++)
+                    for (size_t l1 : lens)
+                        for (size_t l2 : lens) {
+                            const ClassifiedPair p = classifier_streams(f1 != 0, f2 != 0, l1, l2, true);
+                            printf("P %d %d %zu %zu %u %u %d\n", f1, f2, l1, l2, p.st[0], p.st[1], p.counter);
+                        }
+            for (int f1 = 0; f1 < 2; f1++)
+                for (size_t l1 : lens) {
+                    const ClassifiedPair p = classifier_streams(f1 != 0, true, l1, 3, false);
+                    printf("S %d %zu %u %u %d\n", f1, l1, p.st[0], p.st[1], p.counter);
+                }
+            for (unsigned c1 = 0; c1 < 3; c1++)
+                for (unsigned c2 = 0; c2 < 3; c2++)
+                    for (size_t l1 : lens)
+                        for (size_t l2 : lens) {
+                            const TripleStreams t = triple_streams((uint8_t)c1, (uint8_t)c2, l1, l2);
+                            printf("T %u %u %zu %zu %u %u\n", c1, c2, l1, l2, t.st[0], t.st[1]);
+                        }
+            return 0;
+        }
         if (argc == 3 && std::string(argv[1]) == "placement") {
             const int k = atoi(argv[2]);
             if (k < mc::SK_M || k > 32) throw Error("placement: k from 15 to 32");
@@ -396,7 +424,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> [poly] | pointers <pos>... | dedup-tags <records> | long-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | render-host <out_dir> | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> [poly] | pointers <pos>... | dedup-tags <records> | long-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | render-host <out_dir> | streams | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

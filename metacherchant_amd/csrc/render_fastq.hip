@@ -1,5 +1,5 @@
 // libmcgpu.so, the FASTQ rendering unit: the classifiers' output records as text on the device (include/mcgpu.h mc_render_fastq_dev,
-// mc_render_fastq, mc_render_fastq_bound; itmo!/io/writers/FastqDedicatedWriter.java:39-60).  csrc/host/main.cpp FastqOut::put is the
+// mc_render_fastq, mc_render_fastq_bound; itmo!/io/writers/FastqDedicatedWriter.java:39-60).  csrc/host/fastq_out.h FastqOut::put is the
 // host loop these are compared with.  context.h lists the other units.
 //
 // An ITEM is one read of one side, item j = n_sides * read + side; a stream takes its items in item order.  A record's length depends

@@ -13,7 +13,7 @@ sweeps + bytes written) / (count sweep + write sweep), as a fraction of the 6.3 
 File time depends on the machine's storage; it is common to both ways and is reported, not judged.
 
 Every size is a process of its own under its own time limit (one process holds the GPU at a time); the first failure ends the run.
-The last line gives the `auto` constants of csrc/host/main.cpp: for the save and for the load the smallest measured size from
+The last line gives the `auto` constants of csrc/host/cli.h: for the save and for the load the smallest measured size from
 which on, at every measured size and k, the GPU way's median is below the host way's fastest run; null when there is none.
 
     python scripts/kmers_bin_bench.py [--sizes 10000 100000 1000000 10000000 100000000] [--reps 5] [--out profiles/kmers_bin_bench.txt]"""

@@ -7,7 +7,7 @@ the synthetic genome with a side arm every --fork-every bases, `last` on the far
 
 For every k, dir and number of entries one JSON line: the medians of --reps runs (the two ways in turn, the GPU's after one untimed
 run of the same size), the spread of each (max - min of its runs), all runs beside them, the time inside mc_trim_paths and its
-device_ms.  A last line gives TRIM_AUTO_MIN as main.cpp wants it: the smallest measured size from which, at every larger measured
+device_ms.  A last line gives TRIM_AUTO_MIN as csrc/host/cli.h wants it: the smallest measured size from which, at every larger measured
 size too, for every k and dir, the GPU way's median is below the host's by more than the host's own spread; null when there is none.
 
     python scripts/trim_paths_bench.py [--entries 10000 100000 1000000 10000000] [--k 31 63] [--dirs 1 0] [--reps 5] [--fork-every 300]"""

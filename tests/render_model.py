@@ -78,7 +78,7 @@ def pack_side(reads, lead=0):
     return words, phred, offsets
 
 
-# reads-classifier's eight streams (csrc/host/main.cpp run_reads_classifier): the four pair files, the heads of the two _s files (the
+# reads-classifier's eight streams (csrc/host/classifier_streams.h): the four pair files, the heads of the two _s files (the
 # "first only" pairs) and their tails (the "second only" pairs, unnumbered: they are numbered behind the heads when the run ends)
 FOUND_1, FOUND_2, NOT_FOUND_1, NOT_FOUND_2, FOUND_S, NOT_FOUND_S, FOUND_S_TAIL, NOT_FOUND_S_TAIL = range(8)
 CLASSIFIER_FIRST = [1, 1, 1, 1, 1, 1, UNNUMBERED, UNNUMBERED]
@@ -116,3 +116,34 @@ def classifier_files(pairs, found):
         "found_s.fastq": text[FOUND_S] + number_bodies(split_bodies(text[FOUND_S_TAIL], lengths[FOUND_S_TAIL]), heads[FOUND_S] + 1),
         "not_found_s.fastq": text[NOT_FOUND_S] + number_bodies(split_bodies(text[NOT_FOUND_S_TAIL], lengths[NOT_FOUND_S_TAIL]), heads[NOT_FOUND_S] + 1),
     }
+
+
+# triple-reads-classifier's nine streams: a pair file is 2 * class + side, an _s file 6 + class (the classes as include/mcgpu.h
+# numbers them)
+NOT_FOUND, HALF_FOUND, FOUND = range(3)
+
+
+def triple_sides(pairs, classes):
+    """the two sides of triple-reads-classifier's pairs with the stream of every read; classes: a (class of the first mate, class of
+    the second) per pair.  Written from the reference's lists and files (TripleFinder2.run, TripleReadsClassifier.java:248-267): a pair
+    whose mates share a class goes to that class's both_ list, whose first mates make <class>_1 and second mates <class>_2 -- all of
+    them for found, those of length > 0 for the other two classes; the mates of any other pair go each to its own class's s_ list,
+    which is written without its empty reads."""
+    both = {c: [] for c in (NOT_FOUND, HALF_FOUND, FOUND)}
+    single = {c: [] for c in (NOT_FOUND, HALF_FOUND, FOUND)}
+    for i, (ca, cb) in enumerate(classes):
+        if ca == cb:
+            both[ca].append(i)
+        else:
+            single[ca].append((i, 0))
+            single[cb].append((i, 1))
+    streams = [[SKIP] * len(pairs), [SKIP] * len(pairs)]
+    for c in both:
+        for side in (0, 1):
+            for i in both[c]:
+                if c == FOUND or len(pairs[i][side][0]) > 0:
+                    streams[side][i] = 2 * c + side
+        for i, side in single[c]:
+            if len(pairs[i][side][0]) > 0:
+                streams[side][i] = 6 + c
+    return [([a for a, _ in pairs], streams[0]), ([b for _, b in pairs], streams[1])]

@@ -97,7 +97,7 @@ class WholeReads:
         self.offsets = np.concatenate([[0], np.cumsum(np.array(self._lens, dtype=np.uint64))]).astype(np.uint64)
         self.n_reads = len(self._lens)
         bad = np.full(self.n_reads, -1, dtype=np.int32)
-        for r in range(self.n_reads):  # findReadWithCorrection's count of phred < 10 (main.cpp bad_positions)
+        for r in range(self.n_reads):  # findReadWithCorrection's count of phred < 10 (csrc/host/device.h bad_positions)
             low = np.flatnonzero(self.phred[int(self.offsets[r]):int(self.offsets[r + 1])] < 10)
             if len(low):
                 bad[r] = low[0] if len(low) == 1 else -2
