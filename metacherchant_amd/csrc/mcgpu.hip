@@ -1091,7 +1091,13 @@ int ensure_dups(mc_ctx *c)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         uint32_t fl[2];
         memcpy(fl, c->h_scratch + 21, sizeof fl);
-        if (!fl[0] && !fl[1]) { n_listed = c->h_scratch[20]; break; }
+        if (!fl[0] && !fl[1]) {
+            n_listed = c->h_scratch[20];
+            if (c->sw.ingest_debug) fprintf(stderr, "[join] %llu keys, level 1 by %s, %u slices, f2_lg %u, cap2 %llu, k_dup_find<%s>, %llu listed\n", n_used,
+                                                   have_l1 ? "merge streams" : "sweep", slices, f2_lg, (unsigned long long)cap2, per_sub <= 4500.0 ? "13, 256" : "15, 1024",
+                                                   (unsigned long long)n_listed);
+            break;
+        }
         // a stream overflowed (the merge kernel's were sized by a hint that fell short, or the keys are far from evenly spread): once
         // more from a sweep, whose streams are sized by the number of keys the table holds
         if (attempt >= 1 || !have_l1)
