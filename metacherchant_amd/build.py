@@ -15,11 +15,11 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmcgpu.so")
 CLI = os.path.join(LIBDIR, "metacherchant")
 
-# the library's units (csrc/context.h says what each holds), and the host reader the read-file entry point uses
+# the library's units (csrc/context.h says what each holds), and the host readers the read-file entry points use
 HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip", "trim_paths.hip", "kmers_bin.hip", "render_fastq.hip",
-               os.path.join("host", "envfinder.cpp")]
+               os.path.join("host", "reads_io.cpp")]
 # every header under csrc/ makes every object stale (a stale library would travel to the GPU box unnoticed)
-HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "envfinder.h"), os.path.join("test", "bfs_old_race.h"),
+HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "reads_io.h"), os.path.join("test", "bfs_old_race.h"),
                                                                       os.path.join(ROOT, "include", "mcgpu.h")]
 
 
@@ -97,14 +97,24 @@ HOSTDIR = os.path.join(CSRC, "host")
 HOST_FLAGS = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")]
 
 
+# what every host program is made of beside its own units: the readers of read files (the library's too) and the rest of the host side
+HOST_CORE = ["reads_io", "envfinder"]
+
+
 def _host_sources(suffix):
     return sorted(os.path.join(HOSTDIR, f) for f in os.listdir(HOSTDIR) if f.endswith(suffix))
 
 
+def _hosttest_inputs():
+    """(sources, headers) of mc_hosttest: the CPU-only program, plain or under a sanitizer"""
+    srcs = [os.path.join(HOSTDIR, u + ".cpp") for u in ["hosttest"] + HOST_CORE]
+    return srcs, _host_sources(".h") + [os.path.join(ROOT, "include", "mcgpu.h")] + [os.path.join(CSRC, h) for h in ("kmer_hash.h", "read_ptr.h", "switches.h")]
+
+
 def _link_host(out, units, force, verbose):
-    """A host program of csrc/host/<units>.cpp + envfinder.cpp against libmcgpu.so and HIP's host API (no device code).  Any host
+    """A host program of csrc/host/<units>.cpp + HOST_CORE against libmcgpu.so and HIP's host API (no device code).  Any host
     header, any of its units or the library newer than the program rebuilds it; several units compile side by side into lib/obj_<name>."""
-    srcs = [os.path.join(HOSTDIR, u + ".cpp") for u in units + ["envfinder"]]
+    srcs = [os.path.join(HOSTDIR, u + ".cpp") for u in units + HOST_CORE]
     if not force and not _stale(out, srcs + _host_sources(".h") + [os.path.join(ROOT, "include", "mcgpu.h"), LIB]):
         return out
     rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
@@ -129,9 +139,8 @@ CLI_UNITS = ["main", "options", "cli", "tool_kmer_counter", "tool_multi", "tool_
 def build_host(force=False, verbose=False):
     """C++ host side: the `metacherchant` CLI (links libmcgpu.so) and the CPU-only `mc_hosttest`."""
     os.makedirs(LIBDIR, exist_ok=True)
-    srcs = [os.path.join(HOSTDIR, "hosttest.cpp"), os.path.join(HOSTDIR, "envfinder.cpp")]
-    if force or _stale(HOSTTEST, srcs + _host_sources(".h") + [os.path.join(ROOT, "include", "mcgpu.h"), os.path.join(CSRC, "kmer_hash.h"),
-                                                               os.path.join(CSRC, "read_ptr.h")]):
+    srcs, hdrs = _hosttest_inputs()
+    if force or _stale(HOSTTEST, srcs + hdrs):
         _run(["g++"] + HOST_FLAGS + ["-o", HOSTTEST] + srcs + ["-lz", "-ldl"], verbose)
     if os.path.exists(LIB):
         # (the CLI keeps the triple-reads-classifier's reads on the device itself: HIP's host API, no device code)
@@ -165,12 +174,9 @@ def build_host_sanitized(kind, force=False, verbose=False):
     """mc_hosttest under a CPU sanitizer (kind: "asan" = address + undefined behaviour, "tsan" = threads): the host code --
     readers on several threads, the replay of java.util.HashMap with its tree bins, compaction, writers -- run by
     tests/test_host_sanitizers.py.  (No GPU sanitizer runs on this pool; the HIP side has the device self-check instead.)"""
-    hdir = os.path.join(CSRC, "host")
     os.makedirs(LIBDIR, exist_ok=True)
     out = os.path.join(LIBDIR, "mc_hosttest_" + kind)
-    srcs = [os.path.join(hdir, "hosttest.cpp"), os.path.join(hdir, "envfinder.cpp")]
-    hdrs = [os.path.join(hdir, "envfinder.h"), os.path.join(hdir, "fastq_out.h"), os.path.join(hdir, "classifier_streams.h"), os.path.join(CSRC, "kmer_hash.h"), os.path.join(CSRC, "read_ptr.h"),
-            os.path.join(ROOT, "include", "mcgpu.h")]
+    srcs, hdrs = _hosttest_inputs()
     san = {"asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "tsan": ["-fsanitize=thread"]}[kind]
     if force or _stale(out, srcs + hdrs):
         cmd = ["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")] + san + [

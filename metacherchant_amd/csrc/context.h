@@ -3,7 +3,8 @@
 // The library is sixteen units, each defining and launching its own kernels:
 //   mcgpu.hip       the table, the key join, the counting pipeline, the context ABI, and the table work of the walk (solid table,
 //                   the check of its "absent" look-ups)
-//   reads_file.hip  the device tokeniser's driver and mc_add_reads_file
+//   reads_file.hip  the device tokeniser's driver, the upload pipeline that feeds it a file's chunks (tokenize_file_chunks: mc_group_add_reads_file
+//                   runs on it too) and mc_add_reads_file; the host readers it falls back on are csrc/host/reads_io.cpp, linked into the library
 //   walk.hip        the walk's driver and result pool, mc_bfs*, mc_shard_*
 //   group.hip       mc_group_* (no kernels)
 //   classify.hip    mc_classify_reads*: the reads-classifier's per-read coverage (classify.h: its verdict), and mc_triple_classes*
@@ -32,6 +33,7 @@
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -626,7 +628,7 @@ int ensure_buf(mc_ctx *c, T **p, uint64_t *cap, uint64_t need)
 }
 
 // reads_file.hip: the device tokeniser
-namespace mch { struct PlainReadsFile; }
+namespace mch { struct PlainReadsFile; struct PackedBatch; }
 // The chunks of one file, tokenised into the read store back to back and counted together when the file ends: one run
 // of the counting pipeline (which reads and rewrites the whole table) instead of one per 256 MB of text.
 struct TokPending {
@@ -637,6 +639,20 @@ struct TokPending {
 };
 int tokenize_chunk_locked(mc_ctx *c, const mch::PlainReadsFile &f, const char *b, const char *e, uint8_t *d_text, uint64_t *n_reads_out,
                           bool *declined, TokPending *pend = nullptr);
+// One mapped file through the tokeniser, chunk by chunk (host/reads_io.h plain_chunks), into the read store of c: the bytes of chunk
+// i + 1 go up on a helper thread while chunk i is tokenised, the order of steps and the clean-up are written once, and the two callers
+// -- mc_add_reads_file, mc_group_add_reads_file -- say what is theirs.  flush, host_batch and after_chunk run without c's lock (ctx_failed
+// may run under it and takes none); each returns a code it has reported where its caller reports.
+struct FileChunkOps {
+    const char *who = "";                                // the function's name in front of the driver's own error texts
+    std::function<int(TokPending &)> flush;              // what has gathered is counted: ahead of a declined chunk's host batches, and when the file ends
+    uint64_t batch_reads = 0;                            // a declined chunk goes through the host parser in batches of so many reads ...
+    std::function<int(mch::PackedBatch &)> host_batch;   // ... each handed to this
+    std::function<int(size_t i, size_t n_chunks, TokPending &)> after_chunk;  // chunk i is done, its text still on the device
+    std::function<int(int)> ctx_failed;                  // (optional) a failure whose text c->err holds -> the code to return (mc_group: the text goes to the group)
+};
+using FileCuts = std::vector<std::pair<const char *, const char *>>;  // (what plain_chunks gives)
+int tokenize_file_chunks(mc_ctx *c, const mch::PlainReadsFile &f, const FileCuts &cuts, const FileChunkOps &ops, uint64_t *n_reads);
 // ... and what whole_reads.hip takes from it: the scan of 32-bit counts into 64-bit offsets and the newline pass
 int tok_scan(mc_ctx *c, const uint32_t *d_in, uint64_t n, unsigned long long *d_out, uint64_t *total);
 struct TokNewlines {  // the newline positions and the pass's tile buffers: the caller keeps them until its own passes are done

@@ -17,7 +17,7 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1 } ncclDataType_t;
 #endif
 
 #include "context.h"
-#include "host/envfinder.h"
+#include "host/reads_io.h"
 
 // mc_group: the native counterpart of metacherchant_amd/distributed.py, for a host that is one
 // process: a context per device, one host thread per device for the work, and the exchange as peer-to-peer copies --
@@ -493,33 +493,19 @@ int mc_group_add_reads_file(mc_group *g, const char *path, uint64_t *n_reads)
             g->dirty = true;
             mc_ctx *c0 = g->ctx[0];
             const size_t W = g->ctx.size();
-            const uint64_t chunk = g->sw.tokenizer_chunk_bytes;
-            std::vector<std::pair<const char *, const char *>> cuts;
-            for (const char *b = f.p, *end = f.p + f.n; b < end;) {
-                const char *e = (uint64_t)(end - b) <= chunk + chunk / 4 ? end : mch::plain_record_start(f, b + chunk);
-                cuts.emplace_back(b, e);
-                b = e;
-            }
-            {
-                std::lock_guard<std::mutex> g0(c0->mu);
-                HIPCHK(c0, hipSetDevice(c0->cfg.device));
-                const int r = rs_reserve(c0, (f.fastq ? f.n / 2 : f.n) / 32 + 2 * cuts.size() + 2);
-                if (r) return gfail(g, r, c0->err);
-            }
-            std::unique_ptr<TokPending> pend(new TokPending);
-            auto drop_pend = [&] { std::lock_guard<std::mutex> g0(c0->mu); pend.reset(); };
+            const auto cuts = mch::plain_chunks(f, g->sw.tokenizer_chunk_bytes);
             uint64_t total = 0, n_flushes = 0;
             // the reads gathered in `pend` so far: shares to the devices, exchange, count; the store then ends behind them
-            auto flush = [&]() -> int {
-                if (pend->reads == 0) { pend->base_word = -1; pend->bases = 0; return MC_OK; }
+            auto flush = [&](TokPending &P) -> int {
+                if (P.reads == 0) { P.base_word = -1; P.bases = 0; return MC_OK; }
                 n_flushes++;
-                const uint64_t n = pend->reads, base_word = (uint64_t)pend->base_word;
+                const uint64_t n = P.reads, base_word = (uint64_t)P.base_word;
                 std::vector<uint64_t> cut_off(W + 1, 0);  // base offset (relative to the batch) of every share's first read
                 {
                     std::lock_guard<std::mutex> g0(c0->mu);
                     if (hipSetDevice(c0->cfg.device) != hipSuccess) return gfail(g, MC_EHIP, "mc_group_add_reads_file: hipSetDevice");
                     for (size_t r = 0; r <= W; r++)
-                        if (hipMemcpyAsync(&cut_off[r], pend->off.p + n * r / W, 8, hipMemcpyDeviceToHost, c0->stream) != hipSuccess) return gfail(g, MC_EHIP, "mc_group_add_reads_file: copy failed");
+                        if (hipMemcpyAsync(&cut_off[r], P.off.p + n * r / W, 8, hipMemcpyDeviceToHost, c0->stream) != hipSuccess) return gfail(g, MC_EHIP, "mc_group_add_reads_file: copy failed");
                     if (hipStreamSynchronize(c0->stream) != hipSuccess) return gfail(g, MC_EHIP, "mc_group_add_reads_file: copy failed");
                 }
                 std::vector<GroupRank> R(W);
@@ -533,7 +519,7 @@ int mc_group_add_reads_file(mc_group *g, const char *path, uint64_t *n_reads)
                     X.windows = cut_off[r + 1] - cut_off[r];  // (an upper bound: a window per base)
                     if (r == 0) {  // in place: the share is where the walk will read it
                         X.d_words = c0->rs_words + base_word;
-                        X.d_off = pend->off.p;
+                        X.d_off = P.off.p;
                         X.in_store = (int64_t)base_word;
                         return MC_OK;
                     }
@@ -544,7 +530,7 @@ int mc_group_add_reads_file(mc_group *g, const char *path, uint64_t *n_reads)
                     const uint64_t w0 = std::max<uint64_t>(cut_off[r] / 32, 512) - 512, w1 = (cut_off[r + 1] + 31) / 32 + 1;
                     if (X.dw.alloc(w1 - w0) != hipSuccess || X.doff.alloc(b - a + 1) != hipSuccess) return MC_ENOMEM;
                     if (peer_copy(X.dw.p, c, c0->rs_words + base_word + w0, c0, (w1 - w0) * 8, c->stream) != hipSuccess ||
-                        peer_copy(X.doff.p, c, pend->off.p + a, c0, (b - a + 1) * 8, c->stream) != hipSuccess ||
+                        peer_copy(X.doff.p, c, P.off.p + a, c0, (b - a + 1) * 8, c->stream) != hipSuccess ||
                         hipStreamSynchronize(c->stream) != hipSuccess)
                         return MC_EHIP;
                     X.d_words = X.dw.p - w0;
@@ -558,83 +544,20 @@ int mc_group_add_reads_file(mc_group *g, const char *path, uint64_t *n_reads)
                 frc = group_exchange_count(g, R);
                 {   // the batch's reads stay in the first device's store, whoever counted them
                     std::lock_guard<std::mutex> g0(c0->mu);
-                    c0->rs_bases = std::max<uint64_t>(c0->rs_bases, (base_word + (pend->bases + 31) / 32) * 32);
+                    c0->rs_bases = std::max<uint64_t>(c0->rs_bases, (base_word + (P.bases + 31) / 32) * 32);
                 }
-                pend->reads = pend->bases = 0;
-                pend->base_word = -1;
+                P.reads = P.bases = 0;
+                P.base_word = -1;
                 return frc;
             };
-            struct Upload {
-                PoolBuf<uint8_t> text;
-                std::thread th;
-                bool ok = true;
-            };
-            std::unique_ptr<Upload> cur, nxt;
-            auto start_upload = [&](size_t i, std::unique_ptr<Upload> &u) -> int {
-                u.reset(new Upload);
-                const uint64_t n = (uint64_t)(cuts[i].second - cuts[i].first);
-                {
-                    std::lock_guard<std::mutex> g0(c0->mu);
-                    HIPCHK(c0, hipSetDevice(c0->cfg.device));
-                    HIPCHK(c0, u->text.alloc(&c0->tok_pool, (n + tok::T_TILE - 1) / tok::T_TILE * tok::T_TILE));
-                }
-                Upload *up = u.get();
-                const char *b = cuts[i].first;
-                up->th = std::thread([c0, up, b, n, &f] { up->ok = h2d_pinned(c0, up->text.p, b, n, f.fd, (uint64_t)(b - f.p)); });
-                return MC_OK;
-            };
-            auto finish = [&](std::unique_ptr<Upload> &u) {
-                if (!u) return;
-                if (u->th.joinable()) u->th.join();
-                std::lock_guard<std::mutex> g0(c0->mu);
-                u.reset();
-            };
-            rc = cuts.empty() ? MC_OK : start_upload(0, cur);
-            if (rc) rc = gfail(g, rc, c0->err);
-            for (size_t i = 0; i < cuts.size() && rc == MC_OK; i++) {
-                cur->th.join();
-                if (!cur->ok) { rc = gfail(g, MC_EHIP, "mc_group_add_reads_file: host-to-device copy failed"); break; }
-                if (i + 1 < cuts.size()) {
-                    rc = start_upload(i + 1, nxt);
-                    if (rc) { rc = gfail(g, rc, c0->err); break; }
-                }
-                uint64_t got = 0;
-                bool declined = false;
-                {
-                    std::lock_guard<std::mutex> g0(c0->mu);
-                    rc = tokenize_chunk_locked(c0, f, cuts[i].first, cuts[i].second, cur->text.p, &got, &declined, pend.get());
-                    if (rc) rc = gfail(g, rc, c0->err);
-                }
-                if (rc != MC_OK) break;
-                if (declined) {  // (what was gathered goes first: the host's batches are appended behind it)
-                    rc = flush();
-                    if (rc != MC_OK) break;
-                    int hrc = MC_OK;
-                    try {
-                        got = mch::parse_plain_range(f, cuts[i].first, cuts[i].second, W * per_dev, [&](mch::PackedBatch &b) {
-                            if (hrc == MC_OK && b.n_reads()) hrc = group_add_host_batch(g, b.words.data(), b.offsets.data(), b.n_reads());
-                        });
-                    } catch (...) {
-                        finish(cur);
-                        finish(nxt);
-                        drop_pend();
-                        throw;
-                    }
-                    rc = hrc;
-                    if (rc != MC_OK) break;
-                }
-                total += got;
-                if (pend->reads >= W * per_dev) {
-                    rc = flush();
-                    if (rc != MC_OK) break;
-                }
-                finish(cur);
-                cur = std::move(nxt);
-            }
-            finish(cur);
-            finish(nxt);
-            if (rc == MC_OK) rc = flush();
-            drop_pend();
+            FileChunkOps ops;
+            ops.who = "mc_group_add_reads_file";
+            ops.flush = flush;
+            ops.batch_reads = W * per_dev;
+            ops.host_batch = [&](mch::PackedBatch &b) { return b.n_reads() ? group_add_host_batch(g, b.words.data(), b.offsets.data(), b.n_reads()) : MC_OK; };
+            ops.after_chunk = [&](size_t, size_t, TokPending &P) { return P.reads >= W * per_dev ? flush(P) : MC_OK; };
+            ops.ctx_failed = [&](int code) { return gfail(g, code, c0->err); };
+            rc = tokenize_file_chunks(c0, f, cuts, ops, &total);
             if (rc != MC_OK) return rc;
             if (g->sw.ingest_debug)
                 fprintf(stderr, "[ingest] group: %zu chunk(s) tokenised on device %d, %llu reads in %llu exchange(s) over %zu devices\n", cuts.size(), c0->cfg.device,

@@ -22,6 +22,8 @@
 // read: "R <length>\t<bases, N as A>\t<phreds as chars from '!'>".  `mc_hosttest dnaq-range <file> <chunk>`: the same lines from the file
 // cut at record starts every <chunk> bytes, each piece read by DnaQReader over a range of memory.  An error ends both with status 1 after
 // the reads before it.
+// `mc_hosttest cuts <file> [<chunk>]`: the chunks the device tokeniser's drivers read the file in (reads_io.h plain_chunks), a line "b e" a
+// chunk, byte offsets in the file.  <chunk>: MC_TOKENIZER_CHUNK_BYTES as it would be spelt; left out: the switch's default.
 // `mc_hosttest render-host <out_dir>`: what --render adds to the host's writers (csrc/host/fastq_out.h), on designed reads (read i has
 // i % 7 + 1 bases, base j the code (i + j) % 4 and the phred (3 i + 5 j) % 63).  <out_dir>/a.fastq: reads 0 .. 4 through FastqOut::put, 5 .. 9
 // as one block through put_rendered, 10 .. 11 through put again.  <out_dir>/b.fastq: reads 8 and 9 through put, then a SideList that took
@@ -56,6 +58,7 @@
 
 #include "../kmer_hash.h"
 #include "../read_ptr.h"
+#include "../switches.h"
 #include "classifier_streams.h"
 #include "envfinder.h"
 #include "fastq_out.h"
@@ -226,17 +229,21 @@ int main(int argc, char **argv)
             const uint64_t chunk = strtoull(argv[3], nullptr, 10);
             PlainReadsFile f;
             if (!map_plain_reads(argv[2], &f)) throw Error("dnaq-range: not a plain FASTA / FASTQ file");
-            for (const char *p = f.p, *end = f.p + f.n; p < end;) {
-                const char *e = (uint64_t)(end - p) <= chunk + chunk / 4 ? end : plain_record_start(f, p + chunk);
-                DnaQReader part(p, e, reader.fastq(), reader.phred_offset());
+            for (const auto &cut : plain_chunks(f, chunk)) {
+                DnaQReader part(cut.first, cut.second, reader.fastq(), reader.phred_offset());
                 for (;;) {
                     b.clear();
                     const size_t got = read_some(part);
                     print();
                     if (got == 0) break;
                 }
-                p = e;
             }
+            return 0;
+        }
+        if ((argc == 3 || argc == 4) && std::string(argv[1]) == "cuts") {
+            PlainReadsFile f;
+            if (!map_plain_reads(argv[2], &f)) throw Error("cuts: not a plain FASTA / FASTQ file");
+            for (const auto &cut : plain_chunks(f, tokenizer_chunk_bytes_of(argc == 4 ? argv[3] : nullptr))) printf("%td %td\n", cut.first - f.p, cut.second - f.p);
             return 0;
         }
         if (argc == 3 && std::string(argv[1]) == "render-host") {
@@ -424,7 +431,7 @@ int main(int argc, char **argv)
         }
         const bool list_kmers = argc == 3 && std::string(argv[1]) == "kmers";
         if (!list_kmers && (argc != 4 || std::string(argv[1]) != "env")) {
-            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> [poly] | pointers <pos>... | dedup-tags <records> | long-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | render-host <out_dir> | streams | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
+            fprintf(stderr, "usage: mc_hosttest env <dump> <out_prefix> | kmers <dump> | unitigs <k-mers> | placement <k> [poly] | pointers <pos>... | dedup-tags <records> | long-tags <records> | cutreads <reads> <keep> <out.fasta> <index> | dnaq <reads> | dnaq-range <reads> <chunk> | cuts <reads> [<chunk>] | render-host <out_dir> | streams | colour <dump> <out_dir> <name> | seeds <fasta> | reads <file> | fmt <float> | dtoa <hex doubles> | hashmap <keys> | multi <out_dir> <seq> <gene_id> <env>... | multi-packed <out_dir> <seq> <gene_id> <env>...\n");
             return 2;
         }
         std::ifstream f(argv[2]);

@@ -6,7 +6,7 @@
 // into the _dev entry points -- a segment is a slice of one chunk's result, its offsets absolute base positions in its words.  A chunk
 // the device declines is read by DnaQReader's own record functions over that range of memory (the same reads, the same messages) and
 // its segments are packed here and copied up; a compressed file, or an empty one, goes to DnaQReader whole in the same way.
-// (Not part of envfinder.cpp, which stays free of HIP for mc_hosttest.)
+// (Not part of reads_io.cpp, which stays free of HIP for mc_hosttest and the library.)
 #pragma once
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -21,8 +21,9 @@
 
 #include <hip/hip_runtime_api.h>
 
-#include "envfinder.h"
+#include "../switches.h"
 #include "mcgpu.h"
+#include "reads_io.h"
 
 namespace mch {
 
@@ -44,13 +45,7 @@ public:
         offset_ = host_->phred_offset();
         compressed_ = host_->compressed();
         if (!compressed_ && map_file()) {
-            const char *e = getenv("MC_TOKENIZER_CHUNK_BYTES");
-            const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(e && *e ? strtoull(e, nullptr, 10) : 1ull << 28, 64), 3ull << 29);
-            for (const char *b = file_.p, *end = file_.p + file_.n; b < end;) {
-                const char *c = (uint64_t)(end - b) <= chunk + chunk / 4 ? end : plain_record_start(file_, b + chunk);
-                cuts_.emplace_back(b, c);
-                b = c;
-            }
+            cuts_ = plain_chunks(file_, tokenizer_chunk_bytes_of(getenv("MC_TOKENIZER_CHUNK_BYTES")));
             host_.reset();  // (its part is done: the format and the quality offset)
         }
     }

@@ -5,7 +5,7 @@
 
 #include "context.h"
 #include "tokenizer.h"
-#include "host/envfinder.h"
+#include "host/reads_io.h"
 
 // exclusive scan of n 32-bit counts into 64-bit offsets; *total on the host
 int tok_scan(mc_ctx *c, const uint32_t *d_in, uint64_t n, unsigned long long *d_out, uint64_t *total)
@@ -237,6 +237,96 @@ int tokenize_chunk_locked(mc_ctx *c, const mch::PlainReadsFile &f, const char *b
     return MC_OK;
 }
 
+namespace {
+// The two uploads of a file in flight and the reads its chunks have gathered, with the context whose pool their blocks come from:
+// whichever way the driver below is left (the host parser may throw), the helper threads are joined and the blocks go back under
+// that context's lock.
+struct FileInFlight {
+    struct Upload { PoolBuf<uint8_t> text; std::thread th; bool ok = true; };
+    mc_ctx *c;
+    std::unique_ptr<Upload> cur, nxt;
+    std::unique_ptr<TokPending> pend{new TokPending};
+    explicit FileInFlight(mc_ctx *ctx) : c(ctx) {}
+    ~FileInFlight()
+    {
+        release(cur);
+        release(nxt);
+        std::lock_guard<std::mutex> g(c->mu);
+        pend.reset();
+    }
+    // the bytes [b, e) of f start on their way into a block of u's own
+    int start(std::unique_ptr<Upload> &u, const mch::PlainReadsFile &f, const char *b, const char *e)
+    {
+        u.reset(new Upload);
+        const uint64_t n = (uint64_t)(e - b);
+        {
+            std::lock_guard<std::mutex> g(c->mu);
+            HIPCHK(c, hipSetDevice(c->cfg.device));
+            HIPCHK(c, u->text.alloc(&c->tok_pool, (n + tok::T_TILE - 1) / tok::T_TILE * tok::T_TILE));
+        }
+        Upload *up = u.get();
+        mc_ctx *ctx = c;
+        up->th = std::thread([ctx, up, b, n, &f] { up->ok = h2d_pinned(ctx, up->text.p, b, n, f.fd, (uint64_t)(b - f.p)); });
+        return MC_OK;
+    }
+    void release(std::unique_ptr<Upload> &u)
+    {
+        if (!u) return;
+        if (u->th.joinable()) u->th.join();
+        std::lock_guard<std::mutex> g(c->mu);
+        u.reset();
+    }
+};
+}  // namespace
+
+// Chunks of 256 MB: the bytes of chunk i + 1 cross the link (a helper thread, pinned staging buffers) while the kernels tokenise
+// chunk i.  The context's lock is taken per step, never around the host parser or the caller's flush, host_batch and after_chunk.
+int tokenize_file_chunks(mc_ctx *c, const mch::PlainReadsFile &f, const FileCuts &cuts, const FileChunkOps &ops, uint64_t *n_reads)
+{
+    auto own = [&](int rc) { return rc != MC_OK && ops.ctx_failed ? ops.ctx_failed(rc) : rc; };
+    if (c->rs_enabled) {  // the read store grows once, not chunk by chunk (FASTA: a base a byte at most; FASTQ: half that)
+        std::lock_guard<std::mutex> g(c->mu);
+        const int r = [&]() -> int {
+            HIPCHK(c, hipSetDevice(c->cfg.device));
+            return rs_reserve(c, (f.fastq ? f.n / 2 : f.n) / 32 + 2 * cuts.size() + 2);
+        }();
+        if (r) return own(r);
+    }
+    FileInFlight fl(c);
+    uint64_t total = 0;
+    int rc = cuts.empty() ? MC_OK : own(fl.start(fl.cur, f, cuts[0].first, cuts[0].second));
+    for (size_t i = 0; i < cuts.size() && rc == MC_OK; i++) {
+        fl.cur->th.join();
+        if (!fl.cur->ok) {
+            std::lock_guard<std::mutex> g(c->mu);
+            rc = own(fail(c, MC_EHIP, "%s: host-to-device copy failed", ops.who));
+            break;
+        }
+        if (i + 1 < cuts.size() && (rc = own(fl.start(fl.nxt, f, cuts[i + 1].first, cuts[i + 1].second))) != MC_OK) break;
+        uint64_t got = 0;
+        bool declined = false;
+        {
+            std::lock_guard<std::mutex> g(c->mu);
+            rc = own(tokenize_chunk_locked(c, f, cuts[i].first, cuts[i].second, fl.cur->text.p, &got, &declined, fl.pend.get()));
+        }
+        if (rc != MC_OK) break;
+        if (declined) {  // (what was gathered goes first: the host's batches are appended behind what is counted)
+            if ((rc = ops.flush(*fl.pend)) != MC_OK) break;
+            got = mch::parse_plain_range(f, cuts[i].first, cuts[i].second, ops.batch_reads, [&](mch::PackedBatch &b) {
+                if (rc == MC_OK) rc = ops.host_batch(b);
+            });
+            if (rc != MC_OK) break;
+        }
+        total += got;
+        if ((rc = ops.after_chunk(i, cuts.size(), *fl.pend)) != MC_OK) break;
+        fl.release(fl.cur);
+        fl.cur = std::move(fl.nxt);
+    }
+    if (rc == MC_OK) rc = ops.flush(*fl.pend);  // (no upload is left by now)
+    if (rc == MC_OK) *n_reads = total;
+    return rc;
+}
+
 extern "C" int mc_add_reads_file(mc_ctx *c, const char *path, uint64_t *n_reads)
 {
     if (!c) return MC_EINVAL;
@@ -244,140 +334,60 @@ extern "C" int mc_add_reads_file(mc_ctx *c, const char *path, uint64_t *n_reads)
     if (!path) return fail(c, MC_EINVAL, "mc_add_reads_file: null path");
     try {
         int rc = MC_OK;
-        auto sink = [&](mch::PackedBatch &b) {
-            if (rc == MC_OK) rc = mc_add_reads_packed(c, b.words.data(), b.offsets.data(), b.n_reads());
-        };
+        auto add_batch = [c](mch::PackedBatch &b) { return mc_add_reads_packed(c, b.words.data(), b.offsets.data(), b.n_reads()); };
         // Uncompressed FASTA / FASTQ: the bytes go to the device in chunks cut at record starts and are tokenised there
         // (csrc/tokenizer.h); a chunk the device declines goes through the host parser, as does any other kind of file
         // (MC_TOKENIZER=host: every file).  Host batches hold 2^20 reads; the context's lock is taken per batch / chunk.
         mch::PlainReadsFile f;
         if (!c->sw.tokenizer_host && mch::map_plain_reads(path, &f)) {
-            // chunks of 256 MB: the bytes of chunk i + 1 cross the link (a helper thread, pinned staging buffers) while
-            // the kernels tokenise and count chunk i
-            const uint64_t chunk = c->sw.tokenizer_chunk_bytes;
             const bool dbg = c->sw.ingest_debug;
             auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
             const double t_begin = now();
-            std::vector<std::pair<const char *, const char *>> cuts;
-            for (const char *b = f.p, *end = f.p + f.n; b < end;) {
-                const char *e = (uint64_t)(end - b) <= chunk + chunk / 4 ? end : mch::plain_record_start(f, b + chunk);
-                cuts.emplace_back(b, e);
-                b = e;
-            }
-            struct Upload {
-                PoolBuf<uint8_t> text;
-                std::thread th;
-                bool ok = true;
-            };
-            if (c->rs_enabled) {  // the read store grows once, not chunk by chunk (FASTA: a base a byte at most; FASTQ: half that)
+            const auto cuts = mch::plain_chunks(f, c->sw.tokenizer_chunk_bytes);
+            FileChunkOps ops;
+            ops.who = "mc_add_reads_file";
+            ops.flush = [c](TokPending &P) { std::lock_guard<std::mutex> g(c->mu); return tok_flush_locked(c, P); };
+            ops.batch_reads = 1u << 20;
+            ops.host_batch = add_batch;
+            ops.after_chunk = [&](size_t i, size_t n_chunks, TokPending &) -> int {
+                if (i != 0 || n_chunks == 1) return MC_OK;
+                // No capacity hint that still holds: the first chunk says how many distinct k-mers a byte of this file
+                // brings, the file's size says how many chunks follow -- the table goes to its final size now, with one
+                // chunk's keys to move, instead of being rebuilt every other chunk (10 M reads with 1 % errors in six
+                // chunks: 110 ms of counting against ~45).  An over-estimate (the later chunks repeat k-mers of the first)
+                // costs memory, bounded by a third of what the device has free.
                 std::lock_guard<std::mutex> g(c->mu);
-                HIPCHK(c, hipSetDevice(c->cfg.device));
-                int r = rs_reserve(c, (f.fastq ? f.n / 2 : f.n) / 32 + 2 * cuts.size() + 2);
-                if (r) return r;
-            }
-            std::unique_ptr<Upload> cur, nxt;
-            auto start_upload = [&](size_t i, std::unique_ptr<Upload> &u) -> int {
-                u.reset(new Upload);
-                const uint64_t n = (uint64_t)(cuts[i].second - cuts[i].first);
-                {
-                    std::lock_guard<std::mutex> g(c->mu);
-                    HIPCHK(c, hipSetDevice(c->cfg.device));
-                    HIPCHK(c, u->text.alloc(&c->tok_pool, (n + tok::T_TILE - 1) / tok::T_TILE * tok::T_TILE));
+                unsigned long long used = 0;
+                uint32_t fatal = 0;
+                int r = read_counters(c, &used, &fatal);
+                if (r != MC_OK) return r;
+                const bool hint_holds = c->cfg.capacity_hint && used < c->cfg.capacity_hint;
+                if (!hint_holds && used) {
+                    const double scale = (double)f.n / (double)(cuts[0].second - cuts[0].first);
+                    const double load = c->mm_k ? 0.36 : 0.6;
+                    size_t fr = 0, tot = 0;
+                    if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
+                    uint64_t want_slots = (uint64_t)((double)used * scale / load);
+                    want_slots = std::min<uint64_t>(want_slots, fr / 3 / sizeof(Slot));
+                    const uint64_t want = regions_for(c, want_slots);
+                    if (want > c->n_regions && want_slots > c->n_slots()) {
+                        if (dbg) fprintf(stderr, "[ingest] %llu distinct k-mers after %.0f MB of %.0f MB: table to %.1f GB\n", used,
+                                         (cuts[0].second - cuts[0].first) / 1e6, f.n / 1e6, (double)(want << c->sb) * sizeof(Slot) / 1e9);
+                        r = table_grow(c, want);
+                        if (r != MC_OK) return r;
+                        c->solid_list_fresh = false;
+                    }
                 }
-                Upload *up = u.get();
-                const char *b = cuts[i].first;
-                up->th = std::thread([c, up, b, n, &f] { up->ok = h2d_pinned(c, up->text.p, b, n, f.fd, (uint64_t)(b - f.p)); });
                 return MC_OK;
             };
-            auto finish = [&](std::unique_ptr<Upload> &u) {  // (the pool is the context's: blocks go back under its lock)
-                if (!u) return;
-                if (u->th.joinable()) u->th.join();
-                std::lock_guard<std::mutex> g(c->mu);
-                u.reset();
-            };
-            std::unique_ptr<TokPending> pend(new TokPending);  // (its pool block goes back under the context's lock)
-            auto drop_pend = [&] {
-                std::lock_guard<std::mutex> g(c->mu);
-                pend.reset();
-            };
             uint64_t total = 0;
-            rc = cuts.empty() ? MC_OK : start_upload(0, cur);
-            for (size_t i = 0; i < cuts.size() && rc == MC_OK; i++) {
-                cur->th.join();
-                if (!cur->ok) {
-                    std::lock_guard<std::mutex> g(c->mu);
-                    rc = fail(c, MC_EHIP, "mc_add_reads_file: host-to-device copy failed");
-                    break;
-                }
-                if (i + 1 < cuts.size()) {
-                    rc = start_upload(i + 1, nxt);
-                    if (rc != MC_OK) break;
-                }
-                uint64_t got = 0;
-                bool declined = false;
-                {
-                    std::lock_guard<std::mutex> g(c->mu);
-                    rc = tokenize_chunk_locked(c, f, cuts[i].first, cuts[i].second, cur->text.p, &got, &declined, pend.get());
-                    if (rc == MC_OK && declined) rc = tok_flush_locked(c, *pend);  // (the host's batches are appended behind what is counted)
-                }
-                if (rc != MC_OK) break;
-                if (declined) {
-                    try {
-                        got = mch::parse_plain_range(f, cuts[i].first, cuts[i].second, 1u << 20, sink);
-                    } catch (...) {
-                        finish(cur);
-                        finish(nxt);
-                        drop_pend();
-                        throw;
-                    }
-                    if (rc != MC_OK) break;
-                }
-                total += got;
-                if (i == 0 && cuts.size() > 1) {
-                    // No capacity hint that still holds: the first chunk says how many distinct k-mers a byte of this file
-                    // brings, the file's size says how many chunks follow -- the table goes to its final size now, with one
-                    // chunk's keys to move, instead of being rebuilt every other chunk (10 M reads with 1 % errors in six
-                    // chunks: 110 ms of counting against ~45).  An over-estimate (the later chunks repeat k-mers of the first)
-                    // costs memory, bounded by a third of what the device has free.
-                    std::lock_guard<std::mutex> g(c->mu);
-                    unsigned long long used = 0;
-                    uint32_t fatal = 0;
-                    rc = read_counters(c, &used, &fatal);
-                    if (rc != MC_OK) break;
-                    const bool hint_holds = c->cfg.capacity_hint && used < c->cfg.capacity_hint;
-                    if (!hint_holds && used) {
-                        const double scale = (double)f.n / (double)(cuts[0].second - cuts[0].first);
-                        const double load = c->mm_k ? 0.36 : 0.6;
-                        size_t fr = 0, tot = 0;
-                        if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
-                        uint64_t want_slots = (uint64_t)((double)used * scale / load);
-                        want_slots = std::min<uint64_t>(want_slots, fr / 3 / sizeof(Slot));
-                        const uint64_t want = regions_for(c, want_slots);
-                        if (want > c->n_regions && want_slots > c->n_slots()) {
-                            if (dbg) fprintf(stderr, "[ingest] %llu distinct k-mers after %.0f MB of %.0f MB: table to %.1f GB\n", used,
-                                             (cuts[0].second - cuts[0].first) / 1e6, f.n / 1e6, (double)(want << c->sb) * sizeof(Slot) / 1e9);
-                            rc = table_grow(c, want);
-                            if (rc != MC_OK) break;
-                            c->solid_list_fresh = false;
-                        }
-                    }
-                }
-                finish(cur);
-                cur = std::move(nxt);
-            }
-            finish(cur);
-            finish(nxt);
-            if (rc == MC_OK) {
-                std::lock_guard<std::mutex> g(c->mu);
-                rc = tok_flush_locked(c, *pend);
-            }
-            drop_pend();
+            rc = tokenize_file_chunks(c, f, cuts, ops, &total);
             if (rc != MC_OK) return rc;
             if (dbg) fprintf(stderr, "[ingest] device tokeniser: %zu chunk(s), %.1f MB in %.3f s\n", cuts.size(), f.n / 1e6, now() - t_begin);
             if (n_reads) *n_reads = total;
             return MC_OK;
         }
-        const uint64_t n = mch::load_reads_file(path, 1u << 20, sink);
+        const uint64_t n = mch::load_reads_file(path, 1u << 20, [&](mch::PackedBatch &b) { if (rc == MC_OK) rc = add_batch(b); });
         if (rc != MC_OK) return rc;
         if (n_reads) *n_reads = n;
         return MC_OK;

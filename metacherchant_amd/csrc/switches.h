@@ -47,6 +47,13 @@ struct mc_switches {
     bool group_walk_gather = false;           // MC_GROUP_WALK=gather: the walk on gathered solid k-mers, not on every device's table
 };
 
+// MC_TOKENIZER_CHUNK_BYTES as it is spelt (NULL or empty: unset, mc_switches' default) -> the chunk size: for read_switches() below, for
+// the CLI's WholeReadsSource (csrc/host/whole_reads_source.h: the far side of the ABI, it reads the environment itself), for `mc_hosttest cuts`
+inline uint64_t tokenizer_chunk_bytes_of(const char *text)
+{
+    return std::min<uint64_t>(std::max<uint64_t>(text && *text ? strtoull(text, nullptr, 10) : mc_switches().tokenizer_chunk_bytes, 64), 3ull << 29);
+}
+
 inline mc_switches read_switches()
 {
     auto off = [](const char *name) { const char *e = getenv(name); return e && !strcmp(e, "0"); };
@@ -65,7 +72,7 @@ inline mc_switches read_switches()
     if (const char *e = getenv("MC_MAX_RUN_BASES_PER_WINDOW")) if (*e) s.max_run_bases_per_window = std::max<uint64_t>(strtoull(e, nullptr, 10), 1u << 20);
     s.exchange_binned = !off("MC_EXCHANGE_BINNED");
     if (const char *e = getenv("MC_TOKENIZER")) s.tokenizer_host = !strcmp(e, "host");
-    s.tokenizer_chunk_bytes = std::min<uint64_t>(std::max<uint64_t>(num("MC_TOKENIZER_CHUNK_BYTES", 1ull << 28), 64), 3ull << 29);
+    s.tokenizer_chunk_bytes = tokenizer_chunk_bytes_of(getenv("MC_TOKENIZER_CHUNK_BYTES"));
     if (const char *e = getenv("MC_BFS_DIRECT")) s.bfs_direct = strcmp(e, "0") != 0;
     s.bfs_companion = !off("MC_BFS_COMPANION");
     if (const char *e = getenv("MC_BFS_SELFCHECK")) s.bfs_selfcheck = *e && *e != '0';

@@ -2,7 +2,7 @@
 //
 // The reference parses inside its dispatcher's lock, one thread for the whole file (src/io/ReadsDispatcher.java:34-53 ->
 // itmo!/io/readers/FastaReader.java:54-104, FastqReader.java:53-82, FastaReaderFromXQSourceTrunc.java:61-95); the host
-// reader of csrc/host/envfinder.cpp does it on all cores (~5 Gbases/s).  Here the file's bytes go to HBM as they are and
+// reader of csrc/host/reads_io.cpp does it on all cores (~5 Gbases/s).  Here the file's bytes go to HBM as they are and
 // a handful of data-parallel passes do the rest, with the reference's policy:
 //   FASTA  a line that starts with '>' or ';' ends the record before it; the other lines of a record are concatenated
 //          (a trailing '\r' comes off); a record with an N / n anywhere is dropped whole; empty records give nothing;

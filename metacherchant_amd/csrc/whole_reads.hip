@@ -1,6 +1,6 @@
 // libmcgpu.so: whole reads with their qualities, tokenised on the device (include/mcgpu.h mc_tokenize_whole) -- what the classifying
 // tools read their -r files with.  The counting tokeniser (csrc/tokenizer.h) drops FASTA records with N and splits FASTQ reads where
-// phred < 1; this one keeps DnaQReader's policy (csrc/host/envfinder.cpp, restating itmo!/io/ReadersUtils.java:185-215 readDnaQLazy,
+// phred < 1; this one keeps DnaQReader's policy (csrc/host/reads_io.cpp, restating itmo!/io/ReadersUtils.java:185-215 readDnaQLazy,
 // itmo!/io/readers/FastqReader.java:53-82, FastaWithNsReader, itmo!/dna/DnaQBuilder.java:32-45):
 //   FASTQ  records of four lines; N n . give base 0 with phred 0, any other base its code and (quality char - offset) & 63; a read
 //          of length 0 is a read;

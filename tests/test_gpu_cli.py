@@ -422,6 +422,55 @@ def test_cli_several_devices_equal_one(cli, tmp_path, devices, k, extra, env):
     _assert_same_tree(res, outs["one"][0], want)
 
 
+def test_cli_several_devices_chunk_declined_to_the_host_parser(cli, tmp_path):
+    """mc_group_add_reads_file when the first device declines a chunk in the middle of a file (a blank line between two FASTQ
+    records): what the chunks before it gathered is exchanged and counted first, the chunk goes through the host parser and its
+    batches to the devices, and the chunks behind it are the device's again.  Output byte-identical with one device's and with
+    the oracle's."""
+    import re
+    from tests import tokenizer_cases as tc
+    k = 15
+    genome, reads, _ = synth_case(1, 3000, 600, 100, 100)
+    recs = ["@r%d\n%s\n+\n%s\n" % (i, po.decode(reads[i * 100:(i + 1) * 100]), "I" * 100) for i in range(600)]
+    text = ("".join(recs[:300]) + "\n" + "".join(recs[300:])).encode()
+    fq = str(tmp_path / "blank.fq")
+    with open(fq, "wb") as f:
+        f.write(text)
+    seq = str(tmp_path / "genes.fasta")
+    with open(seq, "w") as f:
+        f.write(">g1\n%s\n" % po.decode(genome[1000:1200]))
+    env = {"MC_TOKENIZER_CHUNK_BYTES": "20000", "MC_GROUP_BATCH_READS": "128", "MC_INGEST_DEBUG": "1"}
+    extra = ["--maxkmers", "2000", "--coverage", "3"]
+    outs = {}
+    for name, dev in (("one", None), ("many", "0,0")):
+        out = str(tmp_path / ("out_" + name))
+        cmd = [cli, "-k", str(k), "-i", fq, "--seq", seq, "-o", out, "-w", str(tmp_path / ("wd_" + name)), "--force"] + extra
+        if dev:
+            cmd += ["--devices", dev]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
+        assert p.returncode == 0, p.stderr[-2000:]
+        outs[name] = (out, p.stderr)
+    err = outs["many"][1]
+    assert "Counting on 2 devices" in err
+    # the device prints a line for every chunk it did not decline: all but the one with the blank line, which is neither the
+    # first nor the last, and in the file's order
+    cuts = tc.cut_positions(text, True, 20000)
+    lines = [tc.count_lines(text[b:e]) for b, e, _ in cuts]
+    declined = [i for i, (b, e, _) in enumerate(cuts) if b"\n\n" in text[b:e]]
+    assert len(declined) == 1 and 0 < declined[0] < len(cuts) - 1, (declined, len(cuts))
+    accepted = [int(n) for n in re.findall(r"\[ingest\] device tokeniser: [0-9.]+ MB text, (\d+) lines", err)]
+    assert len(accepted) == len(cuts) - 1 and accepted == lines[:declined[0]] + lines[declined[0] + 1:], (accepted, lines)
+    group = [l for l in err.splitlines() if "[ingest] group:" in l]
+    assert len(group) == 1 and "%d chunk(s) tokenised" % len(cuts) in group[0] and " 600 reads in " in group[0], err[-2000:]
+    assert int(group[0].split(" reads in ")[1].split()[0]) >= 2, group[0]  # (ahead of the declined chunk, and when the file ends)
+    seqs, comments = ho.rich_fasta_read(seq)
+    want = str(tmp_path / "want")
+    _, res = _oracle_run([fq], k, po.KEY_PACKED, seqs, comments, want, max_kmers=2000, coverage=3)
+    assert any(files for files in res.values()), "the seed's environment is not empty"
+    _assert_same_tree(res, outs["many"][0], want)
+    _assert_same_tree(res, outs["one"][0], want)
+
+
 def test_cli_devices_batch_that_falls_back_to_keys_keeps_its_owners(cli, tmp_path):
     """a batch whose records overflow an owner's piece (low-complexity reads: one minimizer, one owner) travels as
     keys instead.  Keys used to be dealt by their own hash, records by their minimizer: a k-mer counted as records in one

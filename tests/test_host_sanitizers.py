@@ -1,5 +1,5 @@
-"""The CPU side under sanitizers (`-m "not gpu"`): the C++ host code (csrc/host/envfinder.cpp: readers on
-several threads, the replay of java.util.HashMap with its tree bins and their removals, trim, compaction, the writers,
+"""The CPU side under sanitizers (`-m "not gpu"`): the C++ host code (csrc/host/reads_io.cpp: readers on
+several threads; csrc/host/envfinder.cpp: the replay of java.util.HashMap with its tree bins and their removals, trim, compaction, the writers,
 environment-finder-multi) built with AddressSanitizer + UndefinedBehaviorSanitizer runs every test of tests/test_host_cpp.py
 and the joins of tests/test_multi_string_model.py; the parallel ingest runs under ThreadSanitizer; and the C oracle
 (oracle/mc_oracle.c, its multi-threaded counting port included) runs the golden tests as an ASan build loaded into a child

@@ -250,3 +250,30 @@ def test_the_designed_probes():
     line_start = text.rfind(b"\n", 0, c.probe) + 1
     assert c.probe == 100 and line_start == len(b"\n".join(lines[:6])) + 1 and lines[6][:1] == b"+" and lines[7][:1] == b"@"
     assert c.e == len(b"\n".join(lines[:8])) + 1 and tc.record_start(text, True, c.e - len(lines[7])) == c.e
+
+
+@pytest.fixture(scope="module")
+def hosttest():
+    import os
+    from metacherchant_amd import build
+    build.build_host()
+    assert os.path.exists(build.HOSTTEST)
+    return build.HOSTTEST
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_plain_chunks_is_the_model(name, hosttest):
+    """`mc_hosttest cuts` (csrc/host/reads_io.cpp plain_chunks, the one cut rule of the library, the CLI's WholeReadsSource and
+    mc_hosttest) prints cut_positions' chunks, at the designed chunk sizes and the switch's default (the small texts: the default's
+    one chunk says nothing more about a text of megabytes)."""
+    import subprocess
+    text, fastq, _ = CASES[name]
+    chunks = tc._chunks(text) + ([None] if name != tc.LARGE else [])
+
+    def run(path):
+        return {c: subprocess.check_output([hosttest, "cuts", path] + ([] if c is None else [str(c)]), text=True) for c in chunks}
+    got = tc._with_file(text, fastq, run)
+    for c in chunks:
+        want = [(b, e) for b, e, _ in tc.cut_positions(text, fastq, c)]
+        assert [tuple(int(x) for x in line.split()) for line in got[c].splitlines()] == want, (name, c)
+        assert want[0][0] == 0 and want[-1][1] == len(text)

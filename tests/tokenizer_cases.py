@@ -2,7 +2,7 @@
 edges, line lengths around the 64-lane stretch, output offsets at every residue of the 32-base word, FASTQ pieces that start at
 lane 0 with and without a good base carried in, records longer than the WavePacker holds, more lines than one round of k_scan_one
 scans -- and the chunk sizes that cut them.  The reads come from oracle/host_oracle.py (read_fasta_reads / read_fastq_reads: the
-reference); cuts() restates the driver's cut loop and plain_record_start (csrc/host/envfinder.cpp) and says what every chunk holds.
+reference); cuts() restates the drivers' cut rule and plain_record_start (csrc/host/reads_io.cpp plain_chunks) and says what every chunk holds.
 tests/test_tokenizer_cases_model.py checks that the texts hold what they are for; tests/test_gpu_tokenizer_edges.py holds the
 kernels to them."""
 import collections
@@ -23,7 +23,7 @@ WORD = 32           # csrc/tokenizer_device.h:121  bases per packed 64-bit word
 WP_WORDS = 65       # csrc/tokenizer_device.h:89  LDS words of a WavePacker
 FLUSH = WP_WORDS * WORD  # csrc/tokenizer_device.h:118  put() flushes when the next stretch would pass 2080 bases
 DEFAULT_CHUNK = 1 << 28  # csrc/switches.h:30  MC_TOKENIZER_CHUNK_BYTES (64 B .. 1.5 GB)
-MIN_CHUNK = 64           # csrc/switches.h:68
+MIN_CHUNK = 64           # csrc/switches.h  tokenizer_chunk_bytes_of
 
 LARGE = "fa_scan_rounds"
 SEED = 20241020
@@ -96,7 +96,7 @@ def fq_records(text):
 
 
 def record_start(text, fastq, q):
-    """plain_record_start (csrc/host/envfinder.cpp): the first record start at or behind the line that byte q - 1 ends or lies in"""
+    """plain_record_start (csrc/host/reads_io.cpp): the first record start at or behind the line that byte q - 1 ends or lies in"""
     end = len(text)
 
     def next_line(s):
@@ -130,7 +130,8 @@ def record_start(text, fastq, q):
 
 
 def cut_positions(text, fastq, chunk):
-    """the loop that builds `cuts` in mc_add_reads_file: (b, e, probe)"""
+    """plain_chunks (csrc/host/reads_io.cpp) with the chunk size as MC_TOKENIZER_CHUNK_BYTES gives it (csrc/switches.h tokenizer_chunk_bytes_of;
+    None: unset): (b, e, probe)"""
     chunk = DEFAULT_CHUNK if chunk is None else min(max(int(chunk), MIN_CHUNK), 3 << 29)
     out, b, end = [], 0, len(text)
     while b < end:

@@ -1,4 +1,4 @@
-"""DnaQReader (csrc/host/envfinder.cpp) restated in Python: the text of a FASTQ / FASTA file in, every read whole with a code and a phred
+"""DnaQReader (csrc/host/reads_io.cpp) restated in Python: the text of a FASTQ / FASTA file in, every read whole with a code and a phred
 a base out -- what the classifying tools read their -r files with, and what mc_tokenize_whole has to give on the device.  The reader
 restates readDnaQLazy of the reference (itmo!/io/ReadersUtils.java:185-215, FastqReader.java:53-82, FastaWithNsReader,
 DnaQBuilder.java:32-45).  tests/test_whole_reads_model.py holds this model to the C++ reader (mc_hosttest dnaq); tests/test_gpu_whole_reads.py
