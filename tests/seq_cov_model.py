@@ -107,8 +107,9 @@ def store_coverage(codes, offsets, k, mode, table, wk=None):
     out = np.zeros((len(offsets) - 1, 2), dtype=np.uint64)
     csum = np.concatenate([[0], np.cumsum(cov)])
     bsum = np.concatenate([[0], np.cumsum(cov > 0)])
-    for s in range(len(offsets) - 1):
-        b, e = int(offsets[s]), int(offsets[s + 1])
-        if e - b >= k:
-            out[s] = (csum[e - k + 1] - csum[b], bsum[e - k + 1] - bsum[b])
+    off = np.asarray(offsets).astype(np.int64)
+    b, e = off[:-1], off[1:]
+    has = e - b >= k  # (a sequence shorter than k has no window)
+    out[has, 0] = csum[e[has] - k + 1] - csum[b[has]]
+    out[has, 1] = bsum[e[has] - k + 1] - bsum[b[has]]
     return out
