@@ -97,8 +97,9 @@ HOSTDIR = os.path.join(CSRC, "host")
 HOST_FLAGS = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")]
 
 
-# what every host program is made of beside its own units: the readers of read files (the library's too) and the rest of the host side
-HOST_CORE = ["reads_io", "envfinder"]
+# what every host program is made of beside its own units: the readers of read files (the library's too), the replay of the JDK, the
+# picture of a subgraph, environment-finder's host side and environment-finder-multi's
+HOST_CORE = ["reads_io", "java_replay", "picture", "envfinder", "multi"]
 
 
 def _host_sources(suffix):

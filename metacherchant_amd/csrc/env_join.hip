@@ -1,6 +1,6 @@
 // libmcgpu.so, the environment join: what environment-finder-multi needs of several graph.txt files at once (include/mcgpu.h
 // mc_env_join*; src/algo/MultiSequenceCalculator.java:51-100, src/io/writers/GFAWriterMulti.java, EnvironmentFinderMultiMain.java:104-170,
-// which csrc/host/envfinder.cpp environment_finder_multi restates on strings and env_join_host on packed keys).  context.h lists the
+// which csrc/host/multi.cpp environment_finder_multi restates on strings and env_join_host on packed keys).  context.h lists the
 // other units.
 //
 // n entries make 2n oriented rows: row 2e is entry e's k-mer as given, row 2e + 1 its reverse complement.  A row has a 64-bit mask of

@@ -1,91 +1,23 @@
-// Host side of the environment-finder path above the C ABI: seed reading, read ingest (the
-// readers' N policy + 2-bit packing), runTrimPaths, the subgraph map, unitig compaction and the
-// writers.  It mirrors the reference's classes (names below) so that the output files are
-// byte-identical; the k-mer table and the BFS themselves live behind include/mcgpu.h.
+// Host side of the environment-finder path above the C ABI: seed reading, runTrimPaths, the subgraph map and the writers of
+// environment-finder's files, with the cutReads writer of the assembler-finder.  It mirrors the reference's classes (names below)
+// so that the output files are byte-identical; the k-mer table and the BFS themselves live behind include/mcgpu.h.  What restates
+// the JDK is java_replay.h, the merge into unitigs picture.h, environment-finder-multi multi.h: included here for the units
+// that want the whole host side.
 //
 // Citations: src/... = reference src/; itmo!/x = ru/ifmo/genetics/x in lib/itmo-assembler-src.jar.
 #pragma once
 #include <cstdint>
 #include <cstdio>
-#include <deque>
 #include <functional>
-#include <map>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
+#include "java_replay.h"
+#include "multi.h"
+#include "picture.h"
 #include "reads_io.h"  // Error, code_of, the readers of read files
 
 namespace mch {
-
-// ---- DNA strings (itmo!/dna/DnaTools.java:31,46-64,131-145; src/utils/StringUtils.java:8-41)
-std::string reverse_complement(const std::string &s);
-std::string normalize_dna(const std::string &s);  // ASCII-lexicographic min of (s, rc(s))
-std::vector<std::string> neighbors_by_dir(int dir, const std::string &kmer);  // A,G,C,T order; dir 0 interleaves L,R
-void pack_kmer(const std::string &s, uint64_t *hi, uint64_t *lo);
-std::string unpack_kmer(uint64_t hi, uint64_t lo, int k);
-
-// ---- treeified bins of java.util.HashMap (JDK 8 HashMap.TreeNode).  A bin's iteration order is
-// its nodes' next-chain, kept here as a vector of entry ids; the red-black tree over the same nodes decides where a new
-// node is linked in: treeify() builds the tree in chain order and moves its root to the front (moveRootToFront),
-// put() is putTreeVal (the new node goes right behind its tree parent, then balanceInsertion, then the root to the front).
-// dir(x, p) = which way x goes below p: by the (signed) spread hash, then String.compareTo -- < 0 left, > 0 right.
-class JavaTreeOrder {
-public:
-    explicit JavaTreeOrder(std::function<int(uint32_t, uint32_t)> dir) : dir_(std::move(dir)) {}
-    void treeify(std::vector<uint32_t> &chain);
-    void put(std::vector<uint32_t> &chain, uint32_t id);
-    // removeTreeNode + balanceDeletion: the chain only loses `id` (with `movable` -- HashMap.remove; an iterator's remove, which
-    // is what retainAll uses, passes false -- the root then moves to the front).  Returns true when the bin untreeifies (the tree
-    // was too small BEFORE the removal) or is empty: the caller forgets the tree and keeps the chain as a plain list.
-    bool remove(std::vector<uint32_t> &chain, uint32_t id, bool movable);
-    void forget(const std::vector<uint32_t> &chain) { for (uint32_t id : chain) t_.erase(id); }
-
-private:
-    static constexpr uint32_t NIL = 0xFFFFFFFFu;
-    struct Node { uint32_t parent = NIL, left = NIL, right = NIL; bool red = false; };
-    uint32_t rotate_left(uint32_t root, uint32_t p);
-    uint32_t rotate_right(uint32_t root, uint32_t p);
-    uint32_t balance_insertion(uint32_t root, uint32_t x);
-    uint32_t balance_deletion(uint32_t root, uint32_t x);
-    static void root_to_front(std::vector<uint32_t> &chain, uint32_t root);
-    std::function<int(uint32_t, uint32_t)> dir_;
-    std::unordered_map<uint32_t, Node> t_;
-};
-
-// ---- java.util.HashMap<String,Integer> iteration order (JDK 8)
-class JavaHashMap {
-public:
-    JavaHashMap();
-    void put(const std::string &key, int value);  // new keys go to the tail of their bin; existing keep their place
-    bool contains(const std::string &key) const { return index_.count(key) != 0; }
-    int get(const std::string &key) const;         // throws if absent
-    bool find(const std::string &key, int *value) const;
-    void remove(const std::string &key, bool movable = false);
-    size_t size() const { return size_; }
-    // The order of a treeified bin is replayed node for node (JavaTreeOrder), removals included (removeTreeNode): nothing sets
-    // the flag any more; it stays for callers that ask.
-    bool treeified() const { return order_unknown_; }
-    size_t bins_treeified() const { return n_treeified_; }  // bins that were treeified at some point (tests)
-    template <typename F>
-    void for_each(F &&f) const
-    {
-        for (const auto &bin : bins_)
-            for (uint32_t e : bin) f(entries_[e].key, entries_[e].value);
-    }
-
-private:
-    struct Entry { std::string key; int value; uint32_t hash; };
-    void resize();
-    int tree_dir(uint32_t x, uint32_t p) const;
-    std::deque<Entry> entries_;
-    std::vector<std::vector<uint32_t>> bins_;  // (a treeified bin's vector is its next-chain)
-    std::vector<char> is_tree_;
-    std::unordered_map<std::string, uint32_t> index_;
-    JavaTreeOrder tree_;
-    size_t cap_ = 16, size_ = 0, n_treeified_ = 0;
-    bool order_unknown_ = false;
-};
 
 // ---- src/io/RichFastaReader.java:38-77 (+ DnaQ(String,0).toString(): N/n/. -> 'A', itmo!/dna/DnaQ.java:21-30)
 struct SeedFile {
@@ -93,56 +25,8 @@ struct SeedFile {
 };
 SeedFile read_seed_fasta(const std::string &path);  // throws Error when the file cannot be opened
 
-// String.format("%.2f", x) for a double: HALF_UP on the shortest decimal that reads back as x (Java's FormattedFloatingDecimal)
-std::string java_format_2f(double x);
-// Double.toString as JDK 19 and later document it: the shortest decimal that reads back as x, at least one digit after the point,
-// plain notation for 10^-3 <= |x| < 10^7 and d.dddE[-]n outside it (seq-cov's columns, src/tools/SequenceCoverage.java:184)
-std::string java_double_to_string(double x);
-
-// ---- 2-bit packed k-mers (k <= 63): base i of the string is bits 2(k-1-i)+1..2(k-1-i), codes A0 G1 C2 T3,
-// the layout of mc_bfs_result's hi/lo words (include/mcgpu.h)
-typedef unsigned __int128 kmer_t;
-kmer_t pack_kmer128(const std::string &s);
-inline std::string unpack_kmer128(kmer_t v, int k) { return unpack_kmer((uint64_t)(v >> 64), (uint64_t)v, k); }
-kmer_t reverse_complement128(kmer_t v, int k);
-kmer_t normalize128(kmer_t v, int k);  // the packed form of normalize_dna(string)
-
-// java.util.HashMap<String, Integer> over k-mer strings held packed: the same bins, resize points, in-bin
-// order and treeify detection as JavaHashMap, with String.hashCode() evaluated on the characters the
-// packed key stands for.  Entries are chained per bin the way the JDK chains them.
-class JavaKmerMap {
-public:
-    explicit JavaKmerMap(int k);
-    int put(kmer_t key, int value);   // entry index; an existing key keeps its place and gets the value
-    int find_entry(kmer_t key) const;  // -1 when absent
-    int value_at(int e) const { return entries_[(size_t)e].value; }
-    void remove(kmer_t key, bool movable = false);
-    size_t size() const { return size_; }
-    size_t n_entries() const { return entries_.size(); }  // removed ones included: bound of the entry indices
-    bool treeified() const { return order_unknown_; }  // (see JavaHashMap::treeified)
-    size_t bins_treeified() const { return n_treeified_; }
-    template <typename F>
-    void for_each(F &&f) const  // f(key, value, entry index) in HashMap iteration order
-    {
-        for (uint32_t h : head_)
-            for (uint32_t e = h; e != NIL; e = entries_[e].next) f(entries_[e].key, entries_[e].value, (int)e);
-    }
-
-private:
-    static constexpr uint32_t NIL = 0xFFFFFFFFu;
-    struct Entry { kmer_t key; int value; uint32_t hash, next; };
-    uint32_t hash_of(kmer_t key) const;
-    void resize();
-    int tree_dir(uint32_t x, uint32_t p) const;
-    void relink(size_t bin, const std::vector<uint32_t> &chain);  // head_/tail_/next of a bin from its chain
-    int k_;
-    std::vector<Entry> entries_;
-    std::vector<uint32_t> head_, tail_;
-    std::unordered_map<size_t, std::vector<uint32_t>> tree_bins_;  // treeified bins: their next-chains
-    JavaTreeOrder tree_;
-    size_t cap_ = 16, size_ = 0, n_treeified_ = 0;
-    bool order_unknown_ = false;
-};
+void write_file(const std::string &path, const std::string &text);  // mkdirs + write
+bool read_lines(const std::string &path, std::vector<std::string> *lines);  // without their ends (\n, \r\n); false when the file cannot be opened
 
 // ---- one runBfs pass as delivered by mc_bfs_batch (or by a dump file in the CPU tests)
 struct BfsPass {
@@ -152,29 +36,6 @@ struct BfsPass {
     std::vector<int16_t> cov;
     std::vector<uint8_t> last;
 };
-
-// ---- initializeStructures + doMerge (src/algo/OneSequenceCalculator.java:387-451) over oriented k-mers in node order: entry e makes
-// node 2e (kmers[e]) and node 2e + 1 (its reverse complement); two nodes merge only when cls is equal for their entries.
-struct PictureNode {
-    std::string sequence;
-    bool deleted = false;
-    int rc = 0;                  // index of the reverse-complement node
-    std::vector<int> neighbors;  // successors of rc(this), in node-array order
-};
-// What the loop ends in, from link analysis: the fields of mc_unitigs_result (include/mcgpu.h has the definitions), owned.
-struct UnitigsResult {
-    std::vector<uint8_t> deg;
-    std::vector<uint32_t> nbr, first, last_rc, irregular;
-    std::vector<uint64_t> base_offsets, bases;
-};
-// fills a result for the k-mers and classes given (mc_unitigs on a context, or unitigs_by_links); throws Error
-using Compactor = std::function<void(int k, const std::vector<kmer_t> &kmers, const std::vector<uint8_t> &cls, UnitigsResult &out)>;
-// the host's link analysis: no label is built before the chains are known.  The model of csrc/unitigs.hip.
-void unitigs_by_links(int k, const std::vector<kmer_t> &kmers, const std::vector<uint8_t> &cls, UnitigsResult &out);
-// Without a compactor: the reference's loop on labels, pass after pass over all nodes.  With one: the nodes are built from its result
-// and the same loop runs over the nodes of the irregular entries only.  Alive nodes, `deleted` and the neighbours lists come out
-// the same either way; what a deleted node keeps as label and rc depends on the loop's scan order and is never read.
-std::vector<PictureNode> make_picture(int k, const std::vector<kmer_t> &kmers, const std::vector<uint8_t> &cls, const Compactor *compact = nullptr);
 
 // ---- src/algo/OneSequenceCalculator.java (after the BFS) + src/algo/SingleNode.java +
 // src/io/writers/GFAWriter.java + src/io/writers/TSVWriter.java; with set_colours, src/algo/SeqEnvCalculator.java (after its BFS)
@@ -227,15 +88,7 @@ public:
     void write_all(const std::string &out_prefix, int chunk_length, const Compactor *compact = nullptr);
 
 private:
-    struct Node {
-        std::string sequence;
-        int id;
-        bool is_gene, deleted = false;
-        int rc;                      // index of the reverse-complement node
-        std::vector<int> neighbors;  // successors of rc(this), in node-array order
-        Colour colour = NO_COLOUR;
-    };
-    std::string node_id(const Node &n) const;
+    std::string node_id(size_t i) const;  // SingleNode's label: the smaller id of the node and its reverse complement, from 1
     int k_;
     std::vector<std::string> genes_;
     std::vector<kmer_t> gene_kmers_;  // sorted: every k-window of the gene sequences, for isGeneNode
@@ -243,10 +96,9 @@ private:
     bool d_treeified_ = false;
     bool coloured_ = false;
     std::vector<Colour> colours_;  // by the subgraph's iteration order (set_colours)
-    std::vector<Node> nodes_;
+    std::vector<PictureNode> nodes_;  // as make_picture leaves them: a node's id is its index, its entry index / 2
+    std::vector<uint8_t> is_gene_;    // by entry (create_picture)
 };
-
-void write_file(const std::string &path, const std::string &text);  // mkdirs + write
 
 // ---- the environment-assembler-finder's cutReads<i>.fasta (src/algo/ReadsFilter.java:36-41,58-66): created empty with its
 // directory, then `>i|n` and the bases as DnaQ.toString() prints them for every kept read of file i, n counting them from 1
@@ -267,51 +119,5 @@ private:
     uint64_t kept_ = 0;
     void flush();
 };
-
-// ---- --tool environment-finder-multi: src/tools/EnvironmentFinderMultiMain.java,
-// src/algo/MultiSequenceCalculator.java, src/algo/MultiNode.java, src/io/writers/GFAWriterMulti.java,
-// src/io/graph/DeBruijnGraphUtils.java.  Joins the graph.txt / env.txt files of several
-// environment-finder runs into one coloured graph and two distance tables: on strings as the reference does
-// (environment_finder_multi), or on packed k-mers with hooks for the join and the compaction (environment_finder_multi_packed).
-struct MultiResult {
-    std::string seqs_fasta, graph_gfa, gene_fasta, jacard_sym, jacard_alt;  // <output>/seqs.fasta, graph.gfa, gene.fasta, Jacard_*.txt
-    std::vector<std::string> log;                                            // "INFO ..." / "WARN ..." lines, in order
-};
-MultiResult environment_finder_multi(const std::vector<std::string> &env_paths, const std::string &seq_path, int gene_id);
-
-// ---- the same tool on packed k-mers.  The join of the graph files (which graphs hold a k-mer, the KC column's depths, is it a gene
-// k-mer, the sums of the two distance tables) is a Joiner's work and the merge loop a Compactor's: include/mcgpu.h mc_env_join has the
-// definitions of the join's fields, which are EnvJoinResult's.
-struct EnvJoinInput {
-    int k = 0;
-    std::vector<kmer_t> entries;                       // entry e: nodes 2e (as given) and 2e + 1 (its reverse complement)
-    std::vector<kmer_t> rec_kmers;                     // the graphs' records one graph after another, as the files spell them
-    std::vector<int32_t> rec_depth;
-    std::vector<uint64_t> graph_offsets;               // n_graphs + 1
-    std::vector<uint64_t> gene_words;                  // the gene packed as reads are, gene_len bases
-    uint64_t gene_len = 0;
-    size_t n_graphs() const { return graph_offsets.empty() ? 0 : graph_offsets.size() - 1; }
-};
-struct EnvJoinResult {
-    std::vector<uint64_t> member;
-    std::vector<uint8_t> is_gene;
-    std::vector<int64_t> kc;
-    std::vector<uint32_t> diff, diff_alt, uni;  // n_graphs x n_graphs, row i column j at i * n_graphs + j
-};
-// fills a result for the input given (mc_env_join on a context, or env_join_host); throws Error
-using Joiner = std::function<void(const EnvJoinInput &in, EnvJoinResult &out)>;
-// the host's join on packed keys, from the definitions.  The model of csrc/env_join.hip.
-void env_join_host(const EnvJoinInput &in, EnvJoinResult &out);
-// What the packed path cannot represent (what() names it): k above 63, a k-mer with a character outside upper-case ACGT, more than
-// 64 graphs, more than 256 merge classes.  environment_finder_multi takes those inputs.
-struct MultiUnpacked : Error {
-    using Error::Error;
-};
-// The files and log lines of environment_finder_multi, byte for byte, with no string k-mer on the way.  n_entries: where the number of
-// entries goes once it is known (NULL: nowhere).
-MultiResult environment_finder_multi_packed(const std::vector<std::string> &env_paths, const std::string &seq_path, int gene_id, const Joiner &join,
-                                            const Compactor &compact, size_t *n_entries = nullptr);
-void write_multi(const MultiResult &r, const std::string &output_dir);
-std::string java_format_6_2f(float x);  // String.format("%6.2f", x)
 
 }  // namespace mch

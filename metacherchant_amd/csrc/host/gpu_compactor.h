@@ -1,12 +1,12 @@
-// mc_unitigs (include/mcgpu.h) as a Compactor of envfinder.h: what `metacherchant --compact gpu` hands to Environment::create_picture,
-// and what mc_unitigs_bench times.  envfinder.{h,cpp} themselves stay free of the library (mc_hosttest builds them without it).
+// mc_unitigs (include/mcgpu.h) as a Compactor of picture.h: what `metacherchant --compact gpu` hands to Environment::create_picture,
+// and what mc_unitigs_bench times.  picture.{h,cpp} themselves stay free of the library (mc_hosttest builds them without it).
 #pragma once
 #include <cstring>
 #include <numeric>
 #include <string>
 #include <vector>
 
-#include "envfinder.h"
+#include "picture.h"
 #include "mcgpu.h"
 
 namespace mch {

@@ -1,10 +1,10 @@
-// mc_env_join (include/mcgpu.h) as a Joiner of envfinder.h: what `metacherchant --tool environment-finder-multi --join gpu` hands to
-// environment_finder_multi_packed.  envfinder.{h,cpp} themselves stay free of the library (mc_hosttest builds them without it).
+// mc_env_join (include/mcgpu.h) as a Joiner of multi.h: what `metacherchant --tool environment-finder-multi --join gpu` hands to
+// environment_finder_multi_packed.  multi.{h,cpp} themselves stay free of the library (mc_hosttest builds them without it).
 #pragma once
 #include <string>
 #include <vector>
 
-#include "envfinder.h"
+#include "multi.h"
 #include "mcgpu.h"
 
 namespace mch {

@@ -1,6 +1,6 @@
 // The host readers of read files (no HIP): packed reads batch by batch from FASTA / FASTQ / binq, plain, .gz or .bz2 (load_reads_file);
 // an uncompressed file mapped for the device tokeniser, its chunks and the serial parser for a chunk the device declines; whole reads with
-// their qualities (DnaQReader).  The one host unit libmcgpu.so links; envfinder.h, which says what the citations mean, includes it.
+// their qualities (DnaQReader).  The one host unit libmcgpu.so links; java_replay.h, which says what the citations mean, includes it.
 #pragma once
 #include <cstdint>
 #include <functional>

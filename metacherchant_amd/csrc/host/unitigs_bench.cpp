@@ -1,5 +1,5 @@
 // mc_unitigs_bench: times the unitig compaction of one synthetic environment both ways through the one entry the tools use,
-// make_picture (envfinder.h): without a compactor (the reference's loop on labels, `--compact host`) and with mc_unitigs as the
+// make_picture (picture.h): without a compactor (the reference's loop on labels, `--compact host`) and with mc_unitigs as the
 // compactor (`--compact gpu`: the k-mers up, the result back, the nodes built from it, the loop over the irregular entries).
 // scripts/unitigs_bench.py runs it and takes the medians; DESIGN.md 3.12 has the figures.
 //

@@ -1,6 +1,6 @@
 // libmcgpu.so, the unitigs unit: the state that the reference's unitig compaction ends in, by link analysis instead of merges
 // (include/mcgpu.h mc_unitigs*; src/algo/OneSequenceCalculator.java:387-451 initializeStructures + doMerge, which
-// csrc/host/envfinder.cpp Environment::create_picture restates).  context.h lists the other units.
+// csrc/host/picture.cpp make_picture restates).  context.h lists the other units.
 //
 // n entries make N = 2n nodes: node 2e spells entry e's k-mer, node 2e + 1 its reverse complement.  One thread a node (or an
 // entry) in every kernel, no LDS, and nothing that depends on the order in which threads run:

@@ -1,4 +1,4 @@
-"""Unitig compaction of one environment, the host's loop against mc_unitigs, both through make_picture (csrc/host/envfinder.cpp), the
+"""Unitig compaction of one environment, the host's loop against mc_unitigs, both through make_picture (csrc/host/picture.cpp), the
 entry every graph-writing tool compacts through: `--compact host` is make_picture without a compactor (the reference's loop on
 labels, the parent's code), `--compact gpu` make_picture with mc_unitigs as the compactor (the k-mers split into words and copied up,
 the passes, the result copied back and into vectors, the nodes built from it, the loop over the irregular entries).  Both are

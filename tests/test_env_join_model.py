@@ -1,5 +1,5 @@
 """The packed path of environment-finder-multi on the CPU: `mc_hosttest multi-packed` (environment_finder_multi_packed with env_join_host and
-unitigs_by_links, csrc/host/envfinder.cpp) must write what `mc_hosttest multi` (the string function) and oracle/host_oracle.py write, byte
+unitigs_by_links; csrc/host/multi.cpp, picture.cpp) must write what `mc_hosttest multi` (the string function) and oracle/host_oracle.py write, byte
 for byte, and tests/env_join_model.py -- mc_env_join's definitions on dicts of strings -- must give the oracle's Jaccard tables and the
 KC and colour of every S line.  Designed graph files: env_join_model.designed_case says what is in them."""
 import os
@@ -170,7 +170,9 @@ def test_last_line_wins_in_kc(hosttest, tmp_path):
 
 @pytest.mark.parametrize("what", ["k70", "lower", "g65", "classes"])
 def test_unpacked_inputs_are_named(hosttest, tmp_path, what):
-    """what the packed path cannot represent ends it with a reason, and the string function takes the same input"""
+    """what the packed path cannot represent ends it with a reason, and the string function takes the same input: its five files and
+    its log are the oracle's, byte for byte (k above 63, more than 64 graphs and more than 256 merge classes reach the tool's writer
+    through the string function alone)"""
     import random
     rng = random.Random(7)
     if what == "k70":
@@ -195,6 +197,11 @@ def test_unpacked_inputs_are_named(hosttest, tmp_path, what):
         assert a.returncode == 1 and "Incorrect nucleotide char" in a.stderr
     else:
         assert a.returncode == 0, a.stderr
+        want, log = ho.environment_finder_multi(envs, seq, None, 1)
+        got = read_files(tmp_path / "string")
+        for f in FILES:
+            assert got[f] == want[f], f
+        assert a.stdout.splitlines() == log
 
 
 def many_classes_case(k=21, G=9, n=300):

@@ -1,4 +1,4 @@
-"""`mc_hosttest unitigs`: the host's link analysis (csrc/host/envfinder.cpp unitigs_by_links) and make_picture with it leave, node
+"""`mc_hosttest unitigs`: the host's link analysis (csrc/host/picture.cpp unitigs_by_links) and make_picture with it leave, node
 for node, what the loop on labels leaves, and both say what tests/unitigs_model.py says (no GPU)."""
 import subprocess
 

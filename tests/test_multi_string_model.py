@@ -1,6 +1,6 @@
 """A second, independent pin for `environment-finder-multi`.  CPU only.
 
-The reference ships no output of this tool, so the C++ host (`environment_finder_multi`, csrc/host/envfinder.cpp) and
+The reference ships no output of this tool, so the C++ host (`environment_finder_multi`, csrc/host/multi.cpp) and
 oracle/host_oracle.py were only ever compared with each other -- both written by this build, from the same reading of the
 Java.  Here a THIRD restatement, written straight from src/algo/MultiSequenceCalculator.java:51-159,
 src/algo/MultiNode.java, src/io/writers/GFAWriterMulti.java:39-133, src/io/graph/DeBruijnGraphUtils.java:13-27 and

@@ -64,7 +64,7 @@ def test_store_coverage_is_the_sum_of_its_windows():
 
 
 def test_the_cpp_double_to_string_equals_the_model(tmp_path):
-    """csrc/host/envfinder.cpp java_double_to_string through `mc_hosttest dtoa`: the pins, 100 000 ratios a / n as seq-cov forms them
+    """csrc/host/java_replay.cpp java_double_to_string through `mc_hosttest dtoa`: the pins, 100 000 ratios a / n as seq-cov forms them
     (a < 2^40, 1 <= n < 2^31) and 20 000 random bit patterns, in one process call"""
     import struct
     import subprocess
