@@ -91,6 +91,22 @@ def test_cycles(k):
     assert got[1].sum() == 1 and got[-1].all()
 
 
+@pytest.mark.parametrize("k", [21, 41])
+@pytest.mark.parametrize("name", tm.NEW_SHAPES)
+def test_deeper_shapes(name, k):
+    """nests of forks that take more than three phases, nodes with three and four ways on, arms that rejoin through PASS pointers of
+    different lengths beside a second stop, two cycles through one node, forks that stay OPEN for good, a dead tip beside a closed
+    cycle, a KEPT stop found through a long PASS chain (tests/test_trim_paths_model.py holds each shape to the branches of
+    k_tp_classify it is named for): by right steps as built, by left steps as the reverse-complement twins, and dir = 0"""
+    kmers, last = tm.shape(name, k)
+    by_right = _check(k, kmers, last)
+    by_left = _check(k, tm.twin(kmers), last)
+    assert np.array_equal(by_right[1], by_left[-1]) and np.array_equal(by_right[-1], by_left[1]) and np.array_equal(by_right[0], by_left[0])
+    order = np.random.default_rng(len(kmers)).permutation(len(kmers))  # the same entries in shuffled order
+    shuffled = _check(k, [kmers[i] for i in order], [last[i] for i in order], dirs=(1,))
+    assert np.array_equal(shuffled[1], by_right[1][order])
+
+
 @pytest.mark.parametrize("k", [21, 32, 33])
 def test_self_loops(k):
     a = "A" * k

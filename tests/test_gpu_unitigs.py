@@ -76,6 +76,26 @@ def test_a_chain_of_70000_entries(k):
     _check(_ctx(k).unitigs(hi, lo, np.array(cls, dtype=np.uint8)), want)
 
 
+WORD_EDGE_CASES = [(k, g) for k in (5, 31, 32, 33, 63) for g in range(len(um.word_edge_groups(k)))]
+
+
+@pytest.mark.parametrize("odd_head", (False, True), ids=("even_head", "odd_head"))
+@pytest.mark.parametrize("k,group", WORD_EDGE_CASES, ids=["%d-%s" % (k, "_".join(map(str, um.word_edge_groups(k)[g]))) for k, g in WORD_EDGE_CASES])
+def test_unitig_lengths_at_word_edges(k, group, odd_head):
+    """k_ut_bases: the head's k-mer over one or two words, every other node's last base at word (rank + k - 1) >> 5: unitigs of a word
+    of bases, one less and one more, side by side (a base written a word late lands in the next unitig's first word), listed from an
+    even node (the k-mer as given) and from an odd one (its reverse complement).  Every length of 31, 32, 33, 63, 64, 65, 96, 97 that
+    has two entries at this k; at k = 5, where the 4-mers do not last for all of them at once, in six calls"""
+    groups = um.word_edge_groups(k)
+    assert sorted({n for g in groups for n in g} - {6}) == [n for n in um.WORD_EDGE_LENGTHS if n >= k + 1]  # (6: the short neighbour at k = 5)
+    kmers, cls, lengths = um.word_edge_chains(500 + k, k, odd_head, group)
+    want = um.link_analysis(kmers, cls, k)
+    assert [len(s) for s in want["seqs"]] == lengths == groups[group] and len(lengths) >= 2 and not want["irregular"]
+    assert all(h % 2 == (1 if odd_head else 0) for h in want["first"])
+    hi, lo = um.pack_kmers(kmers)
+    _check(_ctx(k).unitigs(hi, lo, np.array(cls, dtype=np.uint8)), want)
+
+
 def test_no_entries():
     r = _ctx(21).unitigs(np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint8))
     assert r["n_nodes"] == 0 and r["n_unitigs"] == 0 and r["n_irregular"] == 0 and r["base_offsets"].tolist() == [0]

@@ -80,3 +80,59 @@ def test_designed_shapes_by_hand():
     assert tm.kept_mask(kmers, last, +1).sum() == 1 and tm.kept_mask(kmers, last, -1).all()
     both = ["ACGGTCA", tm.revcomp("ACGGTCA")]  # x and its reverse complement: two unrelated entries
     assert tm.kept_mask(both, [1, 0], 0).tolist() == [1, 0]
+
+
+# ---- the restated phases of csrc/trim_paths.hip against runTrimPaths, and what the deeper shapes are named for
+
+@pytest.mark.parametrize("k", [21, 41])
+@pytest.mark.parametrize("name", tm.SHAPES)
+def test_the_phase_model_keeps_what_the_walk_keeps(name, k):
+    kmers, last = tm.shape(name, k)
+    for direction, entries in ((1, kmers), (-1, tm.twin(kmers)), (-1, kmers), (1, tm.twin(kmers))):
+        kept, phases, took = tm.phase_model(entries, last, direction)
+        assert np.array_equal(kept, tm.kept_mask(entries, last, direction)), (name, k, direction)
+        assert phases <= len(kmers) + 1
+    by_right, by_left = tm.phase_model(kmers, last, 1), tm.phase_model(tm.twin(kmers), last, -1)
+    # the twin is the same shape (its neighbours come in the opposite order of bases: which arm of two is the `rejoin` may differ)
+    assert np.array_equal(by_right[0], by_left[0]) and by_right[1] == by_left[1] and set().union(*by_right[2]) == set().union(*by_left[2])
+    if name in tm.SHAPE_MEETS:
+        phases, branches = tm.SHAPE_MEETS[name]
+        assert by_right[1] >= phases and branches <= set().union(*by_right[2]), (by_right[1], sorted(set().union(*by_right[2])))
+
+
+def test_all_branches_are_met_and_the_deep_nest_needs_more_than_three_phases():
+    met = set()
+    for name in tm.NEW_SHAPES:
+        met |= set().union(*tm.phase_model(*tm.shape(name, 21), 1)[2])
+    assert met == set(tm.BRANCHES)
+    assert tm.phase_model(*tm.shape("fork_nest_6", 21), 1)[1] > 3 and tm.phase_model(*tm.shape("chain", 21), 1)[1] == 2
+
+
+@pytest.mark.parametrize("k", [21, 41])
+def test_the_deeper_shapes_by_hand(k):
+    rng = np.random.default_rng(k)
+    for depth in (2, 3, 6):  # the stem, and one arm a level down to the live tip
+        kmers, last = tm.fork_nest(rng, k, depth)
+        assert len(kmers) == 5 + 3 * (2 ** (depth + 1) - 2) and sum(last) == 1
+        assert int(tm.kept_mask(kmers, last, 1).sum()) == 5 + 3 * depth
+    for width in (3, 4):
+        kmers, last, parts = tm.fan(rng, k, width)
+        kept = dict(zip(kmers, tm.kept_mask(kmers, last, 1)))
+        for p, (stem, arms) in enumerate(parts):
+            assert set(tm.right_neighbors(stem[-1])) & set(kmers) == {a[0] for a in arms} and len(arms) == width
+            assert all(kept[x] for x in stem) and [all(kept[x] for x in a) for a in arms] == [j == p for j in range(width)]
+            assert [any(kept[x] for x in a) for a in arms] == [j == p for j in range(width)]
+    kmers, last, xs = tm.rejoin_through_pass(rng, k)
+    kept = dict(zip(kmers, tm.kept_mask(kmers, last, 1)))
+    assert len(xs) == 24 and [kept[x] for x, variant in xs] == [1 if variant in (0, 1) else 0 for x, variant in xs]
+    assert {len(set(tm.right_neighbors(x)) & set(kmers)) for x, variant in xs} == {2, 3}
+    for with_last in (False, True):
+        for make in (tm.figure_eight, tm.open_triangle):
+            kmers, last = make(rng, k, with_last)
+            kept = tm.kept_mask(kmers, last, 1)
+            assert not kept.any() if not with_last else (kept.all() if make is tm.figure_eight else kept.sum() > 3 * k)
+    kmers, last = tm.dead_beside_cycle(rng, k)
+    assert not tm.kept_mask(kmers, last, 1).any() and not any(last)
+    kmers, last, (q, f) = tm.kept_through_pass(rng, k)
+    kept = dict(zip(kmers, tm.kept_mask(kmers, last, 1)))
+    assert kept[q] and kept[f] and sum(kept.values()) == 5 + (k + 40) + 1 + 4

@@ -236,6 +236,62 @@ def mixed_set(seed, k, chain_lengths=(1, 2, 3, 64, 65)):
     return kmers, [cls.get(min(w, rc(w)), 0) for w in kmers]
 
 
+def disjoint_chains(rng, ms, k):
+    """strings of m + k - 1 bases, one for every m of ms: no (k-1)-mer twice on either strand over all of them, so every string is one
+    regular chain on its own and no chain touches another (grown base by base; a dead end starts the string again)"""
+    used, out = set(), []
+    for m in ms:
+        for _ in range(2000):
+            s = "".join(rng.choice("ACGT") for _ in range(k - 1))
+            if s in used or s == rc(s):
+                continue
+            mine = {s, rc(s)}
+            while len(s) < m + k - 1:
+                for c in rng.sample("ACGT", 4):
+                    e = s[len(s) - (k - 2):] + c if k > 2 else c
+                    if e not in used and e not in mine and e != rc(e):
+                        s += c
+                        mine |= {e, rc(e)}
+                        break
+                else:
+                    break
+            if len(s) == m + k - 1:
+                used |= mine
+                out.append(s)
+                break
+        else:
+            raise AssertionError("no chain of %d entries at k = %d beside the others" % (m, k))
+    return out
+
+
+WORD_EDGE_LENGTHS = (31, 32, 33, 63, 64, 65, 96, 97)
+
+
+def word_edge_groups(k):
+    """The unitig lengths of WORD_EDGE_LENGTHS that exist at this k (a chain has m = length - k + 1 >= 2 entries), in groups that one call
+    can hold side by side.  From k = 31 on one group holds them all.  At k = 5 there are 240 4-mers that are not their own reverse
+    complement, and a chain of m entries takes m + 1 of them on either strand: 31, 32 and 33 fit together, every longer one stands in
+    a call of its own in front of a short neighbour -- 63, 64, 65 before one of 31, 32, 33, and 96 and 97 (186 and 188 4-mers) before
+    a chain of two entries."""
+    if k > 5:
+        return [[n for n in WORD_EDGE_LENGTHS if n - k + 1 >= 2]]
+    return [[31, 32, 33], [63, 31], [64, 32], [65, 33], [96, k + 1], [97, k + 1]]
+
+
+def word_edge_chains(seed, k, odd_head, group=0):
+    """Regular chains side by side whose unitigs have the lengths of word_edge_groups(k)[group]: a word of bases, one less, one more.
+    A base written a word late lands in the next unitig's first word.  Every chain's entries stand in string order, so it is listed
+    from its first entry's node: the entry as given (an even node) or, with odd_head, given as its reverse complement, so that the
+    listed head is the odd node.  The other entries are oriented at random.  Returns (kmers, cls, the unitig lengths)."""
+    rng = random.Random(seed + 17 * group)
+    lengths = word_edge_groups(k)[group]
+    kmers = []
+    for s in disjoint_chains(rng, [n - k + 1 for n in lengths], k):
+        w = windows(s, k)
+        kmers += [rc(w[0]) if odd_head else w[0]] + [x if rng.random() < 0.5 else rc(x) for x in w[1:]]
+    return kmers, [0] * len(kmers), lengths
+
+
 # ---- the packed forms
 
 def pack_kmers(kmers):
