@@ -607,6 +607,42 @@ int mc_trim_paths(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uin
 int mc_trim_paths_dev(mc_ctx *ctx, const uint64_t *d_hi, const uint64_t *d_lo, const uint8_t *d_last, uint64_t n, int dir,
                       uint8_t *d_kept, double *device_ms);
 
+/* ---- the walk order: what the fmt-visualizer's subgraph takes from KmerEnvCalculator.runBfs (src/algo/KmerEnvCalculator.java:60-76),
+ * for every component of one mc_components result at once.  k is the context's; its key mode and its table play no part, and the call
+ * is allowed before mc_finalize_counts.
+ * Input: mc_components_result's hi / lo / comp_offsets as they are: n = comp_offsets[n_components] oriented packed k-mers (hi may be
+ * NULL when k <= 32; bits above the k-mer are dropped), component c's members comp_offsets[c] .. comp_offsets[c + 1] - 1, the first of
+ * them its seed in the read's orientation.  A component is walked against its own members only.
+ * The rule: the queue starts as [seed]; popping x appends, for the eight allNeighbors of x (A, G, C, T, the left neighbour before the
+ * right one), every y whose canonical form is a member that has not been popped yet (x itself counts as not yet popped), then puts
+ * (canonical(x), count) and zeroes the count.  The queue has no visited set, so its length is not bounded by n; the call keeps at most
+ * two entries a member, which gives the same first pops in the same order and the same answer to "popped again" (DESIGN.md 3.18).
+ * Output: reached[c] members of component c are popped (all of them when the slice is connected); order[comp_offsets[c] + i],
+ * i < reached[c], is the member (relative to the slice) that is popped for the first time as the i-th, member 0 first, the places
+ * behind them are 0; twice[m] = 1 iff member m is popped more than once, so that its put value ends as 0.  levels, queue_entries
+ * (of the bounded queue) and wide_levels (levels that took the grid-wide kernels) are summed over the components; device_ms is the
+ * device time of the call (HIP events).  The result is a function of the input alone, whatever the flags.
+ * Errors: MC_EINVAL for null pointers (hi at k <= 32 excepted), unknown flags, n >= 2^30 (decided before hi and lo are read),
+ * comp_offsets that does not start at 0 or does not ascend strictly, or two members anywhere in the call that are the same k-mer or each
+ * other's reverse complement.  n_components == 0 is MC_OK with a zeroed result.  *out is zeroed on an error.  Free a result with
+ * mc_walk_order_free (NULL and zeroed results are allowed).  Device memory: at most 66 bytes a member, 90 once a level takes the wide path.
+ * mc_walk_order takes host pointers, mc_walk_order_dev device ones; the result's arrays are the library's host memory in both. */
+#define MC_WALK_ORDER_WIDE_ONLY 1u   /* tests only: every level by the grid-wide kernels */
+#define MC_WALK_ORDER_NARROW_8  2u   /* tests only: W = 8, so small inputs cross between the two paths many times */
+typedef struct {
+    uint64_t n_components, n_kmers;
+    uint64_t *reached;   /* per component: members the walk pops */
+    uint32_t *order;     /* per component slice: the first reached[c] entries are member numbers (relative to the slice) in first-pop order */
+    uint8_t *twice;      /* per member: 1 iff popped more than once */
+    uint64_t levels, queue_entries, wide_levels;
+    double device_ms;
+} mc_walk_order_result;
+int mc_walk_order(mc_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint64_t *comp_offsets, uint64_t n_components, uint32_t flags,
+                  mc_walk_order_result *out);
+int mc_walk_order_dev(mc_ctx *ctx, const uint64_t *d_hi, const uint64_t *d_lo, const uint64_t *d_comp_offsets, uint64_t n_components,
+                      uint32_t flags, mc_walk_order_result *out);
+void mc_walk_order_free(mc_walk_order_result *r);
+
 /* ---- the environment join: what environment-finder-multi takes from several graph.txt files at once (initializeStructures of
  * src/algo/MultiSequenceCalculator.java:51-100, the KC column of src/io/writers/GFAWriterMulti.java, printProbability of
  * src/tools/EnvironmentFinderMultiMain.java:104-170).  k is the context's; its key mode and its table play no part.

@@ -10,10 +10,11 @@ from .native import components, components_dev  # noqa: F401
 from .native import unitigs, unitigs_dev  # noqa: F401
 from .native import env_join, env_join_dev  # noqa: F401
 from .native import trim_paths, trim_paths_dev  # noqa: F401
+from .native import walk_order, walk_order_dev, WALK_ORDER_WIDE_ONLY, WALK_ORDER_NARROW_8  # noqa: F401
 from .native import tokenize_whole, tokenize_whole_dev, reads_append_dev  # noqa: F401
 from .native import render_fastq, render_fastq_dev, render_fastq_bound  # noqa: F401
 
 __all__ = ["native", "Context", "McError", "KEY_PACKED", "KEY_POLY", "KEY_FNV1A", "seq_coverage", "seq_coverage_dev", "kmer_presence",
            "kmer_presence_dev", "reads_in_set", "reads_in_set_dev", "components", "components_dev", "unitigs", "unitigs_dev",
-           "env_join", "env_join_dev", "trim_paths", "trim_paths_dev", "tokenize_whole", "tokenize_whole_dev", "reads_append_dev",
+           "env_join", "env_join_dev", "trim_paths", "trim_paths_dev", "walk_order", "walk_order_dev", "WALK_ORDER_WIDE_ONLY", "WALK_ORDER_NARROW_8", "tokenize_whole", "tokenize_whole_dev", "reads_append_dev",
            "render_fastq", "render_fastq_dev", "render_fastq_bound"]

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libmcgpu.so")
 CLI = os.path.join(LIBDIR, "metacherchant")
 
 # the library's units (csrc/context.h says what each holds), and the host readers the read-file entry points use
-HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip", "trim_paths.hip", "kmers_bin.hip", "render_fastq.hip",
+HIP_SOURCES = ["mcgpu.hip", "reads_file.hip", "walk.hip", "group.hip", "classify.hip", "last_copy.hip", "seq_cov.hip", "presence.hip", "reads_in_set.hip", "components.hip", "unitigs.hip", "env_join.hip", "whole_reads.hip", "trim_paths.hip", "kmers_bin.hip", "render_fastq.hip", "walk_order.hip",
                os.path.join("host", "reads_io.cpp")]
 # every header under csrc/ makes every object stale (a stale library would travel to the GPU box unnoticed)
 HIP_DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("host", "reads_io.h"), os.path.join("test", "bfs_old_race.h"),
@@ -152,6 +152,7 @@ def build_host(force=False, verbose=False):
 UNITIGS_BENCH = os.path.join(LIBDIR, "mc_unitigs_bench")
 TRIM_PATHS_BENCH = os.path.join(LIBDIR, "mc_trim_paths_bench")
 WHOLE_READS_BENCH = os.path.join(LIBDIR, "mc_whole_reads_bench")
+WALK_ORDER_BENCH = os.path.join(LIBDIR, "mc_walk_order_bench")
 
 
 def build_unitigs_bench(force=False, verbose=False):
@@ -163,6 +164,12 @@ def build_trim_paths_bench(force=False, verbose=False):
     """mc_trim_paths_bench (csrc/host/trim_paths_bench.cpp): the trim of one pass, the host's walk against mc_trim_paths, timed;
     scripts/trim_paths_bench.py runs it"""
     return _link_host(TRIM_PATHS_BENCH, ["trim_paths_bench"], force, verbose)
+
+
+def build_walk_order_bench(force=False, verbose=False):
+    """mc_walk_order_bench (csrc/host/walk_order_bench.cpp): the walk order of one component, the host's replay against mc_walk_order, timed;
+    scripts/walk_order_bench.py runs it"""
+    return _link_host(WALK_ORDER_BENCH, ["walk_order_bench"], force, verbose)
 
 
 def build_whole_reads_bench(force=False, verbose=False):

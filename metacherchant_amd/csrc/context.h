@@ -1,6 +1,6 @@
 // The library's context and what more than one unit of it needs (host side; private to libmcgpu.so, not include/mcgpu.h).
 //
-// The library is sixteen units, each defining and launching its own kernels:
+// The library is seventeen units, each defining and launching its own kernels:
 //   mcgpu.hip       the table, the key join, the counting pipeline, the context ABI, and the table work of the walk (solid table,
 //                   the check of its "absent" look-ups)
 //   reads_file.hip  the device tokeniser's driver, the upload pipeline that feeds it a file's chunks (tokenize_file_chunks: mc_group_add_reads_file
@@ -24,6 +24,8 @@
 //                   which stream them to and from a file in chunks; the scan of the tile counts comes from reads_file.hip
 //   render_fastq.hip mc_render_fastq*: the classifiers' FASTQ records as text, up to sixteen output streams a call, for --render gpu; the
 //                   scan of the per-block counts comes from reads_file.hip
+//   walk_order.hip  mc_walk_order*: the order in which runBfs pops every component's k-mers first and which it pops again, for the fmt-visualizer:
+//                   a queue of at most two entries a member, level by level, narrow levels in one workgroup's LDS and wide ones across the grid
 // multi_table.h is what seq_cov.hip and presence.hip share: one key's home slots in several tables, the probing behind them, and the
 // host's checks of a list of contexts; kmer_set.h what reads_in_set.hip, unitigs.hip and env_join.hip share: the key and hash of a call's exact
 // set (trim_paths.hip takes the hash alone).  A function below the "across units" line is what one unit lends another; everything else stays static in its unit.

@@ -129,6 +129,17 @@ struct Trimmer {
     }
 };
 
+// --replay: the order of the fmt-visualizer's walks over a phase's components, by the host's replay of the reference's queue (a
+// component a thread) or by one mc_walk_order call over all of them; `auto`, the default, takes the GPU for a phase of REPLAY_AUTO_MIN
+// k-mers or more, and below that the host with a cap: a component whose queue passes 64 entries a member + 4096 (the exact queue of
+// 780 random small components never passed 13.4 a member; a few bubbles in a row double it each) is abandoned and goes to the GPU.
+// REPLAY_AUTO_MIN is "never": on thin chains (one component of 10^4 to 10^6 k-mers of error-free reads, k = 31 and 63, medians of 5,
+// scripts/walk_order_bench.py, profiles/walk_order_bench.txt) the host's replay takes 5.6 ms / 74 .. 83 ms / 0.96 s
+// against the GPU way's 23 ms / 0.23 s / 2.3 s, call and copies included -- 2.3 us a level on the device, 0.6 .. 1 us a k-mer on the
+// host -- each time by far more than either spread: no measured size from which the whole phase is faster the device's way.  So `auto`
+// uses the device only behind the cap, for components that the host's queue cannot finish.
+constexpr uint64_t REPLAY_AUTO_MIN = ~0ull;
+
 // --kmers-io: the records of a <name>.kmers.bin by the host's loops (mc_save_kmers, mc_load_kmers) or by the kernels of csrc/kmers_bin.hip
 // with the file streamed in chunks beside them (mc_save_kmers_gpu, mc_load_kmers_gpu); `auto`, the default, takes the GPU from
 // KMERS_SAVE_AUTO_MIN keys in the table for a save, from KMERS_LOAD_AUTO_MIN records in the file for a load.

@@ -182,6 +182,40 @@ void Environment::add_puts(const std::vector<std::pair<kmer_t, int>> &puts)
     for (const auto &p : puts) subgraph_.put(normalize128(p.first, k_), p.second);
 }
 
+// (the fmt-visualizer's host replay; scripts/walk_order_bench.py times it)  KmerEnvCalculator.runBfs (:60-76) over one component: `canon` sorted, `count` beside it (zeroed here); the puts in pop order
+// (cap: `--replay auto` gives up once the queue holds more entries than that, *abandoned says so; 0: no cap)
+std::vector<std::pair<kmer_t, int>> replay_component_walk(int k, kmer_t seed, const std::vector<kmer_t> &canon, std::vector<int> &count,
+                                                          size_t cap, bool *abandoned)
+{
+    const kmer_t kmask = ((kmer_t)1 << (2 * k)) - 1;
+    const int top = 2 * (k - 1);
+    auto at = [&](kmer_t v) -> int {
+        const kmer_t c = normalize128(v, k);
+        const auto it = std::lower_bound(canon.begin(), canon.end(), c);
+        return it != canon.end() && *it == c ? (int)(it - canon.begin()) : -1;
+    };
+    std::vector<kmer_t> queue{seed};
+    std::vector<std::pair<kmer_t, int>> puts;
+    for (size_t head = 0; head < queue.size(); head++) {
+        if (cap && queue.size() > cap) {
+            *abandoned = true;
+            return {};
+        }
+        const kmer_t kmer = queue[head];
+        for (unsigned c = 0; c < 4; c++) {  // allNeighbors: A, G, C, T, the left neighbour before the right one
+            const kmer_t nb[2] = {((kmer_t)c << top) | (kmer >> 2), ((kmer << 2) & kmask) | c};
+            for (const kmer_t x : nb) {
+                const int e = at(x);
+                if (e >= 0 && count[(size_t)e] > 0) queue.push_back(x);
+            }
+        }
+        const int e = at(kmer);  // (a member: it was queued with a count above 0)
+        puts.emplace_back(kmer, count[(size_t)e]);
+        count[(size_t)e] = 0;  // addAndBound(key, -get)
+    }
+    return puts;
+}
+
 static inline void append_uint(std::string &out, unsigned long long v)
 {
     char buf[24];

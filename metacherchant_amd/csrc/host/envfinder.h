@@ -45,6 +45,12 @@ struct BfsPass {
 // does with trim, and what scripts/trim_paths_bench.py times.)
 void trim_pass(JavaKmerMap &d, const BfsPass &p, int k, const std::vector<uint8_t> *kept = nullptr);
 
+// The fmt-visualizer's host replay of KmerEnvCalculator.runBfs (:60-76) over one component: `canon` its canonical k-mers sorted,
+// `count` beside them (zeroed here), seed its first k-mer as the read has it; returns the puts in pop order.  The queue has no
+// visited set; with cap > 0 the replay gives up once the queue holds more entries than that, sets *abandoned and returns nothing.
+std::vector<std::pair<kmer_t, int>> replay_component_walk(int k, kmer_t seed, const std::vector<kmer_t> &canon, std::vector<int> &count,
+                                                          size_t cap = 0, bool *abandoned = nullptr);
+
 class Environment {
 public:
     Environment(int k, std::vector<std::string> gene_sequences);

@@ -64,6 +64,7 @@ const OptSpec FMT_SPECS[] = {
     {"output-dir", "o", 0}, {"input-dir", "i", 0}, {"ext", "ext", 0},
     {"work-dir", "w", 0}, {"available-processors", "p", 0}, {"memory", "m", 0}, {"continue", "c", 1}, {"force", nullptr, 1},
     {"verbose", "v", 1}, {"help", "h", 1}, {"tool", "t", 0}, {"device", nullptr, 0}, {"devices", nullptr, 0}, {"capacity-hint", nullptr, 0}, {"compact", nullptr, 0}, {"parse", nullptr, 0},
+    {"replay", nullptr, 0},
 };
 
 // --tool environment-assembler-finder: its parameters (EnvironmentAssemblerFinder.java:33-122) and the launch options
@@ -209,6 +210,10 @@ Options parse_args(int argc, char **argv)
         if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--trim-on takes host, gpu or auto, not '" + *v + "'");
         o.trim_on = *v;
         o.trim_on_given = true;
+    }
+    if (auto v = val("replay")) {
+        if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--replay takes host, gpu or auto, not '" + *v + "'");
+        o.replay = *v;
     }
     if (auto v = val("kmers-io")) {
         if (*v != "host" && *v != "gpu" && *v != "auto") throw Error("--kmers-io takes host, gpu or auto, not '" + *v + "'");
@@ -363,6 +368,10 @@ void usage()
     puts("                host: the reverse walk over the pass's hash map; gpu: mc_trim_paths on the tool's context, every pass; the files are");
     puts("                the same; default auto: the GPU for a pass of 10000 k-mers or more, the smallest size measured, where it already wins;");
     puts("                it does nothing without --trim; with --devices auto is host and gpu is refused)");
+    puts("                --replay host|gpu|auto (fmt-visualizer: who replays the walk's order over every component.  host: the reference's");
+    puts("                queue, a component a thread -- it has no visited set and does not end on components with many bubbles in a row;");
+    puts("                gpu: mc_walk_order over all components of a phase at once, at most two queue entries a k-mer; the files are the");
+    puts("                same; default auto: the host, and the GPU for the components whose host queue passes 64 entries a k-mer + 4096)");
     puts("                --parse host|gpu|auto (the classifiers, seq-cov, fmt-visualizer, environment-assembler-finder: who parses the whole reads of");
     puts("                -r / --read-file / the read filter.  host: one thread reads the records and the tool packs them; gpu: the text of an");
     puts("                uncompressed FASTA / FASTQ file is tokenised on the device and stays there for the kernels; the files are the same;");

@@ -48,6 +48,8 @@ struct Options {
     // --trim-on: who works out which k-mers --trim keeps (no counterpart in the reference; the files are the same)
     std::string trim_on = "auto";
     bool trim_on_given = false;
+    // --replay: who replays the order of the fmt-visualizer's walks (no counterpart in the reference; the files are the same)
+    std::string replay = "auto";
     // --kmers-io: who encodes / decodes the records of a <name>.kmers.bin (no counterpart in the reference; the files are the same)
     std::string kmers_io = "auto";
     bool kmers_io_given = false;

@@ -165,37 +165,10 @@ int run_recipient_visualiser(const Options &o)
 // --tool fmt-visualizer (src/tools/FMTVisualizer.java:223-317, src/algo/KmerEnvCalculator.java): for the donor, the pre-FMT and the
 // post-FMT reads in turn, one coloured GFA and one FASTA a connected component of the phase's graph.  The reference walks from every
 // window whose count is still above 0 and zeroes what it reaches; here mc_components gives the components with their seeds at once,
-// mc_kmer_presence the class tables of every member, and only what the walk's ORDER decides is replayed on the host, a component
+// mc_kmer_presence the class tables of every member, and only what the walk's ORDER decides is replayed, a component
 // at a time on -p threads (the reference cannot: every walk writes the one shared map): the FIFO without a visited set over the
-// component's own k-mer -> count map, which gives the order of the subgraph's puts and the coverage 0 of a k-mer popped twice.
-
-// KmerEnvCalculator.runBfs (:60-76) over one component: `canon` sorted, `count` beside it (zeroed here); the puts in pop order
-static std::vector<std::pair<kmer_t, int>> replay_component_walk(int k, kmer_t seed, const std::vector<kmer_t> &canon, std::vector<int> &count)
-{
-    const kmer_t kmask = ((kmer_t)1 << (2 * k)) - 1;
-    const int top = 2 * (k - 1);
-    auto at = [&](kmer_t v) -> int {
-        const kmer_t c = normalize128(v, k);
-        const auto it = std::lower_bound(canon.begin(), canon.end(), c);
-        return it != canon.end() && *it == c ? (int)(it - canon.begin()) : -1;
-    };
-    std::vector<kmer_t> queue{seed};
-    std::vector<std::pair<kmer_t, int>> puts;
-    for (size_t head = 0; head < queue.size(); head++) {
-        const kmer_t kmer = queue[head];
-        for (unsigned c = 0; c < 4; c++) {  // allNeighbors: A, G, C, T, the left neighbour before the right one
-            const kmer_t nb[2] = {((kmer_t)c << top) | (kmer >> 2), ((kmer << 2) & kmask) | c};
-            for (const kmer_t x : nb) {
-                const int e = at(x);
-                if (e >= 0 && count[(size_t)e] > 0) queue.push_back(x);
-            }
-        }
-        const int e = at(kmer);  // (a member: it was queued with a count above 0)
-        puts.emplace_back(kmer, count[(size_t)e]);
-        count[(size_t)e] = 0;  // addAndBound(key, -get)
-    }
-    return puts;
-}
+// component's own k-mer -> count map, which gives the order of the subgraph's puts and the coverage 0 of a k-mer popped twice
+// (replay_component_walk, envfinder.cpp) -- or, under --replay gpu | auto, mc_walk_order's bounded form of it for all components at once.
 
 static void fmt_phase(const Options &o, const std::string &name, const std::vector<std::string> &files, const std::vector<std::string> &classes,
                       const std::string &out_root)
@@ -266,11 +239,28 @@ static void fmt_phase(const Options &o, const std::string &name, const std::vect
     std::vector<uint8_t> mask(res.n_kmers);
     if (res.n_kmers) MC_CHECK(tables[0], mc_kmer_presence(tables, nt, res.hi, res.lo, res.n_kmers, mask.data()));
     const std::string out_dir = out_root + "/" + name;
+    // --replay: the walk's order by the host's queue, or by mc_walk_order (at most two queue entries a k-mer).  wo_at[c]: where
+    // component c's slice starts in the device's answer, or all ones for a component the host replays.
+    const bool all_gpu = o.replay == "gpu" || (o.replay == "auto" && res.n_kmers >= REPLAY_AUTO_MIN);
+    const bool capped = o.replay == "auto";
+    mc_walk_order_result wo{};
+    struct WoGuard {
+        mc_walk_order_result &r;
+        ~WoGuard() { mc_walk_order_free(&r); }
+    } wo_guard{wo};
+    std::vector<uint64_t> wo_at(res.n_components, ~0ull), wo_comp(res.n_components, 0);  // (wo_comp[c]: its number in that call)
+    if (all_gpu && res.n_components) {
+        MC_CHECK(G.c, mc_walk_order(G.c, res.hi, res.lo, res.comp_offsets, res.n_components, 0, &wo));
+        for (uint64_t c = 0; c < res.n_components; c++) { wo_at[c] = res.comp_offsets[c]; wo_comp[c] = c; }
+    }
+    std::vector<uint64_t> todo(res.n_components), abandoned;
+    for (uint64_t c = 0; c < res.n_components; c++) todo[c] = c;
     std::atomic<uint64_t> next{0};
     std::mutex err_mu;
     std::string err;
     auto work = [&] {
-        for (uint64_t c; (c = next.fetch_add(1)) < res.n_components;) {
+        for (uint64_t at; (at = next.fetch_add(1)) < todo.size();) {
+            const uint64_t c = todo[at];
             try {
                 const uint64_t a = res.comp_offsets[c], b = res.comp_offsets[c + 1];
                 std::vector<std::pair<kmer_t, uint64_t>> order;  // (canonical k-mer, member)
@@ -278,11 +268,31 @@ static void fmt_phase(const Options &o, const std::string &name, const std::vect
                 for (uint64_t i = a; i < b; i++) order.emplace_back(normalize128(((kmer_t)res.hi[i] << 64) | res.lo[i], o.k), i);
                 std::sort(order.begin(), order.end());
                 std::vector<kmer_t> canon;
-                std::vector<int> count;
-                for (const auto &e : order) { canon.push_back(e.first); count.push_back(res.cov[e.second]); }
-                const kmer_t seed = ((kmer_t)res.hi[a] << 64) | res.lo[a];
+                for (const auto &e : order) canon.push_back(e.first);
                 Environment env(o.k, {});
-                env.add_puts(replay_component_walk(o.k, seed, canon, count));
+                if (wo_at[c] != ~0ull) {
+                    // the first pops in order; a k-mer that is popped again ends with the 0 of its second put
+                    std::vector<std::pair<kmer_t, int>> puts;
+                    const uint64_t reached = wo.reached[wo_comp[c]];
+                    puts.reserve(reached);
+                    for (uint64_t i = 0; i < reached; i++) {
+                        const uint64_t m = wo.order[wo_at[c] + i];
+                        puts.emplace_back(((kmer_t)res.hi[a + m] << 64) | res.lo[a + m], wo.twice[wo_at[c] + m] ? 0 : (int)res.cov[a + m]);
+                    }
+                    env.add_puts(puts);
+                } else {
+                    std::vector<int> count;
+                    for (const auto &e : order) count.push_back(res.cov[e.second]);
+                    const kmer_t seed = ((kmer_t)res.hi[a] << 64) | res.lo[a];
+                    bool gave_up = false;
+                    const auto puts = replay_component_walk(o.k, seed, canon, count, capped ? 64 * (size_t)(b - a) + 4096 : 0, &gave_up);
+                    if (gave_up) {
+                        std::lock_guard<std::mutex> g(err_mu);
+                        abandoned.push_back(c);
+                        continue;
+                    }
+                    env.add_puts(puts);
+                }
                 env.set_colours([&](kmer_t kmer) {
                     const auto it = std::lower_bound(canon.begin(), canon.end(), kmer);
                     const unsigned m = mask[order[(size_t)(it - canon.begin())].second];
@@ -300,14 +310,41 @@ static void fmt_phase(const Options &o, const std::string &name, const std::vect
             }
         }
     };
+    auto run_pool = [&] {
+        next = 0;
+        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+        const uint64_t n_threads = std::max<uint64_t>(1, std::min<uint64_t>(o.processors > 0 ? (uint64_t)o.processors : std::min(hw, 16u), todo.size()));
+        std::vector<std::thread> pool;
+        for (uint64_t t = 1; t < n_threads; t++) pool.emplace_back(work);
+        work();
+        for (auto &th : pool) th.join();
+        if (!err.empty()) throw Error(err);
+    };
     if (res.n_components) write_file(out_dir + "/comp0.gfa", "");  // (the directory, made once before the threads write into it)
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const uint64_t n_threads = std::max<uint64_t>(1, std::min<uint64_t>(o.processors > 0 ? (uint64_t)o.processors : std::min(hw, 16u), res.n_components));
-    std::vector<std::thread> pool;
-    for (uint64_t t = 1; t < n_threads; t++) pool.emplace_back(work);
-    work();
-    for (auto &th : pool) th.join();
-    if (!err.empty()) throw Error(err);
+    run_pool();
+    if (!abandoned.empty()) {
+        // what the host gave up goes to the device in one call, and the pool runs over it again
+        std::sort(abandoned.begin(), abandoned.end());
+        std::vector<uint64_t> hi, lo, off{0};
+        for (const uint64_t c : abandoned) {
+            wo_at[c] = off.back();
+            wo_comp[c] = off.size() - 1;
+            hi.insert(hi.end(), res.hi + res.comp_offsets[c], res.hi + res.comp_offsets[c + 1]);
+            lo.insert(lo.end(), res.lo + res.comp_offsets[c], res.lo + res.comp_offsets[c + 1]);
+            off.push_back(lo.size());
+        }
+        MC_CHECK(G.c, mc_walk_order(G.c, hi.data(), lo.data(), off.data(), abandoned.size(), 0, &wo));
+        todo = abandoned;
+    }
+    std::string line = "Replayed the walks of " + std::to_string(all_gpu ? 0 : res.n_components - abandoned.size()) + " components on the host, " +
+                       std::to_string(all_gpu ? res.n_components : abandoned.size()) + " on the GPU (mc_walk_order)";
+    if (!abandoned.empty()) {
+        line += "; the host's queue passed its cap on";
+        for (size_t i = 0; i < abandoned.size() && i < 8; i++) line += " comp" + std::to_string(abandoned[i]);
+        if (abandoned.size() > 8) line += " ...";
+    }
+    info(line);
+    if (!abandoned.empty()) run_pool();
 }
 
 int run_fmt_visualizer(const Options &o)

@@ -65,6 +65,13 @@ class ReadCov(C.Structure):
     _fields_ = [("sum", C.c_int32), ("covered", C.c_int32), ("last", C.c_int16), ("found", C.c_uint8), ("pad", C.c_uint8)]
 
 
+class _WalkOrder(C.Structure):
+    """mc_walk_order_result"""
+    _fields_ = [("n_components", C.c_uint64), ("n_kmers", C.c_uint64), ("reached", C.POINTER(C.c_uint64)), ("order", C.POINTER(C.c_uint32)),
+                ("twice", C.POINTER(C.c_uint8)), ("levels", C.c_uint64), ("queue_entries", C.c_uint64), ("wide_levels", C.c_uint64),
+                ("device_ms", C.c_double)]
+
+
 class _Components(C.Structure):
     """mc_components_result"""
     _fields_ = [("n_components", C.c_uint64), ("n_kmers", C.c_uint64), ("comp_offsets", C.POINTER(C.c_uint64)),
@@ -113,6 +120,7 @@ SEQ_COV_MAX_TABLES = 4  # mc_seq_coverage
 PRESENCE_MAX_TABLES = 4  # mc_kmer_presence
 RENDER_MAX_STREAMS, RENDER_SKIP, RENDER_UNNUMBERED = 16, 0xFF, 2**64 - 1  # mc_render_fastq
 RENDER_EMPTY, RENDER_QUALITY, RENDER_STREAM = 1, 2, 3  # mc_render_result.error
+WALK_ORDER_WIDE_ONLY, WALK_ORDER_NARROW_8 = 1, 2  # mc_walk_order flags (tests only): every level grid-wide; W = 8
 READS_IN_SET_WEAK_FILTER = 1  # mc_reads_in_set flags (tests only): no bit filter, every window is looked up in the set's table
 
 
@@ -130,6 +138,7 @@ EXPORTS = [
     "mc_kmer_presence", "mc_kmer_presence_dev", "mc_reads_in_set", "mc_reads_in_set_dev",
     "mc_components", "mc_components_dev", "mc_components_free", "mc_unitigs", "mc_unitigs_dev", "mc_unitigs_free",
     "mc_env_join", "mc_env_join_dev", "mc_env_join_free", "mc_trim_paths", "mc_trim_paths_dev",
+    "mc_walk_order", "mc_walk_order_dev", "mc_walk_order_free",
     "mc_kmers_encode_dev", "mc_kmers_decode_dev", "mc_save_kmers_gpu", "mc_load_kmers_gpu",
     "mc_tokenize_whole", "mc_tokenize_whole_dev", "mc_whole_text_bytes", "mc_whole_reads_to_host", "mc_whole_reads_free", "mc_reads_append_dev",
     "mc_render_fastq", "mc_render_fastq_dev", "mc_render_fastq_bound",
@@ -252,6 +261,11 @@ def load():
     if hasattr(L, "mc_trim_paths"):
         L.mc_trim_paths.argtypes = [vp, u64p, u64p, C.POINTER(C.c_uint8), u64, i32, C.POINTER(C.c_uint8), C.POINTER(C.c_double)]
         L.mc_trim_paths_dev.argtypes = [vp, vp, vp, vp, u64, i32, vp, C.POINTER(C.c_double)]
+    if hasattr(L, "mc_walk_order"):
+        L.mc_walk_order.argtypes = [vp, u64p, u64p, u64p, u64, C.c_uint32, C.POINTER(_WalkOrder)]
+        L.mc_walk_order_dev.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, C.POINTER(_WalkOrder)]
+        L.mc_walk_order_free.argtypes = [C.POINTER(_WalkOrder)]
+        L.mc_walk_order_free.restype = None
     if hasattr(L, "mc_tokenize_whole"):
         wr = C.POINTER(_WholeReads)
         L.mc_tokenize_whole.argtypes = [vp, C.c_char_p, u64, i32, i32, C.c_uint32, wr]
@@ -701,6 +715,14 @@ class Context:
         """mc_trim_paths_dev: see the module's trim_paths_dev()"""
         return trim_paths_dev(self, d_hi, d_lo, d_last, n, dir, d_kept)
 
+    def walk_order(self, hi, lo, comp_offsets, flags=0):
+        """mc_walk_order: see the module's walk_order()"""
+        return walk_order(self, hi, lo, comp_offsets, flags)
+
+    def walk_order_dev(self, d_hi, d_lo, d_comp_offsets, n_components, flags=0):
+        """mc_walk_order_dev: see the module's walk_order_dev()"""
+        return walk_order_dev(self, d_hi, d_lo, d_comp_offsets, n_components, flags)
+
     def env_join(self, hi, lo, rec_hi, rec_lo, rec_depth, graph_offsets, gene_words=None, gene_len=0):
         """mc_env_join: see the module's env_join()"""
         return env_join(self, hi, lo, rec_hi, rec_lo, rec_depth, graph_offsets, gene_words, gene_len)
@@ -891,6 +913,48 @@ def trim_paths_dev(context, d_hi, d_lo, d_last, n, dir, d_kept):
     ms = C.c_double(0)
     context._chk(load().mc_trim_paths_dev(context._h, _dptr(d_hi), _dptr(d_lo), _dptr(d_last), int(n), int(dir), _dptr(d_kept), C.byref(ms)))
     return float(ms.value)
+
+
+def _walk_order_result(r):
+    """the library's arrays as numpy arrays of our own, and the library's freed"""
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+    try:
+        nc, nk = int(r.n_components), int(r.n_kmers)
+        return {"n_components": nc, "n_kmers": nk, "reached": arr(r.reached, nc, np.uint64), "order": arr(r.order, nk, np.uint32),
+                "twice": arr(r.twice, nk, np.uint8), "levels": int(r.levels), "queue_entries": int(r.queue_entries),
+                "wide_levels": int(r.wide_levels), "device_ms": float(r.device_ms)}
+    finally:
+        load().mc_walk_order_free(C.byref(r))
+
+
+def walk_order(context, hi, lo, comp_offsets, flags=0):
+    """mc_walk_order: for every component of a components() result (its hi, lo and comp_offsets as they are; hi may be None when k <= 32;
+    member comp_offsets[c] is component c's seed), the order in which KmerEnvCalculator.runBfs pops its members for the first time and
+    which of them it pops again.  Returns a dict: reached (a component: the members the walk pops), order (a member: the first
+    reached[c] places of a slice hold member numbers relative to the slice in first-pop order, the seed first), twice (a member: 1 when
+    its put value ends as 0), levels, queue_entries, wide_levels (summed over the components), n_components, n_kmers, device_ms.
+    flags: WALK_ORDER_* (tests only; the result does not depend on them).  Needs no table."""
+    lo = np.ascontiguousarray(lo, dtype=np.uint64)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64) if hi is not None else None
+    comp_offsets = np.ascontiguousarray(comp_offsets, dtype=np.uint64)
+    n_comp = max(len(comp_offsets) - 1, 0)
+    if hi is not None and len(hi) != len(lo):
+        raise ValueError("hi and lo need one entry a k-mer")
+    if n_comp and int(comp_offsets[n_comp]) < (1 << 30) and int(comp_offsets.max()) > len(lo):
+        raise ValueError("comp_offsets runs past the k-mers")
+    r = _WalkOrder()
+    context._chk(load().mc_walk_order(context._h, _p(hi, C.c_uint64) if hi is not None else None, _p(lo, C.c_uint64), _p(comp_offsets, C.c_uint64),
+                                      n_comp, int(flags), C.byref(r)))
+    return _walk_order_result(r)
+
+
+def walk_order_dev(context, d_hi, d_lo, d_comp_offsets, n_components, flags=0):
+    """mc_walk_order_dev: d_hi (may be None when k <= 32) and d_lo hold a uint64 a k-mer, d_comp_offsets n_components + 1; the result
+    comes back as walk_order's does"""
+    r = _WalkOrder()
+    context._chk(load().mc_walk_order_dev(context._h, _dptr(d_hi), _dptr(d_lo), _dptr(d_comp_offsets), int(n_components), int(flags), C.byref(r)))
+    return _walk_order_result(r)
 
 
 def _env_join_result(r):
